@@ -21,8 +21,13 @@ no data-path collective; the line at N = 1 and at N = 8 names the same config.wo
 its wavefront stays as large as the single GPU's (the scaling proxy of round 4 says why). The timed region ends with the RCCL gather of the half4 tiles to
 rank 0 and the scatter kernel that assembles the frame. `--weak` is the opt-in of rounds 1-4: N x 64 accumulations per step, per-GPU work fixed.
 
-Rank 0 prints ONE JSON line of under 4 KB (`compact_line`: the contract keys, config, roofline, roofline_valu, cpu_baseline and nothing else -- round 4's
-25 KB line could not be parsed by the driver) and writes everything measured to `bench_details.json` (--details) and, as one line, to stderr. The details carry the contract keys plus
+A plain run does what the headline figure needs and nothing more: it sets up, warms up, times exactly `--steps` steps and prints the line (the contract keys,
+config and the timed region's own kernel_ms_per_step). `--full` adds every other measurement and check listed below -- they take runs of their own, and every
+--no-* option still skips its part. `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (`captured_outputs`); a plain and a --full run
+of the same arguments compute the same frames.
+
+Rank 0 prints ONE JSON line of under 4 KB (`compact_line`: the contract keys, config and, where measured, roofline, roofline_valu, cpu_baseline and nothing else -- round 4's
+25 KB line could not be parsed by the driver) and writes everything measured to `bench_details.json` (--details) and, as one line, to stderr. With --full the details carry the contract keys plus
   roofline          the kernel with the largest total time. `traffic` = bytes that crossed the L2's memory side per launch, from rocprofv3 counters:
                     (2 * FETCH_SIZE + WRITE_SIZE) * 1024, measured by child runs of this workload under `rocprofv3 --pmc` before the timed run (fallback:
                     profiles/pmc_traffic.json), calibrated on this renderer's access patterns (profiles/r03_fetch_calibration.txt); launches of the
@@ -60,6 +65,8 @@ import subprocess
 import sys
 import time
 from pathlib import Path
+
+import numpy as np
 
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
@@ -112,6 +119,11 @@ def parse_args(argv=None):
     p.add_argument("--details", default=None, help="where the full record goes (default: bench_details.json next to this script; the compact line on stdout names it)")
     p.add_argument("--no-exact-mode", action="store_true", help="skip the exact arithmetic leg (config.exact_mode)")
     p.add_argument("--no-textured", action="store_true", help="skip the textured / cut-out atrium leg (config.workload_textured)")
+    p.add_argument("--full", action="store_true", help="everything beyond the headline figure: the per-ray counting passes, live counter passes and rooflines, the one-wavefront "
+                   "and retrace legs, RMSE and exact-mode legs, other workloads, scaling proxy, plugin / denoiser figures, CPU baselines and the N > 1 proof (each --no-* "
+                   "option still skips its part). Without it a run sets up, warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, "
+                   "under 64 MB in all): the half4 frame as float32 and, at N = 1, a fixed sample of the f64 running mean")
     return p.parse_args(argv)
 
 
@@ -223,6 +235,27 @@ def kernel_bench_name(kernel: str):
     return None
 
 
+PARENT_RUN_OPTIONS = ("--steps", "--warmup", "--gpus", "--pmc-traffic", "--cpu-baseline-seconds", "--master-port", "--spawn-deadline", "--wavefronts", "--dump-outputs")
+
+
+def counter_pass_arguments(argv):
+    """The workload arguments of this run for its counter passes (`measure_traffic_live`): without the options that shape the parent run (PARENT_RUN_OPTIONS, given
+    as `--option value` or `--option=value`) -- the passes set their own steps, warm-up and wavefronts, and dump nothing."""
+    passthrough = []
+    skip = 0
+    for a in argv:
+        if skip:
+            skip -= 1
+            continue
+        if a in PARENT_RUN_OPTIONS:
+            skip = 1
+            continue
+        if a.split("=")[0] in PARENT_RUN_OPTIONS:
+            continue
+        passthrough.append(a)
+    return passthrough
+
+
 def measure_traffic_live(argv):
     """roofline.traffic measured by THIS run: two child processes, `rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE` (TCC has four counter slots: the two
     cannot share a pass, MI355X_MICROARCH.md "rocprofv3 PMC slots"), each running this script's workload for 2 steps, started before this process has
@@ -239,18 +272,7 @@ def measure_traffic_live(argv):
     rocprof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(rocprof):
         return {}, {"error": "rocprofv3 not found"}
-    passthrough = []
-    skip = 0
-    for i, a in enumerate(argv):        # the workload arguments, without the ones that shape the parent run
-        if skip:
-            skip -= 1
-            continue
-        if a in ("--steps", "--warmup", "--gpus", "--pmc-traffic", "--cpu-baseline-seconds", "--master-port", "--spawn-deadline", "--wavefronts"):
-            skip = 1
-            continue
-        if a.split("=")[0] in ("--steps", "--warmup", "--gpus", "--pmc-traffic", "--cpu-baseline-seconds", "--master-port", "--spawn-deadline", "--wavefronts"):
-            continue
-        passthrough.append(a)
+    passthrough = counter_pass_arguments(argv)
     totals = {}
     rate_kernels = {}
     t0 = time.perf_counter()
@@ -765,8 +787,43 @@ def scaling_proxy(ctx, scene, bounces, args, device, t1_ms):
     return proxy
 
 
-def measure(ctx, scene, scene_name, bounces, args, rank, world, device, steps, warmup, sync):
-    """Instrumented passes (per-ray node / triangle counts), warmup, then exactly `steps` timed steps. Returns the figures of this rank."""
+DUMP_FRAME_BYTES = 48 << 20         # --dump-outputs: the float32 frame whole up to this size, a fixed sample of its pixels beyond
+DUMP_ACCUMULATION_PIXELS = 1 << 18  # and 8 MB of the f64 running mean: 64 MB in all at most
+DUMP_SEED = 0
+
+
+def sampled_pixels(pixels: np.ndarray, count: int) -> np.ndarray:
+    """`count` rows of a (pixels, channels) array, the same ones for the same frame size in every run (seeded, sorted); all of them when there are no more."""
+    if len(pixels) <= count:
+        return pixels
+    return pixels[np.sort(np.random.default_rng(DUMP_SEED).choice(len(pixels), count, replace=False))]
+
+
+def captured_outputs(ctx, frame, world) -> dict:
+    """What a caller of the timed path receives from its last step (rank 0, after the frame is complete): the half4 frame, exactly as float32, and at N = 1 the
+    context's f64 running mean (hipr_read_accumulation). Names map to arrays; larger ones are cut to a fixed sample of pixels (`sampled_pixels`)."""
+    image = frame.float().cpu().numpy()
+    outputs = {}
+    if image.nbytes <= DUMP_FRAME_BYTES:
+        outputs["frame"] = image
+    else:
+        outputs["frame_sample"] = sampled_pixels(image.reshape(-1, 4), DUMP_FRAME_BYTES // (4 * 4))
+    if world == 1:
+        outputs["accumulation_sample"] = sampled_pixels(ctx.read_accumulation().reshape(-1, 4), DUMP_ACCUMULATION_PIXELS)
+    return outputs
+
+
+def dump_outputs(outputs: dict, directory) -> None:
+    directory = Path(directory)
+    directory.mkdir(parents=True, exist_ok=True)
+    for name, array in outputs.items():
+        assert array.dtype in (np.float32, np.float64), (name, array.dtype)
+        np.save(directory / f"{name}.npy", array)
+
+
+def measure(ctx, scene, scene_name, bounces, args, rank, world, device, steps, warmup, sync, capture=False):
+    """Two opening passes (instrumented under --full: per-ray node / triangle counts), warmup, then exactly `steps` timed steps. Returns the figures of this rank;
+    with `capture`, rank 0's result["outputs"] holds what the last timed step computed (`dump_outputs`)."""
     import torch
     import torch.distributed as dist
     from bifrost3d_amd import capi, distributed
@@ -822,7 +879,9 @@ def measure(ctx, scene, scene_name, bounces, args, rank, world, device, steps, w
             ctx.scatter_tiles(gathered.data_ptr(), n_compact, world, W, H, frame.data_ptr(), W)
             ctx.synchronize()
 
-    ctx.set_instrumentation(True)
+    # The opening passes run in every mode, so that the timed steps continue the same sequence of accumulations -- and the frame of the last one is the same --
+    # with and without --full; only --full counts the per-ray work (the roofline's figures).
+    ctx.set_instrumentation(args.full)
     ctx.reset_counters()
     for a in (0, S):
         run_pass(a)
@@ -860,6 +919,7 @@ def measure(ctx, scene, scene_name, bounces, args, rank, world, device, steps, w
 
     ctx.synchronize()
     counters, times = ctx.counters(), ctx.kernel_times()
+    outputs = captured_outputs(ctx, frame, world) if capture and rank == 0 else None
     if args.pmc_child:
         ctx.valu_issue_rates()      # calibration kernels of the SQ pass: their instruction count is known by construction
     stats = torch.tensor([elapsed, counters["closest_rays"], counters["shadow_rays"], counters["camera_rays"]], dtype=torch.float64, device=device)
@@ -875,13 +935,15 @@ def measure(ctx, scene, scene_name, bounces, args, rank, world, device, steps, w
     total = {"closest_rays": float(stats[1]), "shadow_rays": float(stats[2]), "camera_rays": float(stats[3])}
     result = {"elapsed": elapsed, "total": total, "counters": counters, "times": times, "per_ray": per_ray, "S": S, "gather_ms": gather_ms, "passes": steps_run, "steps_per_pass": batch,
               "rank_elapsed": [float(t[0]) for t in per_rank] if world > 1 else [elapsed]}
+    if outputs is not None:
+        result["outputs"] = outputs
     if rank == 0:
         result["frame_ok"] = bool(torch.isfinite(frame.float()).all().item()) and float(frame[..., :3].float().mean()) > 0
         result["small"] = ctx.trace_variant() == capi.TRACE_EXHAUSTIVE
         result["fused"] = ctx.trace_is_fused()
         result["wide8"] = ctx.trace_variant() == capi.TRACE_WIDE8_PERSISTENT
     result["wavefronts"] = ctx.wavefront_count()
-    if world == 1 and result.get("wide8") and not args.pmc_child and not getattr(args, "under_profiler", False) and not getattr(args, "alone_leg", False) and not getattr(args, "skip_retrace", False):      # kept out of profiled runs: their per-kernel averages are the line's own launches
+    if args.full and world == 1 and result.get("wide8") and not args.pmc_child and not getattr(args, "under_profiler", False) and not getattr(args, "alone_leg", False) and not getattr(args, "skip_retrace", False):      # kept out of profiled runs: their per-kernel averages are the line's own launches
         # The same frames with every refused closest hit retraced, as the reference does it (hipr_set_backface_culling 0): a short run beside the line's own,
         # for the ray count and the time the stepping saves. Outside the timed region.
         ctx.set_backface_culling(False)
@@ -1056,17 +1118,18 @@ def compact_line(full: dict, details_path=None) -> dict:
     if isinstance(config.get("verify_build"), dict):
         c["verify_build"] = _pick(config["verify_build"], ("frame", "spp", "pixels_bit_identical_to_oracle", "rmse_vs_oracle", "product_vs_verify_rmse", "product_vs_verify_compare_rms", "error"))
     line["config"] = c
-    roofline = full.get("roofline") or {}
-    r = _pick(roofline, ("bound", "peak", "unit", "avg_launch_ms", "launches", "traffic", "achieved", "frac", "algorithmic_bytes_per_launch", "achieved_model", "frac_model",
-                         "traffic_over_useful", "write_amplification", "limiter"))
-    r["kernel"] = text(roofline.get("kernel"), 160)
-    r["frac_basis"] = text(roofline.get("frac_basis"), 120)
-    if isinstance(roofline.get("traffic_source"), dict):
-        source = roofline["traffic_source"]
-        r["traffic_source"] = text(source.get("measured") or source.get("file"), 120)
-    if isinstance(roofline.get("measured_copy_bandwidth"), dict):
-        r["copy_GBps"] = roofline["measured_copy_bandwidth"].get("GB/s")
-    line["roofline"] = r
+    roofline = full.get("roofline")
+    if isinstance(roofline, dict):      # measured by --full runs only
+        r = _pick(roofline, ("bound", "peak", "unit", "avg_launch_ms", "launches", "traffic", "achieved", "frac", "algorithmic_bytes_per_launch", "achieved_model", "frac_model",
+                             "traffic_over_useful", "write_amplification", "limiter"))
+        r["kernel"] = text(roofline.get("kernel"), 160)
+        r["frac_basis"] = text(roofline.get("frac_basis"), 120)
+        if isinstance(roofline.get("traffic_source"), dict):
+            source = roofline["traffic_source"]
+            r["traffic_source"] = text(source.get("measured") or source.get("file"), 120)
+        if isinstance(roofline.get("measured_copy_bandwidth"), dict):
+            r["copy_GBps"] = roofline["measured_copy_bandwidth"].get("GB/s")
+        line["roofline"] = r
     valu = full.get("roofline_valu")
     if isinstance(valu, dict):
         v = _pick(valu, ("bound", "achieved", "peak", "unit", "frac", "lanes_per_instruction", "valu_busy"))
@@ -1160,7 +1223,7 @@ def main():
     live_traffic = None
     under_profiler = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")
     args.under_profiler = under_profiler
-    if args.gpus == 1 and args.pmc_traffic == "auto" and not args.scene_file and not under_profiler:     # no profiler inside a profiler
+    if args.full and args.gpus == 1 and args.pmc_traffic == "auto" and not args.scene_file and not under_profiler:     # no profiler inside a profiler
         live_traffic = measure_traffic_live(sys.argv[1:])
         if not live_traffic[0]:
             sys.stderr.write(f"bench.py: live counter passes unavailable ({live_traffic[1]}); falling back to profiles/pmc_traffic.json\n")
@@ -1204,10 +1267,12 @@ def main():
     bounces = args.bounces if args.bounces is not None else default_bounces
     ctx = Context(device_index)
     ctx.set_stream(torch.cuda.current_stream(device).cuda_stream)
-    result = measure(ctx, scene, scene_name, bounces, args, rank, world, device, args.steps, args.warmup, sync)
+    result = measure(ctx, scene, scene_name, bounces, args, rank, world, device, args.steps, args.warmup, sync, capture=args.dump_outputs is not None)
+    if "outputs" in result:
+        dump_outputs(result.pop("outputs"), args.dump_outputs)
 
     alone = None
-    if world == 1 and result["wavefronts"] > 1 and not args.pmc_child:
+    if args.full and world == 1 and result["wavefronts"] > 1 and not args.pmc_child:
         # The timed region ran co-running wavefronts: its per-launch HIP-event durations are those of kernels sharing the device. The rooflines price a KERNEL:
         # two more steps with one wavefront -- every kernel alone on the device, HIP events on its launch stream -- right after the timed region, the same
         # shape the counter passes and the committed rocprofv3 --stats profile run in.
@@ -1217,7 +1282,7 @@ def main():
         alone = measure(ctx, scene, scene_name, bounces, alone_args, 0, 1, device, 2, 1, sync)
         ctx.set_wavefront_count(args.wavefronts)
     proof = None
-    if world > 1:
+    if args.full and world > 1:
         try:
             proof = ranks_proof(ctx, scene, bounces, args, rank, world, device)
         except Exception as e:      # the timed line stands without it (a failure here is the same on every rank: library versions, properties torch does not expose)
@@ -1244,8 +1309,10 @@ def main():
                        "closest_rays": main_figures["closest_rays"], "shadow_rays": main_figures["shadow_rays"], "pixel_samples": main_figures["pixel_samples"],
                        "frame_finite_and_lit": main_figures["frame_finite_and_lit"], "library_sha16": library_sha16(), "workload_version": WORKLOAD_VERSION,
                        "rmse_note": "no OptiX image exists or can be produced here (DESIGN.md); rmse_vs_oracle compares with the pinned CPU oracle at equal spp and seed"},
-            "roofline": main_figures["roofline"], "roofline_by_kernel": main_figures["roofline_by_kernel"], "kernel_ms_per_step": main_figures["kernel_ms_per_step"],
+            "kernel_ms_per_step": main_figures["kernel_ms_per_step"],
         }
+        if args.full:
+            out["roofline"], out["roofline_by_kernel"] = main_figures["roofline"], main_figures["roofline_by_kernel"]
         if "kernel_ms_per_step_alone" in main_figures:
             out["kernel_ms_per_step_alone"] = main_figures["kernel_ms_per_step_alone"]
             out["kernel_ms_per_step_note"] = "kernel_ms_per_step sums HIP-event durations of launches that overlap the other wavefront's (it exceeds ms_per_step); kernel_ms_per_step_alone: one wavefront"
@@ -1262,7 +1329,7 @@ def main():
                             "note": "ms_per_step per rank = that rank's own clock over the timed region (the line's ms_per_step is the maximum); gather_ms = rank 0's time in the "
                                     "final gather of the half4 tiles + the scatter kernel, inside the timed region"}
             out["ranks"].update(proof or {})
-        if world == 1 and not args.pmc_child:
+        if args.full and world == 1 and not args.pmc_child:
             # the VALU roof beside the HBM one, and the bytes the dominant kernel could not avoid
             dominant = max(main_figures["roofline_by_kernel"], key=lambda n: main_figures["roofline_by_kernel"][n]["total_ms"])
             entry = main_figures["roofline_by_kernel"][dominant]
@@ -1283,7 +1350,7 @@ def main():
             out["roofline"]["limiter"] = ("valu" if out["roofline_valu"].get("valu_busy", 0) >= 0.6 else "see roofline_valu") if "error" not in out["roofline_valu"] else None
             if not args.no_scaling_proxy and not args.scene_file and not under_profiler:
                 out["scaling_proxy"] = scaling_proxy(ctx, scene, bounces, args, device, main_figures["ms_per_step"])
-        if world == 1:
+        if args.full and world == 1:
             copy_gbs = measured_copy_bandwidth(device)
             out["roofline"]["measured_copy_bandwidth"] = {"GB/s": copy_gbs, "what": "1 GiB device-to-device copy, bytes read + written, best of five (torch)",
                                                           "frac_of_copy": out["roofline"]["achieved"] / copy_gbs if out["roofline"].get("achieved") else None}

@@ -89,8 +89,9 @@ def test_the_line_the_driver_parses_is_small_and_round_trips():
         text = json.dumps(line, allow_nan=False)
         assert len(text) < bench.LINE_LIMIT == 4096, len(text)
         assert "\n" not in text and json.loads(text) == line
-        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
             assert key in line, key
+        assert ("roofline" in line) == ("roofline" in record)      # the roofline of a --full record; a plain run's line has none, not a hollow one
         assert line["metric"] == json.loads((ROOT / "BASELINE.json").read_text())["metric"] and "workload" in line["config"] and "model" not in line["config"]
     line = bench.compact_line(full)
     assert line["value"] == float(f"{full['value']:.6g}") and line["config"]["ms_per_256spp_frame"] == float(f"{full['config']['ms_per_256spp_frame']:.6g}")
@@ -141,3 +142,57 @@ def test_the_round_6_records_keep_their_new_keys_in_the_compact_line():
     ranks = bench.compact_line(two)["ranks"]
     assert ranks["world_seen"] == {"get_world_size": 2, "all_reduce_of_ones": 2} and len(ranks["devices"]) == 2 and ranks["tile_split_probe_identical"] is True
     assert isinstance(ranks["rccl_version"], str) and ranks["backend"] == "gloo" and len(json.dumps(bench.compact_line(two), allow_nan=False)) < bench.LINE_LIMIT
+
+
+def test_plain_runs_by_default_and_outputs_are_dumped_as_fixed_float_samples(tmp_path):
+    """--full is off by default; --dump-outputs writes float32 / float64 .npy files, a larger output as the same seeded sample of pixels in every run, and the
+    counter passes of a --full run (child processes of the same workload, `counter_pass_arguments`) are not handed the dump directory."""
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import bench
+    args = bench.parse_args(["--steps", "5"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 5
+    assert bench.parse_args(["--full", "--dump-outputs", str(tmp_path)]).full is True
+    pixels = np.arange(4000 * 4, dtype=np.float64).reshape(-1, 4)
+    a, b = bench.sampled_pixels(pixels, 100), bench.sampled_pixels(pixels.copy(), 100)
+    assert a.shape == (100, 4) and np.array_equal(a, b) and np.all(np.diff(a[:, 0]) > 0)
+    assert bench.sampled_pixels(pixels, 4000) is pixels
+    bench.dump_outputs({"frame": pixels.astype(np.float32), "accumulation_sample": a}, tmp_path / "out")
+    assert np.array_equal(np.load(tmp_path / "out" / "frame.npy"), pixels.astype(np.float32)) and np.load(tmp_path / "out" / "accumulation_sample.npy").dtype == np.float64
+    assert bench.DUMP_FRAME_BYTES + bench.DUMP_ACCUMULATION_PIXELS * 4 * 8 <= 64 << 20
+    # the counter passes of a --full run get the workload, not the options of the parent run: no dump directory, steps or wavefronts of their own
+    argv = ["--full", "--scene", "atrium", "--dump-outputs", str(tmp_path / "d"), "--steps", "20", "--warmup=5", "--width", "640", "--dump-outputs=x", "--wavefronts", "2"]
+    assert bench.counter_pass_arguments(argv) == ["--full", "--scene", "atrium", "--width", "640"]
+
+
+def test_captured_outputs_sample_a_frame_over_its_budget():
+    """captured_outputs on the host (a CPU tensor for the device frame, a stand-in context): a frame within DUMP_FRAME_BYTES whole and exact, a larger one as the seeded
+    sample of its pixels, the f64 running mean sampled at N = 1 only, and 64 MB in all at most."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    class Context:
+        def __init__(self, h, w):
+            self.accumulation = np.random.default_rng(1).random((h, w, 4))
+
+        def read_accumulation(self):
+            return self.accumulation
+
+    small = torch.from_numpy(np.random.default_rng(2).random((90, 160, 4)).astype(np.float16))
+    out = bench.captured_outputs(Context(90, 160), small, 1)
+    assert set(out) == {"frame", "accumulation_sample"} and out["frame"].dtype == np.float32 and np.array_equal(out["frame"], small.numpy().astype(np.float32))
+    assert np.array_equal(out["accumulation_sample"], Context(90, 160).accumulation.reshape(-1, 4))      # 14 400 pixels: all of them
+    h, w = 1800, 1800      # 51.8 MB as float32: over the budget
+    assert h * w * 16 > bench.DUMP_FRAME_BYTES
+    large = torch.from_numpy(np.random.default_rng(3).random((h, w, 4)).astype(np.float16))
+    ctx = Context(h, w)
+    out = bench.captured_outputs(ctx, large, 1)
+    assert set(out) == {"frame_sample", "accumulation_sample"}
+    frame_sample, accumulation_sample = out["frame_sample"], out["accumulation_sample"]
+    assert frame_sample.dtype == np.float32 and frame_sample.shape == (bench.DUMP_FRAME_BYTES // 16, 4) and accumulation_sample.shape == (bench.DUMP_ACCUMULATION_PIXELS, 4)
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert np.array_equal(frame_sample, bench.sampled_pixels(large.numpy().astype(np.float32).reshape(-1, 4), bench.DUMP_FRAME_BYTES // 16))
+    assert np.array_equal(accumulation_sample, bench.sampled_pixels(ctx.accumulation.reshape(-1, 4), bench.DUMP_ACCUMULATION_PIXELS))
+    assert set(bench.captured_outputs(ctx, large, 2)) == {"frame_sample"}       # N > 1: a rank's running mean holds its tiles only

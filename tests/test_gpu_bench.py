@@ -14,12 +14,13 @@ SMALL = ["--width", "640", "--height", "360", "--atrium-triangles", "20000", "--
          "--no-other-workloads", "--no-rmse", "--no-plugin", "--no-cpu-baseline"]
 
 
-def run_bench(extra, tmp_path=None, extra_env=None):
-    """Returns (the one line of stdout, the full record of --details)."""
+def run_bench(extra, tmp_path=None, extra_env=None, full=True):
+    """Returns (the one line of stdout, the full record of --details). `full`: with --full, the measurements beyond the headline figure these tests check."""
     import tempfile
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", **(extra_env or {}))
     details = Path(tempfile.mkdtemp(prefix="hipr_bench_")) / "details.json"
-    done = subprocess.run([sys.executable, str(ROOT / "bench.py")] + SMALL + extra + ["--details", str(details)], capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
+    done = subprocess.run([sys.executable, str(ROOT / "bench.py")] + SMALL + (["--full"] if full else []) + extra + ["--details", str(details)], capture_output=True, text=True,
+                          timeout=600, env=env, cwd=str(ROOT))
     assert done.returncode == 0, done.stderr[-2000:]
     lines = [text for text in done.stdout.splitlines() if text.strip()]
     assert len(lines) == 1, lines          # ONE JSON line on stdout, everything else on stderr
@@ -62,6 +63,51 @@ def test_bench_line_contract_single_gpu():
     assert "backface_culling" in line["config"]
     assert 1.05 * line["config"]["rays_per_step"] < retrace["rays_per_step"] < 1.3 * line["config"]["rays_per_step"]
     assert retrace["ms_per_step"] > 1.03 * line["ms_per_step"] and retrace["Mrays_per_s"] > 0
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_what_they_computed(tmp_path):
+    """Without --full the line holds the headline figure and nothing measured by runs of its own; --dump-outputs writes the last timed step's frame (the half4
+    frame as float32) and a fixed sample of the f64 running mean, and the same arguments with --full compute the same frame, bit for bit."""
+    compact, plain = run_bench(["--steps", "3", "--dump-outputs", str(tmp_path / "plain")], full=False)
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert key in compact and key in plain, key
+    assert plain["steps"] == 3 and plain["unit"] == "Mrays/s" and plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["higher_is_better"] is True
+    assert plain["config"]["frame_finite_and_lit"] and plain["config"]["spp_total"] == 3 * plain["config"]["spp_per_step"]
+    assert plain["config"]["pixel_samples"] == 3 * 640 * 360 * 4          # camera rays counted in the timed region: 3 steps of 4 accumulations of the frame
+    for key in ("roofline_valu", "retrace_mode", "scaling_proxy", "cpu_baseline", "other_workloads", "roofline_by_kernel", "kernel_ms_per_step_alone"):
+        assert key not in plain, key
+    assert "exact_mode" not in plain["config"] and "workload_textured" not in plain["config"]
+    assert "roofline" not in plain and "roofline" not in compact          # no roofline measured, none shown
+    import numpy as np
+    frame = np.load(tmp_path / "plain" / "frame.npy")
+    sample = np.load(tmp_path / "plain" / "accumulation_sample.npy")
+    assert frame.dtype == np.float32 and frame.shape == (360, 640, 4) and np.isfinite(frame).all() and frame[..., :3].mean() > 0
+    assert sample.dtype == np.float64 and sample.shape == (640 * 360, 4) and np.isfinite(sample).all()
+    # 230 400 pixels: the sample is every pixel, and the frame is the running mean rounded to half
+    assert np.allclose(frame.reshape(-1, 4)[:, :3], sample[:, :3], rtol=1e-3, atol=1e-6)
+    _, full = run_bench(["--steps", "3", "--no-textured", "--no-scaling-proxy", "--no-exact-mode", "--pmc-traffic", "off", "--dump-outputs", str(tmp_path / "full")])
+    assert "roofline_by_kernel" in full and full["config"]["rays_per_step"] == plain["config"]["rays_per_step"]
+    assert np.array_equal(np.load(tmp_path / "full" / "frame.npy"), frame) and np.array_equal(np.load(tmp_path / "full" / "accumulation_sample.npy"), sample)
+    # the dump is the LAST timed step: the same scene rendered here pass by pass -- two opening passes, one warm-up step, three timed steps, 4 accumulations
+    # each -- gives the dumped running mean and frame after the sixth pass, and not after the fifth
+    import torch
+    from bifrost3d_amd.host import Scene
+    from bifrost3d_amd.renderer import Context
+    scene = Scene("atrium", param0=20000, param1=1)
+    ctx = Context(0)
+    try:
+        ctx.upload_scene(scene)
+        ctx.set_wavefront_count(0)
+        ctx.set_frame(640, 360, 0, 1, 4)
+        mine = torch.zeros((360, 640, 4), dtype=torch.float16, device="cuda:0")
+        torch.cuda.synchronize()
+        for k in range(6):
+            if k == 5:
+                assert not np.array_equal(ctx.read_accumulation().reshape(-1, 4), sample)
+            ctx.render_pass(scene.camera(640, 360, accumulations=4 * k, max_bounce_count=4), mine.data_ptr(), 640, synchronize=True)
+        assert np.array_equal(ctx.read_accumulation().reshape(-1, 4), sample) and np.array_equal(mine.float().cpu().numpy(), frame)
+    finally:
+        ctx.close()
 
 
 def test_bench_two_ranks_on_one_device():

@@ -5,7 +5,7 @@
 set -u
 export HIPR_LIBRARY=$(pwd)/bifrost3d_amd/csrc/libhiprenderer_sort.so
 root=$(pwd); out=$root/gpurun_out/r4sort; mkdir -p $out; export TMPDIR=/tmp
-quiet="--no-cpu-baseline --no-other-workloads --no-plugin --no-scaling-proxy --no-rmse"
+quiet="--full --no-cpu-baseline --no-other-workloads --no-plugin --no-scaling-proxy --no-rmse"
 python -m pytest tests/test_gpu_coverage.py -m gpu -q -k "order_the_trace_kernel" 2>&1 | tail -3
 for sort in 0 1; do
   for wf in 1 2; do

@@ -33,7 +33,7 @@ for scene, key in KEYS.items():
     if line:
         json.loads(line)   # must be the one JSON line
         (profiles / f"{tag}_{scene}_bench_under_rocprof.json").write_text(line + "\n")
-    command = f"rocprofv3 --pmc {{FETCH_SIZE|WRITE_SIZE}} -- python3 bench.py --no-cpu-baseline --no-other-workloads --no-rmse --no-plugin --scene {scene} --steps 4 --warmup 1"
+    command = f"rocprofv3 --pmc {{FETCH_SIZE|WRITE_SIZE}} -- python3 bench.py --full --no-cpu-baseline --no-other-workloads --no-rmse --no-plugin --scene {scene} --steps 4 --warmup 1"
     subprocess.run([sys.executable, str(ROOT / "tools" / "make_pmc_traffic.py"), key, str(d / "pmc_fetch"), str(d / "pmc_write"), command], check=True)
 
 # ---- SQ / cache counters of the atrium ---------------------------------------------------------------------------------

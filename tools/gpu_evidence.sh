@@ -2,7 +2,7 @@
 # The evidence run of a round on the GPU box, one runner for every round (replaces the per-round job scripts):
 #   tools/gpu_evidence.sh <tag> [part ...]        e.g. gpurun -- 'bash tools/gpu_evidence.sh r04 bench stats tests'
 # parts (default: all, in this order)
-#   bench     the default `python bench.py` line (what the driver runs)
+#   bench     the `python bench.py --full` line (the default workload with every measurement beside the headline figure)
 #   stats     rocprofv3 --kernel-trace --stats of the same workload with ONE wavefront (every kernel alone on the device: the durations the bench line's
 #             rooflines are priced on; the timed region of the default line runs two co-running wavefronts whose launches overlap)
 #   workloads the other BASELINE configurations (material, cornell_diffuse, the textured atrium, 10 M triangles at 4K, 1 spp per pass, two ranks on one device)
@@ -19,12 +19,12 @@ root=$(pwd)
 out=$root/gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-quiet="--no-cpu-baseline --no-other-workloads --no-plugin --no-scaling-proxy"
+quiet="--full --no-cpu-baseline --no-other-workloads --no-plugin --no-scaling-proxy"
 for part in $parts; do
     case $part in
     bench)
-        python bench.py --details $out/bench_details.json > $out/bench_default.json 2> $out/bench_default.err; wc -c $out/bench_default.json; tail -c 600 $out/bench_default.json
-        python3 bench.py --gpus 1 --steps 20 --warmup 5 --details $out/bench_driver_command_details.json > $out/bench_driver_command.json 2> $out/bench_driver_command.err ;;
+        python bench.py --full --details $out/bench_details.json > $out/bench_default.json 2> $out/bench_default.err; wc -c $out/bench_default.json; tail -c 600 $out/bench_default.json
+        python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --details $out/bench_driver_command_details.json > $out/bench_driver_command.json 2> $out/bench_driver_command.err ;;
     stats)
         cd /tmp
         timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $root/bench.py $quiet --no-rmse --no-textured --pmc-traffic off --wavefronts 1 --details $out/bench_under_rocprof_details.json > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err
@@ -36,7 +36,7 @@ for part in $parts; do
         done
         python bench.py --atrium-triangles 10000000 --width 3840 --height 2160 --spp-per-pass 8 --steps 4 --warmup 1 $quiet --details $out/bench_atrium10M_4k_details.json > $out/bench_atrium10M_4k.json 2> $out/bench_atrium10M_4k.err
         python bench.py --spp-per-pass 1 --steps 64 --warmup 8 $quiet --no-rmse --details $out/bench_atrium_1spp_details.json > $out/bench_atrium_1spp.json 2> $out/bench_atrium_1spp.err
-        python bench.py --gpus 2 --share-device --dist-backend gloo --steps 4 --warmup 1 --no-rmse --details $out/bench_2rank_gloo_shared_device_details.json > $out/bench_2rank_gloo_shared_device.json 2> $out/bench_2rank.err ;;
+        python bench.py --gpus 2 --share-device --dist-backend gloo --steps 4 --warmup 1 --full --no-rmse --details $out/bench_2rank_gloo_shared_device_details.json > $out/bench_2rank_gloo_shared_device.json 2> $out/bench_2rank.err ;;
     rmse)
         timeout 1800 python tools/rmse_protocol.py --size 480x270 --decay-to 1024 --out $out/rmse_protocol_480x270.json > $out/rmse_480.log 2>&1
         timeout 900 python tools/rmse_protocol.py --size 160x90 --decay-to 4096 --out $out/rmse_protocol_160x90.json > $out/rmse_160.log 2>&1 ;;
