@@ -323,6 +323,22 @@ int hipr_group_update_scene_geometry(HiprGroup* g, const HiprSceneDesc* scene) {
     return for_each_member(g, [&](Member& m, uint32_t) { return hipr_update_scene_geometry(m.context, scene); });
 }
 
+int hipr_group_refit_scene_transforms(HiprGroup* g, const HiprInstanceTransform* moved, uint32_t moved_count, const HiprLight* lights, uint32_t light_count, HiprRefitResult* out) {
+    if (!g || !out) return HIPR_ERROR_INVALID_ARGUMENT;
+    std::vector<HiprRefitResult> results(g->members.size());
+    const int status = for_each_member(g, [&](Member& m, uint32_t index) { return hipr_refit_scene_transforms(m.context, moved, moved_count, lights, light_count, &results[index]); });
+    if (status) return status;
+    *out = results.empty() ? HiprRefitResult() : results[0];
+    for (const HiprRefitResult& r : results)      // the members ran the same kernels on the same arrays
+        if (std::memcmp(&r.child_half_area, &out->child_half_area, sizeof(double)) || std::memcmp(r.grid_min, out->grid_min, sizeof(r.grid_min)) ||
+            std::memcmp(r.grid_cell, out->grid_cell, sizeof(r.grid_cell)) || r.needs_rebuild != out->needs_rebuild) {
+            hipr_internal_set_last_error("hipr_group_refit_scene_transforms: the members' refits disagree");
+            fprintf(stderr, "hiprenderer: hipr_group_refit_scene_transforms: the members' refits disagree\n");
+            return HIPR_ERROR_HIP;
+        }
+    return HIPR_OK;
+}
+
 int hipr_group_set_scene_state(HiprGroup* g, const HiprSceneState* state) {
     if (!g) return HIPR_ERROR_INVALID_ARGUMENT;
     for (Member& m : g->members)

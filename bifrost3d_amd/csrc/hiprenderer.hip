@@ -10,6 +10,7 @@
 #define HIPR_WIDE8_LOW_BUCKET 0
 #endif
 #include "wide8_kernels.h"
+#include "wide8_refit.h"
 #include "launch.h"
 
 #include <hip/hip_runtime.h>
@@ -144,6 +145,15 @@ struct HiprContext {
     int shading_models = 7;             // bit mask of the shading models the scene's instances reference
     std::vector<HiprMaterial> uploaded_materials;      // host copies of what hipr_upload_scene put on the device: a refit (hipr_update_scene_geometry) leaves the material pool
     std::vector<uint32_t> uploaded_light_types;        // and the environment data as they are, so what is derived from them must come from THESE, not from the refit's description
+
+    // device refit of the 8-wide tree (wide8_refit.h, hipr_refit_scene_transforms); filled at upload for scenes that bring the tree
+    DeviceBuffer refit_leaf_slots, refit_node_slots, refit_exact, refit_moved, refit_partial, refit_scratch;
+    std::vector<uint32_t> refit_level_begin;           // refit_node_slots[level_begin[l], level_begin[l + 1]) = the nodes l levels below the root
+    uint32_t refit_leaf_count = 0;
+    std::vector<uint32_t> refit_node_list, refit_node_words;      // host copy of refit_node_slots and each node's (base_valid, inner_mask) at the time: the topology the lists hold
+    std::vector<HiprInstance> uploaded_instances;      // host copy of the instances on the device: a device refit checks a new matrix's handedness against them
+    double uploaded_half_area = 0.0, current_half_area = 0.0;
+    bool tree_stale = false;                           // a device refit left the BVH2 and 4-wide arrays behind: hipr_set_trace_variant refuses them until the next upload / geometry update
 
     // frame
     FrameInfo frame = {};
@@ -953,6 +963,106 @@ int build_derived_geometry(HiprContext* c, const HiprSceneDesc* s, bool pools_up
     return HIPR_OK;
 }
 
+// ---- device refit (wide8_refit.h) -------------------------------------------------------------------------------------------------------------------------
+// refit_scratch: [0, 48) the six reduced bounds, [48, 52) the rebuild flag, [64, 72) the area sum.
+constexpr size_t REFIT_SCRATCH_FLAG = 48, REFIT_SCRATCH_AREA = 64, REFIT_SCRATCH_BYTES = 128;
+
+// Queues passes 2 - 4 on the context's stream. WRITE = false: exact boxes and area only (the slots stay as uploaded).
+template <bool WRITE>
+void queue_refit_tree(HiprContext* c, const float* grid_min, const float* grid_cell) {
+    hipStream_t st = c->stream;
+    HiprSlot8* slots = c->wide8_slots.as<HiprSlot8>();
+    RefitBox* exact = c->refit_exact.as<RefitBox>();
+    char* scratch = c->refit_scratch.as<char>();
+    const uint32_t slot_count = c->wide8.slot_count;
+    if (c->refit_leaf_count)
+        hipLaunchKernelGGL((k_refit_leaves<WRITE>), dim3((c->refit_leaf_count + REFIT_BLOCK - 1) / REFIT_BLOCK), dim3(REFIT_BLOCK), 0, st, slots, c->refit_leaf_slots.as<uint32_t>(), c->refit_leaf_count,
+                           c->triangles.as<HiprTriangle>(), exact, reinterpret_cast<uint32_t*>(scratch + REFIT_SCRATCH_FLAG));
+    for (size_t level = c->refit_level_begin.size() - 1; level-- > 0;) {      // deepest first: a launch per level is the only ordering there is
+        const uint32_t begin = c->refit_level_begin[level], count = c->refit_level_begin[level + 1] - begin;
+        if (!count) continue;
+        hipLaunchKernelGGL((k_refit_nodes<WRITE>), dim3((count + REFIT_BLOCK - 1) / REFIT_BLOCK), dim3(REFIT_BLOCK), 0, st, slots, c->refit_node_slots.as<uint32_t>() + begin, count, exact,
+                           grid_min[0], grid_min[1], grid_min[2], grid_cell[0], grid_cell[1], grid_cell[2]);
+    }
+    const uint32_t blocks = (slot_count + REFIT_BLOCK - 1) / REFIT_BLOCK;
+    hipLaunchKernelGGL(k_refit_area, dim3(blocks), dim3(REFIT_BLOCK), 0, st, exact, slot_count, c->refit_partial.as<double>());
+    hipLaunchKernelGGL(k_refit_area_final, dim3(1), dim3(REFIT_BLOCK), 0, st, c->refit_partial.as<double>(), blocks, reinterpret_cast<double*>(scratch + REFIT_SCRATCH_AREA));
+}
+
+// After an upload (`new_topology`) or a geometry update of a scene with the 8-wide tree: the slot lists by kind and level, the host copy of the instances and the
+// half area the tree starts with, taken by the kernels that take it after a refit.
+int prepare_refit(HiprContext* c, const HiprSceneDesc* s, bool new_topology) {
+    c->tree_stale = false;
+    if (c->wide8.slot_count == 0) {
+        c->uploaded_instances.clear();
+        c->refit_level_begin.clear();
+        c->refit_node_list.clear();
+        c->refit_node_words.clear();
+        c->refit_leaf_count = 0;
+        c->uploaded_half_area = c->current_half_area = 0.0;
+        return HIPR_OK;
+    }
+    c->uploaded_instances.assign(s->instances, s->instances + s->instance_count);
+    const uint32_t slot_count = c->wide8.slot_count;
+    hipStream_t st = c->stream;
+    // A geometry update promises the uploaded topology, and hipr_update_scene_geometry has only compared counts and heights: the lists are kept when every node they
+    // name carries the topology words they were made from -- from the root down that is the same tree, slot for slot -- and made again otherwise, so that the
+    // leaf kernel never takes a node slot for a leaf record.
+    if (!new_topology) {
+        new_topology = c->refit_node_list.empty() || c->refit_node_words.size() != c->refit_node_list.size() * 2;
+        for (size_t i = 0; i < c->refit_node_list.size() && !new_topology; ++i) {
+            const HiprNode8& n = s->wide8_slots[c->refit_node_list[i]].node;
+            new_topology = n.base_valid != c->refit_node_words[2 * i] || n.inner_mask != c->refit_node_words[2 * i + 1];
+        }
+    }
+    if (new_topology) {
+        std::vector<uint32_t> nodes = {0u}, leaves;
+        nodes.reserve(slot_count / 4 + 1);
+        leaves.reserve(slot_count);
+        c->refit_level_begin.assign(1, 0u);
+        for (size_t begin = 0; begin < nodes.size();) {      // the tree was validated: every child slot is in range and has one parent
+            const size_t end = nodes.size();
+            c->refit_level_begin.push_back(uint32_t(end));
+            for (size_t i = begin; i < end; ++i) {
+                const HiprNode8& n = s->wide8_slots[nodes[i]].node;
+                const uint32_t base = n.base_valid & 0xFFFFFFu, valid = n.base_valid >> 24;
+                uint32_t rank = 0;
+                for (int p = 0; p < 8; ++p) {
+                    if (!(valid >> p & 1u)) continue;
+                    const uint32_t child = base + rank++;
+                    if (n.inner_mask >> p & 1u) nodes.push_back(child); else leaves.push_back(child);
+                }
+            }
+            begin = end;
+        }
+        c->refit_leaf_count = uint32_t(leaves.size());
+        c->refit_node_list.clear();      // the host copies describe what the device holds: set together, once the uploads below are through
+        c->refit_node_words.clear();
+        const size_t triangle_blocks = (size_t(s->triangle_count) + REFIT_BLOCK - 1) / REFIT_BLOCK, slot_blocks = (size_t(slot_count) + REFIT_BLOCK - 1) / REFIT_BLOCK;
+        int r = 0;
+        r |= c->refit_node_slots.upload(nodes.data(), nodes.size() * 4, st);
+        r |= c->refit_leaf_slots.upload(leaves.data(), leaves.size() * 4, st);
+        r |= c->refit_exact.resize(size_t(slot_count) * sizeof(RefitBox));
+        r |= c->refit_moved.resize(std::max<size_t>(s->instance_count, 1) * 4);
+        r |= c->refit_partial.resize(std::max(triangle_blocks * 6 * sizeof(RefitBound), slot_blocks * sizeof(double)));
+        r |= c->refit_scratch.resize(REFIT_SCRATCH_BYTES);
+        if (r) return r < 0 ? r : HIPR_ERROR_HIP;
+        HIP_TRY(hipStreamSynchronize(st));      // the upload reads the lists
+        c->refit_node_words.resize(nodes.size() * 2);
+        for (size_t i = 0; i < nodes.size(); ++i) {
+            c->refit_node_words[2 * i] = s->wide8_slots[nodes[i]].node.base_valid;
+            c->refit_node_words[2 * i + 1] = s->wide8_slots[nodes[i]].node.inner_mask;
+        }
+        c->refit_node_list = std::move(nodes);
+    }
+    queue_refit_tree<false>(c, c->wide8.grid_min, c->wide8.grid_cell);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&c->uploaded_half_area, c->refit_scratch.as<char>() + REFIT_SCRATCH_AREA, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c->current_half_area = c->uploaded_half_area;
+    return HIPR_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1048,7 +1158,7 @@ int hipr_destroy(HiprContext* c) {
     if (!c) return HIPR_OK;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    DeviceBuffer* all[] = {&c->shade_triangles, &c->trace_triangles, &c->trace_items, &c->wide_nodes, &c->wide8_slots, &c->environment_PDF, &c->environment_samples, &c->nodes, &c->triangles, &c->instances, &c->indices, &c->geometry, &c->texcoords, &c->tints, &c->emissions, &c->materials,
+    DeviceBuffer* all[] = {&c->refit_leaf_slots, &c->refit_node_slots, &c->refit_exact, &c->refit_moved, &c->refit_partial, &c->refit_scratch, &c->shade_triangles, &c->trace_triangles, &c->trace_items, &c->wide_nodes, &c->wide8_slots, &c->environment_PDF, &c->environment_samples, &c->nodes, &c->triangles, &c->instances, &c->indices, &c->geometry, &c->texcoords, &c->tints, &c->emissions, &c->materials,
                            &c->lights, &c->textures, &c->texels, &c->ggx_rho, &c->dielectric_rho, &c->alpha, &c->sample_offsets, &c->sobol_tables, &c->radiance, &c->radiance_other,
                            &c->accumulation, &c->scratch_accumulation, &c->counters, &c->work_counters, &c->debug_a, &c->debug_b, &c->debug_c};
     for (DeviceBuffer* b : all) b->release();
@@ -1179,6 +1289,7 @@ int hipr_upload_scene(HiprContext* c, const HiprSceneDesc* s) {
     d.light_count = s->light_count;
     if (int status = build_derived_geometry(c, s, true)) return status;
     if (int status = upload_wide8(c, s, wide8_height)) return status;
+    if (int status = prepare_refit(c, s, true)) return status;
     c->choose_variant();
     c->stack_size = s->bvh_max_depth <= 16 ? 16 : (s->bvh_max_depth <= 32 ? 32 : 64);
     int models = 0;
@@ -1238,7 +1349,100 @@ int hipr_update_scene_geometry(HiprContext* c, const HiprSceneDesc* s) {
     int models = 0;   // the instances were re-uploaded: a changed material_index may reference another shading model -- of the material pool the DEVICE holds
     for (uint32_t i = 0; i < s->instance_count; ++i) models |= 1 << std::min<int>(c->uploaded_materials[s->instances[i].material_index].shading_model, 2);
     c->shading_models = models ? models : 7;
-    return build_derived_geometry(c, s, false);
+    if (int status = build_derived_geometry(c, s, false)) return status;
+    return prepare_refit(c, s, false);      // also ends the state a device refit left (hipr_refit_scene_transforms)
+}
+
+int hipr_refit_scene_transforms(HiprContext* c, const HiprInstanceTransform* moved, uint32_t moved_count, const HiprLight* lights, uint32_t light_count, HiprRefitResult* out) {
+    if (int st = check_context(c)) return st;
+    if (!out || (moved_count && !moved)) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_refit_scene_transforms: null argument");
+    if (!c->scene_ready) return fail(HIPR_ERROR_NOT_READY, "hipr_refit_scene_transforms: no scene uploaded");
+    const DeviceScene& d = c->scene;
+    // Scenes that are not traced through the 8-wide tree have at most 64 BVH2 nodes (or a tree too high for the kernels, or a search forced for an experiment): the
+    // host path costs nothing there, and the arrays their search walks are the ones this call leaves stale. The exhaustive search's items are built on the host.
+    if (c->wide8.slot_count == 0 || !c->use_wide8() || d.trace_item_count != 0 || d.triangle_count > 0x55555555u)
+        return fail(HIPR_ERROR_UNSUPPORTED, "hipr_refit_scene_transforms: the uploaded scene is not traced through the 8-wide tree; refit on the host and call hipr_update_scene_geometry");
+    for (uint32_t k = 0; k < moved_count; ++k) {
+        if (moved[k].instance_index >= c->uploaded_instances.size())
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_refit_scene_transforms: instance %u of %zu", moved[k].instance_index, c->uploaded_instances.size());
+        for (int e = 0; e < 12; ++e)
+            if (!std::isfinite(moved[k].object_to_world[e])) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_refit_scene_transforms: the matrix of instance %u is not finite", moved[k].instance_index);
+        // A mirrored instance is drawn from index triples of its own (two corners exchanged): that changes the triangle array, which stays the host path's business.
+        if (refit_mirrors(moved[k].object_to_world) != refit_mirrors(c->uploaded_instances[moved[k].instance_index].object_to_world))
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_refit_scene_transforms: the matrix of instance %u changes its handedness; refit on the host", moved[k].instance_index);
+    }
+    if (lights) {
+        if (light_count != d.light_count) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_refit_scene_transforms: %u lights given, the uploaded scene has %u", light_count, d.light_count);
+        for (uint32_t l = 0; l < light_count; ++l)
+            if ((lights[l].flags & HIPR_LIGHT_TYPE_MASK) != c->uploaded_light_types[l])
+                return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_refit_scene_transforms: light %u changes its type (%u -> %u); upload the scene instead", l, c->uploaded_light_types[l], lights[l].flags & HIPR_LIGHT_TYPE_MASK);
+    }
+    if (int finish_status = finish_all(c)) return finish_status;      // no pending pass may go on over the new geometry
+    hipStream_t st = c->stream;
+    *out = {};
+    if (lights && light_count) {
+        if (int r = c->lights.upload(lights, size_t(light_count) * sizeof(HiprLight), st)) return r;
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (moved_count) {
+        std::vector<uint32_t> flags(c->uploaded_instances.size(), 0u);
+        std::vector<HiprInstance> instances = c->uploaded_instances;      // becomes the context's copy once the device holds it (after the last synchronise)
+        for (uint32_t k = 0; k < moved_count; ++k) {
+            std::memcpy(instances[moved[k].instance_index].object_to_world, moved[k].object_to_world, sizeof(moved[k].object_to_world));
+            flags[moved[k].instance_index] = 1u;
+        }
+        HIP_TRY(hipMemcpyAsync(c->instances.ptr, instances.data(), instances.size() * sizeof(HiprInstance), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->refit_moved.ptr, flags.data(), flags.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(c->refit_scratch.ptr, 0, REFIT_SCRATCH_BYTES, st));
+        // pass 1: world-space triangles and the scene's bounds
+        const uint32_t blocks = (d.triangle_count + REFIT_BLOCK - 1) / REFIT_BLOCK;
+        hipLaunchKernelGGL(k_refit_triangles, dim3(blocks), dim3(REFIT_BLOCK), 0, st, c->triangles.as<HiprTriangle>(), d.triangle_count, c->instances.as<HiprInstance>(), c->refit_moved.as<uint32_t>(),
+                           c->indices.as<uint32_t>(), c->geometry.as<HiprVertexGeometry>(), c->refit_partial.as<RefitBound>());
+        hipLaunchKernelGGL(k_refit_bounds_final, dim3(1), dim3(REFIT_BLOCK), 0, st, c->refit_partial.as<RefitBound>(), blocks, c->refit_scratch.as<RefitBound>());
+        HIP_TRY(hipGetLastError());
+        RefitBound bounds[6];
+        HIP_TRY(hipMemcpyAsync(bounds, c->refit_scratch.ptr, sizeof(bounds), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));      // `flags` and the instances are read by now as well
+        const float lo[3] = {bounds[0].v, bounds[1].v, bounds[2].v}, hi[3] = {bounds[3].v, bounds[4].v, bounds[5].v};
+        float grid_min[3], grid_cell[3];
+        refit_grid(lo, hi, grid_min, grid_cell);      // the moved scene's bounds: node origins must not be clamped at the ends of a stale grid
+        // passes 2 - 4, then the records derived from the triangles
+        queue_refit_tree<true>(c, grid_min, grid_cell);
+        hipLaunchKernelGGL(k_build_shade_triangles, dim3((d.triangle_count + 255) / 256), dim3(256), 0, st, d, c->shade_triangles.as<float4>());
+        hipLaunchKernelGGL(k_build_trace_triangles, dim3((d.triangle_count + 255) / 256), dim3(256), 0, st, d.triangles, d.triangle_count, c->trace_triangles.as<float4>());
+        HIP_TRY(hipGetLastError());
+        struct { uint32_t flag; uint32_t pad[3]; double area; } tail = {};
+        static_assert(REFIT_SCRATCH_AREA - REFIT_SCRATCH_FLAG == 16, "the flag and the area are read back together");
+        HIP_TRY(hipMemcpyAsync(&tail, c->refit_scratch.as<char>() + REFIT_SCRATCH_FLAG, sizeof(tail), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        c->uploaded_instances.swap(instances);
+        c->tree_stale = true;
+        for (int a = 0; a < 3; ++a) { c->wide8.grid_min[a] = grid_min[a]; c->wide8.grid_cell[a] = grid_cell[a]; }
+        c->current_half_area = tail.area;
+        if (tail.flag) {      // a pair parted: this tree cannot hold the scene any more
+            c->scene_ready = false;
+            out->needs_rebuild = 1;
+        }
+    }
+    out->child_half_area = c->current_half_area;
+    out->uploaded_half_area = c->uploaded_half_area;
+    for (int a = 0; a < 3; ++a) { out->grid_min[a] = c->wide8.grid_min[a]; out->grid_cell[a] = c->wide8.grid_cell[a]; }
+    return HIPR_OK;
+}
+
+int hipr_debug_read_scene_buffer(HiprContext* c, int which, void* out, uint64_t capacity_bytes) {
+    if (int st = check_context(c)) return st;
+    if (!out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: null output");
+    if (c->scene.triangle_count == 0 && c->wide8.slot_count == 0) return fail(HIPR_ERROR_NOT_READY, "hipr_debug_read_scene_buffer: no scene uploaded");
+    const void* from = nullptr;
+    uint64_t bytes = 0;
+    if (which == HIPR_SCENE_BUFFER_TRIANGLES) { from = c->triangles.ptr; bytes = uint64_t(c->scene.triangle_count) * sizeof(HiprTriangle); }
+    else if (which == HIPR_SCENE_BUFFER_WIDE8_SLOTS) { from = c->wide8_slots.ptr; bytes = uint64_t(c->wide8.slot_count) * sizeof(HiprSlot8); }
+    else return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: unknown buffer %d", which);
+    if (capacity_bytes < bytes) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: %llu bytes needed, %llu given", (unsigned long long)bytes, (unsigned long long)capacity_bytes);
+    if (int finish_status = finish_all(c)) return finish_status;
+    if (bytes) HIP_TRY(hipMemcpy(out, from, bytes, hipMemcpyDeviceToHost));
+    return HIPR_OK;
 }
 
 int hipr_set_scene_state(HiprContext* c, const HiprSceneState* state) {
@@ -1549,6 +1753,8 @@ int hipr_get_trace_variant(HiprContext* c, int* out_variant) {
 int hipr_set_trace_variant(HiprContext* c, int variant) {
     if (!c) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null context");
     if (variant < -1 || variant > HIPR_TRACE_WIDE8_PERSISTENT) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_set_trace_variant: unknown variant %d", variant);
+    if (c->tree_stale && (variant == HIPR_TRACE_BVH2 || variant == HIPR_TRACE_WIDE_PERSISTENT))
+        return fail(HIPR_ERROR_UNSUPPORTED, "hipr_set_trace_variant: the BVH2 and 4-wide arrays are stale after hipr_refit_scene_transforms; call hipr_update_scene_geometry or hipr_upload_scene first");
     c->trace_variant = variant;     // the exhaustive search's items are built at upload: upload the scene after this call
     return HIPR_OK;
 }

@@ -27,6 +27,9 @@ def load_host_library() -> C.CDLL:
     lib.hiprh_png_load.restype = C.c_size_t
     lib.hiprh_make_camera.argtypes = [C.POINTER(C.c_float), C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(capi.HiprCameraState)]
     lib.hiprh_scene_move_model.argtypes = [vp, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_double]
+    lib.hiprh_scene_model_pose.argtypes = [vp, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_uint), C.POINTER(C.c_float), C.c_uint]
+    lib.hiprh_wide8_quantise_nodes.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_uint), C.POINTER(C.c_float), vp, C.c_uint]
+    lib.hiprh_wide8_quantise_nodes.restype = None
     lib.hiprh_scene_destroy.argtypes = [vp]
     lib.hiprh_scene_desc.argtypes = [vp]
     lib.hiprh_scene_desc.restype = C.POINTER(capi.HiprSceneDesc)
@@ -118,6 +121,22 @@ class Scene:
         if status < 0:
             raise capi.HiprError("hiprh_scene_move_model failed")
         return status == 1
+
+    def model_pose(self, model_index: int, translation, rotation=(0.0, 0.0, 0.0, 1.0), scale: float = 1.0) -> list:
+        """[(instance index, 3x4 object-to-world matrix)] of the model under the pose, for Context.refit_scene_transforms; the scene itself is not touched."""
+        t = (C.c_float * 3)(*translation)
+        r = (C.c_float * 4)(*rotation)
+        count = self.lib.hiprh_scene_model_pose(self.handle, model_index, t, r, scale, None, None, 0)
+        if count < 0:
+            raise capi.HiprError("hiprh_scene_model_pose failed")
+        indices = np.zeros(max(count, 1), np.uint32)
+        matrices = np.zeros((max(count, 1), 3, 4), np.float32)
+        self.lib.hiprh_scene_model_pose(self.handle, model_index, t, r, scale, indices.ctypes.data_as(C.POINTER(C.c_uint)), matrices.ctypes.data_as(C.POINTER(C.c_float)), count)
+        return [(int(indices[k]), matrices[k].copy()) for k in range(count)]
+
+    def wide8_slots(self) -> np.ndarray:
+        d = self.desc
+        return np.ctypeslib.as_array(C.cast(d.wide8_slots, C.POINTER(C.c_uint32)), shape=(d.wide8_slot_count, 16)).copy()
 
     def triangles(self) -> np.ndarray:
         d = self.desc

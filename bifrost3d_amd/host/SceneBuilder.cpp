@@ -277,8 +277,8 @@ void SceneBuilder::finalize(uint32_t bvh_max_depth) {
     d.environment = m_has_environment ? &m_environment : nullptr;
 }
 
-bool SceneBuilder::update_model_transforms(const std::vector<std::pair<uint32_t, Transform>>& model_transforms, double rebuild_threshold) {
-    std::vector<bool> moved(m_instances.size(), false);
+bool SceneBuilder::record_model_transforms(const std::vector<std::pair<uint32_t, Transform>>& model_transforms, std::vector<HiprInstanceTransform>* moved_instances) {
+    if (m_staged_moved.size() != m_instances.size()) m_staged_moved.assign(m_instances.size(), false);
     // Decided before anything is touched: does an update turn an instance inside out? Such an instance is drawn from its own index triples (two corners
     // exchanged, index_offset_for), so the triangle array is rebuilt from the instances -- with EVERY update of the batch applied first; the caller is told
     // "rebuilt" (false) and uploads a desc() that carries all the new poses.
@@ -289,8 +289,44 @@ bool SceneBuilder::update_model_transforms(const std::vector<std::pair<uint32_t,
                 Matrix3x4f m = to_matrix3x4(update.second);
                 flips = flips || mirrors(m.begin()) != mirrors(m_instances[i].object_to_world);
                 std::memcpy(m_instances[i].object_to_world, m.begin(), sizeof(m_instances[i].object_to_world));
-                moved[i] = true;
+                m_staged_moved[i] = true;
+                if (moved_instances) {
+                    HiprInstanceTransform t = {};
+                    t.instance_index = uint32_t(i);
+                    std::memcpy(t.object_to_world, m.begin(), sizeof(t.object_to_world));
+                    moved_instances->push_back(t);
+                }
             }
+    m_staged_flips = m_staged_flips || flips;
+    return !flips;
+}
+
+bool SceneBuilder::stage_model_transforms(const std::vector<std::pair<uint32_t, Transform>>& model_transforms, std::vector<HiprInstanceTransform>& moved_instances) {
+    const size_t before = moved_instances.size();
+    const bool no_flip = record_model_transforms(model_transforms, &moved_instances);
+    m_staged = m_staged || moved_instances.size() != before;
+    return no_flip;
+}
+
+void SceneBuilder::rebuild() {
+    m_staged = false; m_staged_flips = false;
+    m_staged_moved.assign(m_instances.size(), false);
+    for (size_t i = 0; i < m_instances.size(); ++i) m_instances[i].index_offset = index_offset_for(m_instance_mesh[i], m_instances[i].object_to_world);
+    finalize(m_bvh_max_depth_limit);
+}
+
+bool SceneBuilder::update_model_transforms(const std::vector<std::pair<uint32_t, Transform>>& model_transforms, double rebuild_threshold) {
+    record_model_transforms(model_transforms, nullptr);
+    m_staged = true;
+    return apply_staged_transforms(rebuild_threshold);
+}
+
+bool SceneBuilder::apply_staged_transforms(double rebuild_threshold) {
+    if (!m_staged) return true;
+    const std::vector<bool> moved = m_staged_moved;
+    const bool flips = m_staged_flips;
+    m_staged = false; m_staged_flips = false;
+    m_staged_moved.assign(m_instances.size(), false);
     if (flips) {
         for (size_t i = 0; i < m_instances.size(); ++i)
             if (moved[i]) m_instances[i].index_offset = index_offset_for(m_instance_mesh[i], m_instances[i].object_to_world);

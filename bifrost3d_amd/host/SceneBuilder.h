@@ -7,6 +7,7 @@
 #include "BvhBuilder.h"
 #include "Math.h"
 
+#include <cassert>
 #include <cstdint>
 #include <string>
 #include <utility>
@@ -75,14 +76,27 @@ public:
     // past `rebuild_threshold` times the built tree's (a badly stretched tree traverses slowly) the scene is rebuilt instead. Returns true when
     // the topology was kept (nodes, triangle order and counts unchanged: hipr_update_scene_geometry suffices), false after a rebuild.
     bool update_model_transforms(const std::vector<std::pair<uint32_t, Transform>>& model_transforms, double rebuild_threshold = 1.5);
+    // The same update in two steps, for a renderer whose device refits the tree itself (hipr_refit_scene_transforms): stage_model_transforms records the
+    // matrices in the instances, decides flips as update_model_transforms does and appends the instances it touched, with their 3x4 matrices, to
+    // `moved_instances` -- the triangles and the trees are NOT touched: while has_staged_transforms() holds, desc() and bounds() are those of the poses before.
+    // Whoever needs the description then (a new camera's upload, a rebuild, the fallback) calls apply_staged_transforms() first, which runs the code of
+    // update_model_transforms over everything staged; true = topology kept, false = the scene was rebuilt (a flip, the BVH2's ratio rule) and every holder
+    // of the old description needs the new one whole. stage_model_transforms returns false when an update turns an instance inside out (the device cannot
+    // refit that; apply_staged_transforms will rebuild). rebuild(): a fresh tree over the instances as they stand.
+    bool stage_model_transforms(const std::vector<std::pair<uint32_t, Transform>>& model_transforms, std::vector<HiprInstanceTransform>& moved_instances);
+    bool apply_staged_transforms(double rebuild_threshold = 1.5);
+    bool has_staged_transforms() const { return m_staged; }
+    void rebuild();
+    const std::vector<HiprLight>& lights() const { return m_lights; }
+    const std::vector<HiprInstance>& instances() const { return m_instances; }
     // The lights of a finalized scene replaced one for one (moved or re-coloured lights; the count must match).
     bool replace_lights(const std::vector<HiprLight>& lights);
 
-    const HiprSceneDesc& desc() const { return m_desc; }
+    const HiprSceneDesc& desc() const { assert(!m_staged && "apply_staged_transforms() first: the instances lead the triangles and the trees"); return m_desc; }
     const HiprSceneState& state() const { return m_state; }
     HiprSceneState& state() { return m_state; }
     CameraDescription camera;
-    AABB bounds() const { return m_bounds; }
+    AABB bounds() const { assert(!m_staged && "apply_staged_transforms() first"); return m_bounds; }
     size_t mesh_count() const { return m_meshes.size(); }
     size_t model_count() const { return m_instances.size(); }
 
@@ -92,6 +106,9 @@ private:
     // them with the second and third corner exchanged, so that the world-space corners wind the way the reference's transformed geometric normal points
     // (rtTransformNormal through the inverse transpose, ORS/MonteCarlo.cu:147) and every consumer of the triple order sees the same triangle.
     uint32_t index_offset_for(uint32_t mesh, const float* object_to_world);
+    bool record_model_transforms(const std::vector<std::pair<uint32_t, Transform>>& model_transforms, std::vector<HiprInstanceTransform>* moved_instances);
+    bool m_staged = false, m_staged_flips = false;      // transforms recorded in m_instances that m_triangles / m_bvh do not carry yet
+    std::vector<bool> m_staged_moved;
     std::vector<MeshRecord> m_meshes;
     std::vector<uint32_t> m_indices;
     std::vector<HiprVertexGeometry> m_geometry;

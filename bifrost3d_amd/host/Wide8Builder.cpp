@@ -723,4 +723,14 @@ bool refit_wide8(Wide8Result& tree, const OrderedTriangles& triangles) {
     return true;
 }
 
+void quantise_wide8_node(const float* boxes_8x6, uint32_t valid, const float* grid_min, const float* grid_cell, HiprNode8& node) {
+    Box boxes[8], all; all.reset();
+    for (int s = 0; s < 8; ++s) {
+        if (!(valid >> s & 1u)) continue;
+        for (int a = 0; a < 3; ++a) { boxes[s].lo[a] = boxes_8x6[6 * s + a]; boxes[s].hi[a] = boxes_8x6[6 * s + 3 + a]; }
+        all.grow(boxes[s]);
+    }
+    Collapse::quantise_node(boxes, valid, all, grid_min, grid_cell, node);
+}
+
 } // namespace HIPRenderer

@@ -33,4 +33,8 @@ Wide8Result build_wide8(const std::vector<HiprBvhNode>& nodes, const OrderedTria
 // false: a paired record's shared corners are no longer bit-identical after the move -- the tree is stale and must be rebuilt (nothing else is wrong).
 bool refit_wide8(Wide8Result& tree, const OrderedTriangles& triangles_in_leaf_order);
 
+// The quantisation step of both on its own (tests: the device's restatement, csrc/wide8_refit.h, is held to it): the child boxes of the positions in `valid`
+// (lo xyz, hi xyz each), quantised on the node's grid as build_wide8 / refit_wide8 do. Writes origin, exponent, qlo and qhi of `node`.
+void quantise_wide8_node(const float* boxes_8x6, uint32_t valid, const float* grid_min, const float* grid_cell, HiprNode8& node);
+
 } // namespace HIPRenderer

@@ -318,6 +318,35 @@ int hiprh_scene_move_model(void* scene, unsigned model_index, const float* trans
     catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_move_model: %s\n", e.what()); return -1; }
 }
 
+// The instances model `model_index` is drawn by and the 3x4 object-to-world matrix the pose gives them -- what hipr_refit_scene_transforms takes -- WITHOUT moving
+// anything in the scene. Returns the number of instances (written up to `capacity`), -1 on bad arguments.
+int hiprh_scene_model_pose(void* scene, unsigned model_index, const float* translation3, const float* rotation4, float scale, unsigned* out_instance_indices, float* out_matrices_12, unsigned capacity) {
+    if (!scene || !translation3 || !rotation4) return -1;
+    const Transform t(Vector3f(translation3[0], translation3[1], translation3[2]), Bifrost::Math::Quaternionf(rotation4[0], rotation4[1], rotation4[2], rotation4[3]), scale);
+    const Bifrost::Math::Matrix3x4f m = Bifrost::Math::to_matrix3x4(t);
+    const std::vector<HiprInstance>& instances = static_cast<SceneBuilder*>(scene)->instances();
+    unsigned count = 0;
+    for (size_t i = 0; i < instances.size(); ++i)
+        if (uint32_t(instances[i].instance_id) == ((1u << 30) | model_index)) {
+            if (count < capacity && out_instance_indices && out_matrices_12) {
+                out_instance_indices[count] = unsigned(i);
+                std::memcpy(out_matrices_12 + 12 * size_t(count), m.begin(), 12 * sizeof(float));
+            }
+            ++count;
+        }
+    return int(count);
+}
+
+// Wide8Builder.cpp's quantise_node on one synthetic node (tests of csrc/wide8_refit.h's restatement).
+void hiprh_wide8_quantise_node(const float* boxes_8x6, unsigned valid, const float* grid_min3, const float* grid_cell3, HiprNode8* out) {
+    HIPRenderer::quantise_wide8_node(boxes_8x6, valid, grid_min3, grid_cell3, *out);
+}
+
+// `count` nodes at once: 48 floats of boxes, a valid mask, 6 floats of grid (min xyz, cell xyz) and a 64-byte node each.
+void hiprh_wide8_quantise_nodes(const float* boxes, const unsigned* valid, const float* grids, HiprNode8* out, unsigned count) {
+    for (unsigned i = 0; i < count; ++i) HIPRenderer::quantise_wide8_node(boxes + 48 * size_t(i), valid[i], grids + 6 * size_t(i), grids + 6 * size_t(i) + 3, out[i]);
+}
+
 void hiprh_scene_destroy(void* scene) { delete static_cast<SceneBuilder*>(scene); }
 
 const HiprSceneDesc* hiprh_scene_desc(void* scene) { return scene ? &static_cast<SceneBuilder*>(scene)->desc() : nullptr; }

@@ -70,6 +70,31 @@ class Context:
         self._scene = scene
         self._check(self.lib.hipr_update_scene_geometry(self.handle, C.byref(scene.desc)), "hipr_update_scene_geometry")
 
+    def refit_scene_transforms(self, moved=(), lights=None) -> dict:
+        """hipr_refit_scene_transforms: `moved` is a sequence of (instance index, 3x4 matrix) -- Scene.model_pose() -- refitted on the device; `lights`: None keeps the
+        lights, else a sequence of capi.HiprLight that replaces them one for one. Returns needs_rebuild, child_half_area, uploaded_half_area, grid_min, grid_cell."""
+        moved = list(moved)
+        array = (capi.HiprInstanceTransform * max(len(moved), 1))()
+        for k, (index, matrix) in enumerate(moved):
+            array[k].instance_index = int(index)
+            array[k].object_to_world[:] = [float(v) for v in np.asarray(matrix, np.float32).reshape(12)]
+        light_array, light_count = None, 0
+        if lights is not None:
+            lights = list(lights)
+            light_array, light_count = (capi.HiprLight * max(len(lights), 1))(*lights), len(lights)
+        result = capi.HiprRefitResult()
+        self._check(self.lib.hipr_refit_scene_transforms(self.handle, array, len(moved), light_array, light_count, C.byref(result)), "hipr_refit_scene_transforms")
+        return dict(needs_rebuild=bool(result.needs_rebuild), child_half_area=float(result.child_half_area), uploaded_half_area=float(result.uploaded_half_area),
+                    grid_min=np.array(result.grid_min[:], np.float32), grid_cell=np.array(result.grid_cell[:], np.float32))
+
+    def read_scene_buffer(self, which: int) -> np.ndarray:
+        """The scene array the device holds (hipr_debug_read_scene_buffer): capi.SCENE_BUFFER_TRIANGLES -> (triangles, 12) uint32 words, SCENE_BUFFER_WIDE8_SLOTS -> (slots, 16)."""
+        desc = self._scene.desc
+        rows, words = (desc.triangle_count, 12) if which == capi.SCENE_BUFFER_TRIANGLES else (desc.wide8_slot_count, 16)
+        out = np.zeros((rows, words), np.uint32)
+        self._check(self.lib.hipr_debug_read_scene_buffer(self.handle, int(which), C.c_void_p(out.ctypes.data), out.nbytes), "hipr_debug_read_scene_buffer")
+        return out
+
     def set_scene_state(self, state: capi.HiprSceneState):
         self._check(self.lib.hipr_set_scene_state(self.handle, C.byref(state)), "hipr_set_scene_state")
 

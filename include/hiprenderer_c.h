@@ -339,6 +339,30 @@ int hipr_validate_scene(const HiprSceneDesc* scene);
  * counts and tree topology must equal the uploaded scene's, and rebuilds the per-triangle records derived from them; meshes,
  * materials, textures, environment and tables stay as uploaded. */
 int hipr_update_scene_geometry(HiprContext* context, const HiprSceneDesc* scene);
+/* The same transform-only update WITHOUT the host refit and the re-upload (OR/Renderer.cpp:472,1010-1041: OptiX refits the root acceleration on the device too):
+ * the instances named in `moved` get new object-to-world matrices, and kernels recompute their world-space triangles from the resident object-space pools,
+ * rebuild the leaf records of the 8-wide tree, requantise its nodes level by level and rebuild the per-triangle records -- bit for bit what
+ * SceneBuilder::update_model_transforms + hipr_update_scene_geometry leave in those arrays (csrc/wide8_refit.h). `lights`: NULL keeps the lights, else
+ * `light_count` lights replace the uploaded ones one for one. Checked before anything on the device is touched:
+ *   HIPR_ERROR_UNSUPPORTED        the uploaded scene brings no 8-wide tree (at most 64 BVH2 nodes); OR the search the context walks is another one (a tree too
+ *                                 high for the 8-wide kernels, a variant forced with hipr_set_trace_variant): the arrays that search reads are the ones this call
+ *                                 leaves stale; OR the scene carries the exhaustive search's items, which only the host builds; OR it has more than 0x55555555
+ *                                 triangles (the corner ordinal 3 t + k that decides ties among equal bounds is 32 bits wide);
+ *   HIPR_ERROR_INVALID_ARGUMENT   an instance index out of range; a matrix with an entry that is not finite (the scene's bounds and with them the grid would not
+ *                                 be); a matrix whose handedness differs from the uploaded instance's (a mirrored instance has index triples of its own, which
+ *                                 the host path provides); a light count other than the uploaded one; a light that changes its type.
+ * Afterwards the BVH2 and 4-wide arrays on the device are stale: hipr_set_trace_variant to HIPR_TRACE_BVH2 / HIPR_TRACE_WIDE_PERSISTENT returns
+ * HIPR_ERROR_UNSUPPORTED until the next hipr_upload_scene or hipr_update_scene_geometry. */
+typedef struct HiprInstanceTransform { uint32_t instance_index; float object_to_world[12]; } HiprInstanceTransform;
+typedef struct HiprRefitResult {
+    int32_t needs_rebuild;        /* 1: a leaf record could not be refitted (two object-space vertices that shared a world position at build time parted); the
+                                     context's scene is no longer usable until hipr_upload_scene */
+    double  child_half_area;      /* sum over all child boxes of all 8-wide nodes after the refit (exact boxes; per box in f32, summed in f64 in a fixed shape) */
+    double  uploaded_half_area;   /* the same sum, taken by the same kernels when the scene was uploaded */
+    float   grid_min[3], grid_cell[3];      /* the 8-wide tree's grid over the moved scene's bounds (HiprSceneDesc::wide8_grid_*) */
+} HiprRefitResult;
+int hipr_refit_scene_transforms(HiprContext* context, const HiprInstanceTransform* moved, uint32_t moved_count,
+                                const HiprLight* lights /* NULL: keep */, uint32_t light_count, HiprRefitResult* out);
 int hipr_set_scene_state(HiprContext* context, const HiprSceneState* state);
 
 /* Entry points, numbered like OR/Types.h:33-44. set_backend() of the host renderer maps Backend values onto them
@@ -417,6 +441,8 @@ const char* hipr_group_gather_description(HiprGroup* group);   /* which transpor
 int hipr_group_upload_tables(HiprGroup* group, const HiprTables* tables);
 int hipr_group_upload_scene(HiprGroup* group, const HiprSceneDesc* scene);
 int hipr_group_update_scene_geometry(HiprGroup* group, const HiprSceneDesc* scene);
+int hipr_group_refit_scene_transforms(HiprGroup* group, const HiprInstanceTransform* moved, uint32_t moved_count,
+                                      const HiprLight* lights, uint32_t light_count, HiprRefitResult* out);   /* every member; their results must agree */
 int hipr_group_set_scene_state(HiprGroup* group, const HiprSceneState* state);
 int hipr_group_set_entry_point(HiprGroup* group, int entry);
 int hipr_group_use_scratch_accumulation(HiprGroup* group, int enable);
@@ -552,6 +578,9 @@ int hipr_debug_sample_offsets(HiprContext* context, float* out_256x4);
 int hipr_debug_trace_closest(HiprContext* context, const float* rays, const uint32_t* skip, uint32_t n, float* out_hits);
 /* K4: shadow transmittance for n rays (float4 origin_tmin + float4 direction_tmax) -> one float per ray. */
 int hipr_debug_trace_shadow(HiprContext* context, const float* rays, uint32_t n, float* out_transmittance);
+/* The uploaded (or device-refitted) scene arrays as the device holds them: HiprTriangle[triangle_count] or HiprSlot8[wide8_slot_count]. */
+enum { HIPR_SCENE_BUFFER_TRIANGLES = 0, HIPR_SCENE_BUFFER_WIDE8_SLOTS = 1 };
+int hipr_debug_read_scene_buffer(HiprContext* context, int which, void* out, uint64_t capacity_bytes);
 
 #ifdef __cplusplus
 }
