@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -49,9 +50,14 @@ int fail(int status, const char* fmt, ...) {
                         hipGetErrorString(err__), __FILE__, __LINE__);                                         \
     } while (0)
 
+// Device memory that goes with its owner: movable, not copyable.
 struct DeviceBuffer {
     void* ptr = nullptr;
     size_t bytes = 0;
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer&& other) noexcept : ptr(other.ptr), bytes(other.bytes) { other.ptr = nullptr; other.bytes = 0; }
+    DeviceBuffer& operator=(DeviceBuffer&& other) noexcept { std::swap(ptr, other.ptr); std::swap(bytes, other.bytes); return *this; }
+    ~DeviceBuffer() { release(); }
     int resize(size_t new_bytes) {
         if (new_bytes <= bytes && ptr) return HIPR_OK;
         if (ptr) { (void)hipFree(ptr); ptr = nullptr; bytes = 0; }
@@ -70,35 +76,42 @@ struct DeviceBuffer {
     template <typename T> T* as() const { return static_cast<T*>(ptr); }
 };
 
+// A stream, an event or pinned host memory that goes with its owner; reads as the plain handle wherever one is expected.
+template <typename T, hipError_t (*FREE)(T)>
+struct Owned {
+    T handle = nullptr;
+    Owned() = default;
+    Owned(Owned&& other) noexcept : handle(other.handle) { other.handle = nullptr; }
+    Owned& operator=(Owned&& other) noexcept { std::swap(handle, other.handle); return *this; }
+    ~Owned() { if (handle) (void)FREE(handle); }
+    operator T() const { return handle; }
+};
+hipError_t free_pinned_words(uint32_t* words) { return hipHostFree(words); }
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using PinnedWords = Owned<uint32_t*, free_pinned_words>;
+// Each leaves the owner empty when HIP refuses: the caller checks the handle.
+Stream make_stream() { Stream s; if (hipStreamCreateWithFlags(&s.handle, hipStreamNonBlocking) != hipSuccess) s.handle = nullptr; return s; }
+Event make_event(unsigned flags = hipEventDisableTiming) { Event e; if (hipEventCreateWithFlags(&e.handle, flags) != hipSuccess) e.handle = nullptr; return e; }
+PinnedWords make_pinned_words(size_t count) { PinnedWords p; if (hipHostMalloc((void**)&p.handle, count * sizeof(uint32_t)) != hipSuccess) p.handle = nullptr; return p; }
+
 struct TimedLaunch { int kernel; hipEvent_t start, stop; };
 
 // One independent wavefront of paths: its own queues, queue sizes and stream. A pass splits its path slots over the
 // context's wavefronts; they advance through their bounces independently, so while one of them shades (few resident
 // waves, waiting on gathers) the other one traces (many waves, latency bound) on the same CUs.
 struct Wavefront {
-    hipStream_t stream = nullptr;       // wavefront 0 runs on the context stream, the others on their own
-    hipStream_t own_stream = nullptr;
-    hipEvent_t shade_done[2] = {nullptr, nullptr}, counts_copied[2] = {nullptr, nullptr}, finished = nullptr;   // by bounce parity: two bounces are in flight
+    Stream own_stream;                  // first member: destroyed after the events and buffers below
+    hipStream_t stream = nullptr;       // borrowed: wavefront 0 runs on the context stream, the others on their own
+    Event shade_done[2], counts_copied[2], finished;   // by bounce parity: two bounces are in flight
     DeviceBuffer path[2][4], hits, shadow[3], queue_counts, order, order_coat, nee_flags, sort_keys[2], sort_order, sort_temp;     // sort_*: ray_sort.hip (HIPR_COHERENCE_SORT=1)   // queue_counts: COUNT_LINES 64 B lines (see there); order: k_classify_hits' listing of a bounce's rays
-    uint32_t* host_counts = nullptr;    // pinned: {continuing paths, shadow rays} per bounce parity, [4] staging word
+    PinnedWords host_counts;            // pinned: {continuing paths, shadow rays} per bounce parity, [4] staging word
     uint32_t first_slot = 0, n_slots = 0;      // first_slot: the wavefront's phase in the round-robin deal of 64-slot groups (partition_path_slots)
 
     PathState path_state(int which) const {
         return {path[which][0].as<float4>(), path[which][1].as<float4>(), path[which][2].as<float4>(), path[which][3].as<uint2>()};
     }
     ShadowQueue shadow_queue() const { return {shadow[0].as<float4>(), shadow[1].as<float4>(), shadow[2].as<float4>()}; }
-    void release() {
-        for (auto& buffers : path) for (DeviceBuffer& b : buffers) b.release();
-        hits.release(); queue_counts.release(); order.release(); order_coat.release(); nee_flags.release();
-        sort_keys[0].release(); sort_keys[1].release(); sort_order.release(); sort_temp.release();
-        for (DeviceBuffer& b : shadow) b.release();
-        for (hipEvent_t e : shade_done) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : counts_copied) if (e) (void)hipEventDestroy(e);
-        if (finished) (void)hipEventDestroy(finished);
-        if (own_stream) (void)hipStreamDestroy(own_stream);
-        if (host_counts) (void)hipHostFree(host_counts);
-        *this = Wavefront();
-    }
 };
 constexpr int MAX_WAVEFRONTS = 4;
 constexpr int COUNT_PAIR_STRIDE = 16;   // uint32 words between the counters of a wavefront (one 64 B line each)
@@ -108,52 +121,99 @@ constexpr int COUNT_PAIR_STRIDE = 16;   // uint32 words between the counters of 
 constexpr int COUNT_PAIRS = 3, COUNT_LINES = 5;
 constexpr int HOST_COUNT_WORDS = 8 + COUNT_LINES * COUNT_PAIR_STRIDE;   // pinned: 2 x {paths, shadow rays} read back, [4..8) spare, then the image of the counters at the start of a pass
 
+// What the argument checks of a description derive on their way (preflight_scene).
+struct Preflight {
+    uint32_t wide_stack_need = 0;       // worst-case stack need of the 4-wide tree: derived, not taken from the caller
+    uint32_t wide8_height = 0;          // 0: the description brings no 8-wide tree
+};
+
+// The scene the device holds: the uploaded pools, what is derived from them, the argument blocks the kernels take and the host's copies of what later calls are
+// checked against. Its writers -- upload() (hipr_upload_scene), update_geometry() (hipr_update_scene_geometry) and refit_transforms() (hipr_refit_scene_transforms) --
+// are called once every refusal is behind the entry point and every queued pass has finished, and go: ready = false, device work, publish pointers, counts and
+// flags, ready = true. One that fails on the way leaves a scene that answers HIPR_ERROR_NOT_READY until an upload succeeds, never one that names freed memory.
+struct ResidentScene {
+    DeviceBuffer nodes, wide_nodes, wide8_slots, triangles, instances, lights;                                     // what a geometry update brings again
+    DeviceBuffer indices, geometry, texcoords, tints, emissions, materials, textures, texels, environment_PDF, environment_samples;      // ... and leaves in place
+    DeviceBuffer shade_triangles, trace_triangles, trace_items;         // derived per triangle (derive_from_triangles)
+    DeviceBuffer triangle_class;        // one byte per triangle for the listing pass (k_classify_hits): bit 0 = its material is coated
+    DeviceScene args = {};              // also carries what is not the scene's: the tables, the sample offsets, the environment tint (hipr_create, hipr_upload_tables, hipr_set_scene_state)
+    Wide8Scene wide8 = {};              // the 8-wide tree with leaf records: what the persistent kernels walk when the scene brings one
+    uint32_t wide8_height = 0, wide_stack_entries = 0;
+    int stack_size = 16;
+    int shading_models = 7;             // bit mask of the shading models the scene's instances reference
+    // Kernel instantiations picked by what the pools hold. A geometry update leaves the material, texture and environment pools in place, so these keep what
+    // the UPLOAD decided: a refit description with other materials or texture formats must not switch the kernels over pools that still hold the old data.
+    bool coverage_textures_r8 = false;  // every coverage texture is HIPR_TEXEL_R8 and linear: k_trace_wide8<..., COVERAGE_R8 = true>
+    bool has_environment = true;        // an environment map, a presampled environment light or a float texture: k_shade<..., TEXTURES = 2>; 8-bit textures without those: TEXTURES = 1
+    bool has_textures = true;           // a material references a texture, or has_environment: k_shade<..., TEXTURES = true>
+    bool all_triangles_opaque = false;  // no triangle needs its material's coverage sampled (HIPR_TRIANGLE_OPAQUE on all): k_trace_wide8<..., COVERAGE = false>
+    bool any_coated_triangle = false;
+    // Host copies of what the device holds: a geometry update and a device refit are checked against THESE, and what they derive from the pools they leave in
+    // place comes from these, not from their own description.
+    std::vector<HiprMaterial> uploaded_materials;
+    std::vector<uint32_t> uploaded_light_types;
+    std::vector<HiprInstance> uploaded_instances;      // a device refit checks a new matrix's handedness against them
+    uint32_t uploaded_texture_count = 0, uploaded_vertex_count = 0, uploaded_index_count = 0;
+    uint64_t uploaded_texel_bytes = 0;
+
+    // device refit of the 8-wide tree (wide8_refit.h); filled at upload for scenes that bring the tree
+    DeviceBuffer refit_leaf_slots, refit_node_slots, refit_exact, refit_moved, refit_partial, refit_scratch;
+    std::vector<uint32_t> refit_level_begin;           // refit_node_slots[level_begin[l], level_begin[l + 1]) = the nodes l levels below the root
+    uint32_t refit_leaf_count = 0;
+    std::vector<uint32_t> refit_node_list, refit_node_words;      // host copy of refit_node_slots and each node's (base_valid, inner_mask) at the time: the topology the lists hold
+    double uploaded_half_area = 0.0, current_half_area = 0.0;
+    bool tree_stale = false;            // a device refit left the BVH2 and 4-wide arrays behind: hipr_set_trace_variant refuses them until the next upload / geometry update
+
+    bool ready = false;
+    // The search of the uploaded scene, fixed when it is uploaded (hipr_set_trace_variant / HIPR_TRACE_VARIANT name a request for the NEXT upload).
+    int chosen_variant = HIPR_TRACE_BVH2;
+    void choose_variant(int requested) {
+        const bool large = args.node_count > 64;
+        int v = requested;
+        if (v < 0) v = large ? HIPR_TRACE_WIDE8_PERSISTENT : (args.triangle_count <= SMALL_SCENE_TRIANGLES ? HIPR_TRACE_EXHAUSTIVE : HIPR_TRACE_BVH2);
+        if (v == HIPR_TRACE_WIDE8_PERSISTENT && wide8.slot_count == 0) v = HIPR_TRACE_WIDE_PERSISTENT;      // no 8-wide tree (none given, or higher than the LDS stacks)
+        if (v == HIPR_TRACE_WIDE_PERSISTENT && args.wide_node_count == 0) v = HIPR_TRACE_BVH2;
+        if (v == HIPR_TRACE_EXHAUSTIVE && args.trace_item_count == 0 && args.triangle_count != 0) v = HIPR_TRACE_BVH2;
+        chosen_variant = v;
+    }
+
+    // `requested_variant`, `cull_backfaces`: the context's settings at the time of the call.
+    int upload(const HiprSceneDesc* s, const Preflight& checked, int requested_variant, bool cull_backfaces, hipStream_t stream);
+    int update_geometry(const HiprSceneDesc* s, const Preflight& checked, int requested_variant, bool cull_backfaces, hipStream_t stream);
+    int refit_transforms(const HiprInstanceTransform* moved, uint32_t moved_count, const HiprLight* new_lights, uint32_t light_count, hipStream_t stream, HiprRefitResult* out);
+    int lights_keep_their_types(const char* who, const HiprLight* new_lights, uint32_t count) const;
+
+private:
+    int upload_pools(const HiprSceneDesc* s, bool all_pools, hipStream_t stream);
+    void derive_from_pools(const HiprSceneDesc* s);
+    int derive_from_triangles(const HiprSceneDesc* s, const Preflight& checked, bool new_topology, int requested_variant, bool cull_backfaces, hipStream_t stream);
+    void queue_triangle_records(hipStream_t stream) const;
+    int upload_wide8(const HiprSceneDesc* s, uint32_t height, bool cull_backfaces, hipStream_t stream);
+    int prepare_refit(const HiprSceneDesc* s, bool new_topology, hipStream_t stream);
+    template <bool WRITE> void queue_refit_tree(const float* grid_min, const float* grid_cell, hipStream_t stream) const;
+};
+
 } // namespace
 
 struct HiprContext {
     int device = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr, copy_stream = nullptr;
-    hipEvent_t pass_start = nullptr;
+    Stream own_stream, copy_stream;     // first members: destroyed last, after everything that was queued on them
+    hipStream_t stream = nullptr;       // own_stream, or the one hipr_set_stream lent (never destroyed here)
+    Event pass_start;
     Wavefront wavefronts[MAX_WAVEFRONTS];
     int wavefront_limit = 0;                // hipr_set_wavefront_count / HIPR_WAVEFRONTS; 0 = by scene: see wavefronts_wanted()
     int wavefront_count = 1;                // set by partition_path_slots: small frames run as one wavefront
     int partitioned_for = 0;                // the wavefronts_wanted() the current partition was made for
 
-    // scene
-    DeviceBuffer shade_triangles, trace_triangles, trace_items, wide_nodes, wide8_slots, environment_PDF, environment_samples;
-    Wide8Scene wide8 = {};              // the 8-wide tree with leaf records: what the persistent kernels walk when the scene brings one
-    uint32_t wide8_height = 0;
-    DeviceBuffer nodes, triangles, instances, indices, geometry, texcoords, tints, emissions, materials, lights, textures, texels;
-    bool coverage_textures_r8 = false;  // every coverage texture of the uploaded scene is HIPR_TEXEL_R8 and linear: k_trace_wide8<..., COVERAGE_R8 = true>
-    bool all_triangles_opaque = false;  // no triangle of the uploaded scene needs its material's coverage sampled (HIPR_TRIANGLE_OPAQUE on all): k_trace_wide8<..., COVERAGE = false>
+    ResidentScene scene;                // the uploaded scene and the argument blocks the kernels take (scene.args, scene.wide8)
     bool lean_trace = true;             // HIPR_LEAN_TRACE=0: always the full kernel
-    bool scene_has_environment = true;  // ... an environment map, a presampled environment light or a float texture: k_shade<..., TEXTURES = 2>; 8-bit textures without those: TEXTURES = 1
-    bool scene_has_textures = true;     // a material references a texture, or the scene brings an environment map / presampled environment light: k_shade<..., TEXTURES = true>
     bool lean_shade = true;             // HIPR_LEAN_SHADE=0: always the full kernel
-    DeviceBuffer triangle_class;        // one byte per triangle for the listing pass (k_classify_hits): bit 0 = its material is coated
     int arithmetic = HIPR_ARITHMETIC_FAST;     // hipr_set_arithmetic: which build of the shade unit the context launches (launch.h ShadeUnit)
     const hipr::ShadeUnit& shade_unit() const { return arithmetic == HIPR_ARITHMETIC_EXACT ? hipr::shade_unit_exact() : hipr::shade_unit_fast(); }
     bool coherence_sort = false;        // HIPR_COHERENCE_SORT=1: the rays of a fused trace launch are taken by (origin cell, octant), ray_sort.hip (built and measured in round 4: profiles/r04_ab_coherence_sort.txt)
-    bool any_coated_triangle = false, shade_classes = false;     // HIPR_SHADE_CLASSES=1: coated surface hits listed apart (built and measured in round 4: no gain, profiles/r04_ab_shade_classes.txt)
+    bool shade_classes = false;         // HIPR_SHADE_CLASSES=1: coated surface hits listed apart (built and measured in round 4: no gain, profiles/r04_ab_shade_classes.txt)
     DeviceBuffer ggx_rho, dielectric_rho, alpha, sample_offsets, sobol_tables;
-    DeviceScene scene = {};
-    bool tables_ready = false, scene_ready = false;
-    size_t uploaded_instance_bytes = 0;
-    uint32_t uploaded_material_count = 0, uploaded_texture_count = 0, uploaded_vertex_count = 0, uploaded_index_count = 0;   // pools a geometry update leaves in place
-    uint64_t uploaded_texel_bytes = 0;
-    int stack_size = 16;
-    int shading_models = 7;             // bit mask of the shading models the scene's instances reference
-    std::vector<HiprMaterial> uploaded_materials;      // host copies of what hipr_upload_scene put on the device: a refit (hipr_update_scene_geometry) leaves the material pool
-    std::vector<uint32_t> uploaded_light_types;        // and the environment data as they are, so what is derived from them must come from THESE, not from the refit's description
-
-    // device refit of the 8-wide tree (wide8_refit.h, hipr_refit_scene_transforms); filled at upload for scenes that bring the tree
-    DeviceBuffer refit_leaf_slots, refit_node_slots, refit_exact, refit_moved, refit_partial, refit_scratch;
-    std::vector<uint32_t> refit_level_begin;           // refit_node_slots[level_begin[l], level_begin[l + 1]) = the nodes l levels below the root
-    uint32_t refit_leaf_count = 0;
-    std::vector<uint32_t> refit_node_list, refit_node_words;      // host copy of refit_node_slots and each node's (base_valid, inner_mask) at the time: the topology the lists hold
-    std::vector<HiprInstance> uploaded_instances;      // host copy of the instances on the device: a device refit checks a new matrix's handedness against them
-    double uploaded_half_area = 0.0, current_half_area = 0.0;
-    bool tree_stale = false;                           // a device refit left the BVH2 and 4-wide arrays behind: hipr_set_trace_variant refuses them until the next upload / geometry update
+    bool tables_ready = false;
 
     // frame
     FrameInfo frame = {};
@@ -169,7 +229,7 @@ struct HiprContext {
         uint32_t first_parity = 0;      // the first tail bounce's sizes come back through the wavefront's regular read-back pair of this parity
         uint32_t blind_bounces = 0;     // bounces after it, read back into `tail_counts`
         uint32_t next_bounce = 0;       // the bounce that would follow the tail
-        uint32_t* tail_counts = nullptr;   // pinned: {paths that continue, shadow rays queued} per blind bounce
+        PinnedWords tail_counts;        // pinned: {paths that continue, shadow rays queued} per blind bounce
         uint32_t work_index = 0;        // next unused claim-counter set of the slot's half of the ring
         HiprCameraState camera = {};    // of the pass that left the tail (finish_slot may have to queue more bounces)
     } pass_slots[2];
@@ -179,7 +239,7 @@ struct HiprContext {
     bool pipeline_passes = false;       // hipr_set_pass_pipelining / HIPR_PIPELINE_PASSES=1; off by default: measured slower
     bool pipelining_now = false;        // the pass being queued is a pipelined one
     int pipeline_spare_blocks = 1;      // HIPR_PIPELINE_SPARE_BLOCKS
-    hipEvent_t accumulated = nullptr;   // the last hipr_accumulate_samples: the next one (on the other slot's stream) folds after it
+    Event accumulated;                  // the last hipr_accumulate_samples: the next one (on the other slot's stream) folds after it
     bool accumulated_valid = false;
     DeviceBuffer radiance_other;        // the other slot's radiance (the two swap when the slots do)
     uint32_t traced_samples = 0;        // samples the radiance buffer holds since the last hipr_trace_pass
@@ -203,27 +263,16 @@ struct HiprContext {
     // queues next to wavefront 1's half: about 1.5x the queue memory of a 64-accumulation 1080p pass, plus a redundant allocation and synchronisation).
     int wavefronts_wanted(bool frame_is_set) const {
         if (wavefront_limit > 0) return wavefront_limit;
-        if (scene_ready && use_persistent()) return frame_is_set && uint64_t(frame.owned_tiles) * 64u * frame.samples_per_pass >= TWO_WAVEFRONTS_FROM_SLOTS ? 2 : 1;
+        if (scene.ready && use_persistent()) return frame_is_set && uint64_t(frame.owned_tiles) * 64u * frame.samples_per_pass >= TWO_WAVEFRONTS_FROM_SLOTS ? 2 : 1;
         return 2;
     }
     int wavefronts_wanted() const { return wavefronts_wanted(frame_ready); }
-    // The search of the uploaded scene, fixed when it is uploaded (hipr_set_trace_variant / HIPR_TRACE_VARIANT name a request for the NEXT upload).
-    int chosen_variant = HIPR_TRACE_BVH2;
-    void choose_variant() {
-        const bool large = scene.node_count > 64;
-        int v = trace_variant;
-        if (v < 0) v = large ? HIPR_TRACE_WIDE8_PERSISTENT : (scene.triangle_count <= SMALL_SCENE_TRIANGLES ? HIPR_TRACE_EXHAUSTIVE : HIPR_TRACE_BVH2);
-        if (v == HIPR_TRACE_WIDE8_PERSISTENT && wide8.slot_count == 0) v = HIPR_TRACE_WIDE_PERSISTENT;      // no 8-wide tree (none given, or higher than the LDS stacks)
-        if (v == HIPR_TRACE_WIDE_PERSISTENT && scene.wide_node_count == 0) v = HIPR_TRACE_BVH2;
-        if (v == HIPR_TRACE_EXHAUSTIVE && scene.trace_item_count == 0 && scene.triangle_count != 0) v = HIPR_TRACE_BVH2;
-        chosen_variant = v;
-    }
-    bool use_wide8() const { return chosen_variant == HIPR_TRACE_WIDE8_PERSISTENT; }
-    bool use_wide4() const { return chosen_variant == HIPR_TRACE_WIDE_PERSISTENT; }
+    bool use_wide8() const { return scene.chosen_variant == HIPR_TRACE_WIDE8_PERSISTENT; }
+    bool use_wide4() const { return scene.chosen_variant == HIPR_TRACE_WIDE_PERSISTENT; }
     bool use_persistent() const { return use_wide8() || use_wide4(); }      // fused launches, one wavefront
     // tiny scenes: exhaustive search over the triangles (k_trace_*_small)
-    bool use_exhaustive() const { return chosen_variant == HIPR_TRACE_EXHAUSTIVE; }
-    int active_trace_variant() const { return chosen_variant; }
+    bool use_exhaustive() const { return scene.chosen_variant == HIPR_TRACE_EXHAUSTIVE; }
+    int active_trace_variant() const { return scene.chosen_variant; }
     int cu_count = 256;
     int blocks_per_cu_override = 0;     // HIPR_BLOCKS_PER_CU
     int shade_blocks_per_cu = 0;        // persistent shade blocks per CU = waves per SIMD; 0: 3 (what the kernel is compiled for), 2 for all-Diffuse scenes (HIPR_SHADE_BLOCKS_PER_CU)
@@ -242,7 +291,7 @@ struct HiprContext {
     bool trace_log = false;
     DeviceCounters trace_log_previous = {};
     bool timing = true;
-    std::vector<hipEvent_t> event_pool;
+    std::vector<Event> event_pool;
     size_t events_used = 0;
     std::vector<TimedLaunch> timed;
     HiprKernelTimes times = {};
@@ -251,9 +300,9 @@ struct HiprContext {
 
     hipEvent_t next_event() {
         if (events_used == event_pool.size()) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return nullptr;
-            event_pool.push_back(e);
+            Event e = make_event(hipEventDefault);
+            if (!e) return nullptr;
+            event_pool.push_back(std::move(e));
         }
         return event_pool[events_used++];
     }
@@ -380,7 +429,7 @@ void launch_persistent(HiprContext* c, const Wavefront& w, const PathState& in, 
     const uint32_t waves_per_block = TRACE_BLOCK / 64;
     uint32_t grid = uint32_t(c->cu_count) * uint32_t(per_cu);
     grid = std::max(1u, std::min(grid, (upper_bound + 63u) / 64u / waves_per_block + 1u));
-    hipLaunchKernelGGL((k_trace_persistent<STACK, MODE, INSTRUMENT, OVERFLOW>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene, in, w.hits.as<float4>(), w.shadow_queue(),
+    hipLaunchKernelGGL((k_trace_persistent<STACK, MODE, INSTRUMENT, OVERFLOW>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, in, w.hits.as<float4>(), w.shadow_queue(),
                        c->radiance.as<float4>(), closest_count, shadow_count, next_work_counter(c), c->refill_below, c->counters.as<DeviceCounters>());
 }
 
@@ -401,26 +450,26 @@ void launch_wide8(HiprContext* c, const Wavefront& w, const PathState& in, const
     grid = std::max(1u, std::min(grid, (upper_bound + 63u) / 64u / waves_per_block + 1u));
 #if HIPR_RAY_SORT
     if constexpr (MODE == TRACE_FUSED && !INSTRUMENT) if (sorted) {     // ray_sort.hip listed the launch's rays
-        if (c->all_triangles_opaque && c->lean_trace)
-            hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT, false, true>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene, c->wide8, in, w.hits.as<float4>(), w.shadow_queue(),
+        if (c->scene.all_triangles_opaque && c->lean_trace)
+            hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT, false, true>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, c->scene.wide8, in, w.hits.as<float4>(), w.shadow_queue(),
                                c->radiance.as<float4>(), closest_count, shadow_count, next_work_counter(c), c->refill_below, c->counters.as<DeviceCounters>(), sorted);
         else
-            hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT, true, true>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene, c->wide8, in, w.hits.as<float4>(), w.shadow_queue(),
+            hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT, true, true>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, c->scene.wide8, in, w.hits.as<float4>(), w.shadow_queue(),
                                c->radiance.as<float4>(), closest_count, shadow_count, next_work_counter(c), c->refill_below, c->counters.as<DeviceCounters>(), sorted);
         return;
     }
 #endif
-    if constexpr (!INSTRUMENT && MODE != TRACE_CLOSEST) if (!sorted && !c->all_triangles_opaque && c->coverage_textures_r8 && c->lean_trace) {     // the coverage sampler for 8-bit single-channel textures only
-        hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT, true, false, true>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene, c->wide8, in, w.hits.as<float4>(), w.shadow_queue(),
+    if constexpr (!INSTRUMENT && MODE != TRACE_CLOSEST) if (!sorted && !c->scene.all_triangles_opaque && c->scene.coverage_textures_r8 && c->lean_trace) {     // the coverage sampler for 8-bit single-channel textures only
+        hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT, true, false, true>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, c->scene.wide8, in, w.hits.as<float4>(), w.shadow_queue(),
                            c->radiance.as<float4>(), closest_count, shadow_count, next_work_counter(c), c->refill_below, c->counters.as<DeviceCounters>());
         return;
     }
     // scenes whose triangles are all statically opaque run the kernel without the coverage code (closest-only launches never reach it anyway)
-    if (!INSTRUMENT && MODE != TRACE_CLOSEST && c->all_triangles_opaque && c->lean_trace)
-        hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT, false>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene, c->wide8, in, w.hits.as<float4>(), w.shadow_queue(),
+    if (!INSTRUMENT && MODE != TRACE_CLOSEST && c->scene.all_triangles_opaque && c->lean_trace)
+        hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT, false>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, c->scene.wide8, in, w.hits.as<float4>(), w.shadow_queue(),
                            c->radiance.as<float4>(), closest_count, shadow_count, next_work_counter(c), c->refill_below, c->counters.as<DeviceCounters>());
     else
-    hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene, c->wide8, in, w.hits.as<float4>(), w.shadow_queue(),
+    hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, c->scene.wide8, in, w.hits.as<float4>(), w.shadow_queue(),
                        c->radiance.as<float4>(), closest_count, shadow_count, next_work_counter(c), c->refill_below, c->counters.as<DeviceCounters>());
 }
 
@@ -432,19 +481,19 @@ void launch_persistent_for_stack(HiprContext* c, const Wavefront& w, const PathS
     // atrium) spill often enough that 32 LDS entries + scratch is the faster split (116.7 vs 119.9 ms).
     if (c->use_wide8()) {       // height h: at most h - 1 groups wait on the stack
 #if HIPR_WIDE8_LOW_BUCKET
-        if (c->wide8_height <= 9u) launch_wide8<8, MODE, INSTRUMENT>(c, w, in, closest_count, shadow_count, upper_bound, 3, sorted);
+        if (c->scene.wide8_height <= 9u) launch_wide8<8, MODE, INSTRUMENT>(c, w, in, closest_count, shadow_count, upper_bound, 3, sorted);
         else
 #endif
-        if (c->wide8_height <= uint32_t(WIDE8_STACK_SHALLOW) + 1u) launch_wide8<WIDE8_STACK_SHALLOW, MODE, INSTRUMENT>(c, w, in, closest_count, shadow_count, upper_bound, 0, sorted);
-        else if (c->wide8_height <= 17u) launch_wide8<16, MODE, INSTRUMENT>(c, w, in, closest_count, shadow_count, upper_bound, 1, sorted);
+        if (c->scene.wide8_height <= uint32_t(WIDE8_STACK_SHALLOW) + 1u) launch_wide8<WIDE8_STACK_SHALLOW, MODE, INSTRUMENT>(c, w, in, closest_count, shadow_count, upper_bound, 0, sorted);
+        else if (c->scene.wide8_height <= 17u) launch_wide8<16, MODE, INSTRUMENT>(c, w, in, closest_count, shadow_count, upper_bound, 1, sorted);
         else launch_wide8<32, MODE, INSTRUMENT>(c, w, in, closest_count, shadow_count, upper_bound, 2, sorted);
         return;
     }
 #ifndef HIPR_STACK_MID
 #define HIPR_STACK_MID 16
 #endif
-    if (c->wide_stack_entries <= 16) launch_persistent<16, MODE, INSTRUMENT, false>(c, w, in, closest_count, shadow_count, upper_bound, 0);
-    else if (c->wide_stack_entries <= 32) launch_persistent<HIPR_STACK_MID, MODE, INSTRUMENT, true>(c, w, in, closest_count, shadow_count, upper_bound, 1);
+    if (c->scene.wide_stack_entries <= 16) launch_persistent<16, MODE, INSTRUMENT, false>(c, w, in, closest_count, shadow_count, upper_bound, 0);
+    else if (c->scene.wide_stack_entries <= 32) launch_persistent<HIPR_STACK_MID, MODE, INSTRUMENT, true>(c, w, in, closest_count, shadow_count, upper_bound, 1);
     else launch_persistent<32, MODE, INSTRUMENT, true>(c, w, in, closest_count, shadow_count, upper_bound, 2);
 }
 
@@ -456,14 +505,14 @@ void launch_trace_closest(HiprContext* c, const Wavefront& w, const PathState& i
     if (c->use_persistent()) { launch_persistent_for_stack<TRACE_CLOSEST, INSTRUMENT>(c, w, in, count_ptr, nullptr, upper_bound); return; }
     DeviceCounters* dc = c->counters.as<DeviceCounters>();
     if (c->use_exhaustive()) {
-        hipLaunchKernelGGL((k_trace_closest_small<INSTRUMENT>), dim3(grid_for(upper_bound, 256, 256u * 16u)), dim3(256), 0, w.stream, c->scene, in, hits, count_ptr, dc);
+        hipLaunchKernelGGL((k_trace_closest_small<INSTRUMENT>), dim3(grid_for(upper_bound, 256, 256u * 16u)), dim3(256), 0, w.stream, c->scene.args, in, hits, count_ptr, dc);
         return;
     }
     const uint32_t grid = grid_for(upper_bound, TRACE_BLOCK, 256u * 16u);
-    switch (c->stack_size) {
-    case 16: hipLaunchKernelGGL((k_trace_closest<16, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene, in, hits, count_ptr, dc); break;
-    case 32: hipLaunchKernelGGL((k_trace_closest<32, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene, in, hits, count_ptr, dc); break;
-    default: hipLaunchKernelGGL((k_trace_closest<64, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene, in, hits, count_ptr, dc); break;
+    switch (c->scene.stack_size) {
+    case 16: hipLaunchKernelGGL((k_trace_closest<16, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, in, hits, count_ptr, dc); break;
+    case 32: hipLaunchKernelGGL((k_trace_closest<32, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, in, hits, count_ptr, dc); break;
+    default: hipLaunchKernelGGL((k_trace_closest<64, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, in, hits, count_ptr, dc); break;
     }
 }
 
@@ -474,14 +523,14 @@ void launch_trace_shadow(HiprContext* c, const Wavefront& w, const uint32_t* cou
     float4* rad = c->radiance.as<float4>();
     ShadowQueue q = w.shadow_queue();
     if (c->use_exhaustive()) {
-        hipLaunchKernelGGL((k_trace_shadow_small<INSTRUMENT>), dim3(grid_for(upper_bound, 256, 256u * 16u)), dim3(256), 0, w.stream, c->scene, q, rad, count_ptr, dc);
+        hipLaunchKernelGGL((k_trace_shadow_small<INSTRUMENT>), dim3(grid_for(upper_bound, 256, 256u * 16u)), dim3(256), 0, w.stream, c->scene.args, q, rad, count_ptr, dc);
         return;
     }
     const uint32_t grid = grid_for(upper_bound, TRACE_BLOCK, 256u * 16u);
-    switch (c->stack_size) {
-    case 16: hipLaunchKernelGGL((k_trace_shadow<16, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene, q, rad, count_ptr, dc); break;
-    case 32: hipLaunchKernelGGL((k_trace_shadow<32, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene, q, rad, count_ptr, dc); break;
-    default: hipLaunchKernelGGL((k_trace_shadow<64, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene, q, rad, count_ptr, dc); break;
+    switch (c->scene.stack_size) {
+    case 16: hipLaunchKernelGGL((k_trace_shadow<16, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, q, rad, count_ptr, dc); break;
+    case 32: hipLaunchKernelGGL((k_trace_shadow<32, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, q, rad, count_ptr, dc); break;
+    default: hipLaunchKernelGGL((k_trace_shadow<64, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, q, rad, count_ptr, dc); break;
     }
 }
 
@@ -494,7 +543,7 @@ void launch_trace_fused(HiprContext* c, const Wavefront& w, const PathState& in,
         const ShadowQueue q = w.shadow_queue();
         hipr::RaySortLaunch a = {w.stream, in.o_tmin, in.d_pdf, q.o_tmax, q.d_slot, closest_count, shadow_count, std::min(upper_bound, 2u * std::max(w.n_slots, 64u)), {}, {},
                                  w.sort_keys[0].as<uint16_t>(), w.sort_keys[1].as<uint16_t>(), w.sort_order.as<uint32_t>(), w.sort_temp.ptr, w.sort_temp.bytes};
-        for (int k = 0; k < 3; ++k) { a.grid_min[k] = c->wide8.grid_min[k]; a.cells_per_unit[k] = 16.0f / (c->wide8.grid_cell[k] * 2097152.0f); }
+        for (int k = 0; k < 3; ++k) { a.grid_min[k] = c->scene.wide8.grid_min[k]; a.cells_per_unit[k] = 16.0f / (c->scene.wide8.grid_cell[k] * 2097152.0f); }
         if (hipr::launch_ray_sort(a) == 0) sorted = w.sort_order.as<uint32_t>();
     }
 #endif
@@ -512,9 +561,9 @@ void launch_shade(HiprContext* c, const Wavefront& w, const HiprCameraState& cam
     // Camera rays need no listing: a wave of them is one pixel's samples (or an 8 x 8 tile's pixels) -- they hit a surface, or miss, together (HIPR_SHADE_ORDERED_CAMERA=1 lists them anyway).
     if (c->shade_ordered && c->use_persistent() && c->entry == HIPR_ENTRY_PATH_TRACING && alive >= c->shade_ordered_from && (!camera_rays || c->shade_ordered_camera)) {
         unsigned long long* taken = reinterpret_cast<unsigned long long*>(taken_words + COUNT_PAIR_STRIDE * cur);
-        if (c->shade_classes && c->any_coated_triangle)
+        if (c->shade_classes && c->scene.any_coated_triangle)
             hipLaunchKernelGGL(k_classify_hits<true>, dim3(grid_for(alive, 256u * CLASSIFY_ROUNDS, uint32_t(c->cu_count) * 8u)), dim3(256), 0, w.stream, w.hits.as<float4>(), in_count, w.order.as<uint32_t>(), taken,
-                               c->triangle_class.as<unsigned char>(), w.order_coat.as<uint32_t>());
+                               c->scene.triangle_class.as<unsigned char>(), w.order_coat.as<uint32_t>());
         else
             hipLaunchKernelGGL(k_classify_hits<false>, dim3(grid_for(alive, 256u * CLASSIFY_ROUNDS, uint32_t(c->cu_count) * 8u)), dim3(256), 0, w.stream, w.hits.as<float4>(), in_count, w.order.as<uint32_t>(), taken,
                                (const unsigned char*)nullptr, w.order_coat.as<uint32_t>());
@@ -524,15 +573,15 @@ void launch_shade(HiprContext* c, const Wavefront& w, const HiprCameraState& cam
     // persistent blocks: three per CU stay resident (3 waves per SIMD), each walks the queue with a grid stride, one batch ahead on its inputs
     // measured: the Default / Transmissive kernels gain from a third wave per SIMD (atrium 29.4 -> 25.9 ms of shading per step), the lighter all-Diffuse
     // kernel loses (Cornell 18 390 -> 17 194 Mrays/s)
-    const bool split = c->shade_split && c->entry == HIPR_ENTRY_PATH_TRACING && c->scene.light_count != 0 && w.nee_flags.ptr;
-    const uint32_t blocks_per_cu = c->shade_blocks_per_cu > 0 ? uint32_t(c->shade_blocks_per_cu) : (split ? uint32_t(HIPR_SHADE_SPLIT_WAVES) : (c->shading_models == 2 ? 2u : uint32_t(c->shade_unit().waves_per_simd)));
+    const bool split = c->shade_split && c->entry == HIPR_ENTRY_PATH_TRACING && c->scene.args.light_count != 0 && w.nee_flags.ptr;
+    const uint32_t blocks_per_cu = c->shade_blocks_per_cu > 0 ? uint32_t(c->shade_blocks_per_cu) : (split ? uint32_t(HIPR_SHADE_SPLIT_WAVES) : (c->scene.shading_models == 2 ? 2u : uint32_t(c->shade_unit().waves_per_simd)));
     PathState shaded = w.path_state(cur);
     if (camera_rays) shaded.thr_bounces = nullptr;      // k_generate's queue: throughput 1, no bounce yet -- not stored
-    ShadeLaunch a = {grid_for(alive, SHADE_BLOCK, uint32_t(c->cu_count) * blocks_per_cu), w.stream, c->scene, camera, c->frame, c->entry, shaded, w.hits.as<float4>(), order, w.order_coat.as<uint32_t>(), listed, w.path_state(1 - cur),
+    ShadeLaunch a = {grid_for(alive, SHADE_BLOCK, uint32_t(c->cu_count) * blocks_per_cu), w.stream, c->scene.args, camera, c->frame, c->entry, shaded, w.hits.as<float4>(), order, w.order_coat.as<uint32_t>(), listed, w.path_state(1 - cur),
                      w.shadow_queue(), c->radiance.as<float4>(), in_count, reinterpret_cast<unsigned long long*>(out_counts), reinterpret_cast<unsigned long long*>(zero_pair),
                      reinterpret_cast<unsigned long long*>(taken_words + COUNT_PAIR_STRIDE * (1 - cur)), split ? w.nee_flags.as<unsigned char>() : nullptr,
-                     c->counters.as<DeviceCounters>(), c->scene_has_textures || !c->lean_shade, c->scene_has_environment || !c->lean_shade};
-    c->shade_unit().shade(c->shading_models, a);
+                     c->counters.as<DeviceCounters>(), c->scene.has_textures || !c->lean_shade, c->scene.has_environment || !c->lean_shade};
+    c->shade_unit().shade(c->scene.shading_models, a);
 }
 
 // Splits the path slots of a pass (owned tiles x 64 x samples_per_pass) over the wavefronts on a tile (= wave) boundary and sizes the
@@ -868,18 +917,71 @@ const char* validate_wide8(const HiprSceneDesc* s, uint32_t& height, char* messa
 #undef INVALID
 }
 
+// Bit mask of the shading models that instances reference; `materials`: the pool the DEVICE holds (a geometry update brings instances, not materials).
+int shading_model_mask(const HiprInstance* instances, uint32_t count, const HiprMaterial* materials) {
+    int models = 0;
+    for (uint32_t i = 0; i < count; ++i) models |= 1 << std::min<int>(materials[instances[i].material_index].shading_model, 2);
+    return models ? models : 7;
+}
+// Everything hipr_upload_scene and hipr_update_scene_geometry refuse a description for by looking at it alone, and what the checks derive on the way. Pure host
+// code -- no context, no HIP call: hipr_validate_scene is exactly this, and the two uploads run it before they touch the device. `who`: the entry point, for the message.
+int preflight_scene(const char* who, const HiprSceneDesc* s, Preflight& out) {
+    if (!s) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null scene", who);
+    if (s->triangle_count && (!s->nodes || !s->triangles || !s->instances || !s->indices || !s->geometry || !s->materials))
+        return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: missing geometry arrays", who);
+    char invalid[256];
+    if (validate_scene(s, out.wide_stack_need, invalid, sizeof(invalid)) || validate_wide8(s, out.wide8_height, invalid, sizeof(invalid)))
+        return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: %s", who, invalid);
+    for (uint32_t i = 0; i < s->instance_count; ++i)
+        if ((s->instances[i].mesh_flags & HIPR_MESH_TEXCOORDS && !s->texcoords) || (s->instances[i].mesh_flags & HIPR_MESH_TINTS && !s->tints) ||
+            (s->instances[i].mesh_flags & HIPR_MESH_EMISSIVE && !s->emissions))
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: instance %u flags an attribute whose pool is null", who, i);
+    if (const HiprEnvironment* env = s->environment)
+        if (env->environment_map_ID <= 0 || uint32_t(env->environment_map_ID) >= s->texture_count || !env->per_pixel_PDF || !env->samples || env->sample_count == 0 ||
+            env->pdf_width == 0 || env->pdf_height == 0)
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: incomplete environment description", who);
+    return HIPR_OK;
+}
+
+// The pools of a checked description, queued on `stream`: all of them (an upload), or those a geometry update brings again.
+int ResidentScene::upload_pools(const HiprSceneDesc* s, bool all_pools, hipStream_t stream) {
+    int r = 0;
+    r |= nodes.upload(s->nodes, size_t(s->node_count) * sizeof(HiprBvhNode), stream);
+    if (s->wide_nodes && s->wide_node_count) r |= wide_nodes.upload(s->wide_nodes, size_t(s->wide_node_count) * sizeof(HiprWideNode), stream);
+    r |= triangles.upload(s->triangles, size_t(s->triangle_count) * sizeof(HiprTriangle), stream);
+    r |= instances.upload(s->instances, size_t(s->instance_count) * sizeof(HiprInstance), stream);
+    r |= lights.upload(s->lights, size_t(s->light_count) * sizeof(HiprLight), stream);
+    if (all_pools) {
+        r |= indices.upload(s->indices, size_t(s->index_count) * 4, stream);
+        r |= geometry.upload(s->geometry, size_t(s->vertex_count) * sizeof(HiprVertexGeometry), stream);
+        if (s->texcoords) r |= texcoords.upload(s->texcoords, size_t(s->vertex_count) * 8, stream);
+        if (s->tints) r |= tints.upload(s->tints, size_t(s->vertex_count) * 4, stream);
+        if (s->emissions) r |= emissions.upload(s->emissions, size_t(s->vertex_count) * 12, stream);
+        r |= materials.upload(s->materials, size_t(s->material_count) * sizeof(HiprMaterial), stream);
+        r |= textures.upload(s->textures, size_t(s->texture_count) * sizeof(HiprTexture), stream);
+        r |= texels.upload(s->texels, s->texel_bytes, stream);
+        if (const HiprEnvironment* env = s->environment) {
+            r |= environment_PDF.upload(env->per_pixel_PDF, size_t(env->pdf_width) * env->pdf_height * sizeof(float), stream);
+            r |= environment_samples.upload(env->samples, size_t(env->sample_count) * sizeof(HiprLightSample), stream);
+        }
+    }
+    if (r) return r < 0 ? r : HIPR_ERROR_HIP;
+    HIP_TRY(hipStreamSynchronize(stream));      // the caller's arrays are read
+    return HIPR_OK;
+}
+
 // Uploads (or re-uploads, after a refit) the 8-wide tree of a validated description; trees higher than the largest LDS stack are left to the 4-wide kernels.
-int upload_wide8(HiprContext* c, const HiprSceneDesc* s, uint32_t height) {
-    c->wide8 = {};
-    c->wide8_height = 0;
+int ResidentScene::upload_wide8(const HiprSceneDesc* s, uint32_t height, bool cull_backfaces, hipStream_t stream) {
+    wide8 = {};
+    wide8_height = 0;
     if (!s->wide8_slots || s->wide8_slot_count == 0 || height > 33u) return HIPR_OK;
-    if (int r = c->wide8_slots.upload(s->wide8_slots, size_t(s->wide8_slot_count) * sizeof(HiprSlot8), c->stream)) return r;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->wide8.slots = c->wide8_slots.as<uint4>();
-    c->wide8.slot_count = s->wide8_slot_count;
-    for (int a = 0; a < 3; ++a) { c->wide8.grid_min[a] = s->wide8_grid_min[a]; c->wide8.grid_cell[a] = s->wide8_grid_cell[a]; }
-    c->wide8.cull_backfaces = c->cull_backfaces ? 1u : 0u;
-    c->wide8_height = height;
+    if (int r = wide8_slots.upload(s->wide8_slots, size_t(s->wide8_slot_count) * sizeof(HiprSlot8), stream)) return r;
+    HIP_TRY(hipStreamSynchronize(stream));
+    wide8.slots = wide8_slots.as<uint4>();
+    wide8.slot_count = s->wide8_slot_count;
+    for (int a = 0; a < 3; ++a) { wide8.grid_min[a] = s->wide8_grid_min[a]; wide8.grid_cell[a] = s->wide8_grid_cell[a]; }
+    wide8.cull_backfaces = cull_backfaces ? 1u : 0u;
+    wide8_height = height;
     return HIPR_OK;
 }
 
@@ -897,132 +999,128 @@ float reverse_halton(int prime, int i) {
     return float(h);
 }
 
-// What the kernels read per triangle is derived on the device from the uploaded pools: the shading records (k_build_shade_triangles), the
-// vertex + edges form the trace kernels test (k_build_trace_triangles) and, for scenes searched exhaustively, the items (build_trace_items).
-// `pools_uploaded`: the call follows an upload of materials, textures and texels (hipr_upload_scene). hipr_update_scene_geometry leaves those pools on the device as they are,
-// so the kernel instantiations chosen from them (textures or not, environment code, 8-bit coverage sampler) must keep what the UPLOAD decided (a refit
-// description with other materials or texture formats would otherwise switch the kernels over pools that still hold the old data).
-int build_derived_geometry(HiprContext* c, const HiprSceneDesc* s, bool pools_uploaded) {
-    DeviceScene& d = c->scene;
-    if (pools_uploaded) {
-        c->uploaded_materials.assign(s->materials, s->materials + s->material_count);
-        c->uploaded_light_types.resize(s->light_count);
-        for (uint32_t l = 0; l < s->light_count; ++l) c->uploaded_light_types[l] = s->lights[l].flags & HIPR_LIGHT_TYPE_MASK;
-    }
-    hipStream_t st = c->stream;
-    if (s->triangle_count) {   // flatten the per-hit attribute chain into one record per triangle
-        if (c->shade_triangles.resize(size_t(s->triangle_count) * SHADE_TRIANGLE_QUADS * sizeof(float4))) return HIPR_ERROR_OUT_OF_MEMORY;
-        d.shade_triangles = c->shade_triangles.as<float4>();
-        hipLaunchKernelGGL(k_build_shade_triangles, dim3((s->triangle_count + 255) / 256), dim3(256), 0, st, d, c->shade_triangles.as<float4>());
-        if (c->trace_triangles.resize(size_t(s->triangle_count) * 3 * sizeof(float4))) return HIPR_ERROR_OUT_OF_MEMORY;
-        d.trace_triangles = c->trace_triangles.as<float4>();
-        hipLaunchKernelGGL(k_build_trace_triangles, dim3((s->triangle_count + 255) / 256), dim3(256), 0, st, d.triangles, s->triangle_count, c->trace_triangles.as<float4>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    // the listing pass's class of every triangle (k_classify_hits): bit 0 = the material of its instance carries a coat
-    if (pools_uploaded) {
-    c->scene_has_textures = s->environment != nullptr;
-    c->scene_has_environment = s->environment != nullptr;
-    for (uint32_t m = 0; m < s->material_count; ++m) {
-        const HiprMaterial& material = s->materials[m];
-        c->scene_has_textures = c->scene_has_textures || material.tint_roughness_texture_ID || material.roughness_texture_ID || material.metallic_texture_ID || material.coverage_texture_ID;
-    }
-    for (uint32_t l = 0; l < s->light_count; ++l) c->scene_has_environment = c->scene_has_environment || (s->lights[l].flags & HIPR_LIGHT_TYPE_MASK) == HIPR_LIGHT_PRESAMPLED_ENVIRONMENT;
+// What an upload derives from the material, texture and light pools it brings: the host copies later calls are checked against, and the kernel instantiations
+// the pools allow (ResidentScene: a geometry update keeps them).
+void ResidentScene::derive_from_pools(const HiprSceneDesc* s) {
+    uploaded_materials.assign(s->materials, s->materials + s->material_count);
+    uploaded_light_types.resize(s->light_count);
+    for (uint32_t l = 0; l < s->light_count; ++l) uploaded_light_types[l] = s->lights[l].flags & HIPR_LIGHT_TYPE_MASK;
+    uploaded_texture_count = s->texture_count; uploaded_vertex_count = s->vertex_count; uploaded_index_count = s->index_count; uploaded_texel_bytes = s->texel_bytes;
+    has_textures = has_environment = s->environment != nullptr;
+    for (const HiprMaterial& material : uploaded_materials)
+        has_textures = has_textures || material.tint_roughness_texture_ID || material.roughness_texture_ID || material.metallic_texture_ID || material.coverage_texture_ID;
+    for (uint32_t type : uploaded_light_types) has_environment = has_environment || type == HIPR_LIGHT_PRESAMPLED_ENVIRONMENT;
     for (uint32_t t = 1; t < s->texture_count; ++t)       // float textures take the generic samplers: TEXTURES = 2 as well
-        c->scene_has_environment = c->scene_has_environment || s->textures[t].format == HIPR_TEXEL_R32F || s->textures[t].format == HIPR_TEXEL_RGBA32F;
-    c->scene_has_textures = c->scene_has_textures || c->scene_has_environment;
-    c->coverage_textures_r8 = true;
-    for (uint32_t m = 0; m < s->material_count; ++m)
-        if (const int32_t id = s->materials[m].coverage_texture_ID)
-            c->coverage_textures_r8 = c->coverage_textures_r8 && uint32_t(id) < s->texture_count && s->textures[id].format == HIPR_TEXEL_R8 && !s->textures[id].is_sRGB;
-    }
-    c->any_coated_triangle = false;
-    c->all_triangles_opaque = true;
-    for (uint32_t t = 0; t < s->triangle_count; ++t) c->all_triangles_opaque = c->all_triangles_opaque && (s->triangles[t].flags & HIPR_TRIANGLE_OPAQUE) != 0;
+        has_environment = has_environment || s->textures[t].format == HIPR_TEXEL_R32F || s->textures[t].format == HIPR_TEXEL_RGBA32F;
+    has_textures = has_textures || has_environment;
+    coverage_textures_r8 = true;
+    for (const HiprMaterial& material : uploaded_materials)
+        if (const int32_t id = material.coverage_texture_ID)
+            coverage_textures_r8 = coverage_textures_r8 && uint32_t(id) < s->texture_count && s->textures[id].format == HIPR_TEXEL_R8 && !s->textures[id].is_sRGB;
+}
+
+// The shade and trace records of every triangle (k_build_shade_triangles: the per-hit attribute chain flattened; k_build_trace_triangles: the vertex + edges form
+// the trace kernels test), from the pools and the triangles the device holds at the time.
+void ResidentScene::queue_triangle_records(hipStream_t stream) const {
+    hipLaunchKernelGGL(k_build_shade_triangles, dim3((args.triangle_count + 255) / 256), dim3(256), 0, stream, args, shade_triangles.as<float4>());
+    hipLaunchKernelGGL(k_build_trace_triangles, dim3((args.triangle_count + 255) / 256), dim3(256), 0, stream, args.triangles, args.triangle_count, trace_triangles.as<float4>());
+}
+
+// What an upload and a geometry update derive from the triangles, instances and trees they bring -- over the material pool the device HOLDS (uploaded_materials): the
+// per-triangle records, the listing pass's classes, the exhaustive search's items (build_trace_items), the 8-wide tree and the device refit's lists.
+// `new_topology`: an upload; a geometry update keeps the tree the upload took (or left).
+int ResidentScene::derive_from_triangles(const HiprSceneDesc* s, const Preflight& checked, bool new_topology, int requested_variant, bool cull_backfaces, hipStream_t stream) {
+    shading_models = shading_model_mask(s->instances, s->instance_count, uploaded_materials.data());
+    uploaded_instances.assign(s->instances, s->instances + s->instance_count);
+    any_coated_triangle = false;
+    all_triangles_opaque = true;
+    args.trace_items = nullptr;
+    args.trace_item_count = 0;
     if (s->triangle_count) {
-        std::vector<unsigned char> classes(s->triangle_count, 0);
+        if (int r = shade_triangles.resize(size_t(s->triangle_count) * SHADE_TRIANGLE_QUADS * sizeof(float4))) return r;
+        if (int r = trace_triangles.resize(size_t(s->triangle_count) * 3 * sizeof(float4))) return r;
+        args.shade_triangles = shade_triangles.as<float4>();
+        args.trace_triangles = trace_triangles.as<float4>();
+        queue_triangle_records(stream);
+        HIP_TRY(hipGetLastError());
+        std::vector<unsigned char> classes(s->triangle_count, 0);      // k_classify_hits: bit 0 = the material of its instance carries a coat
         for (uint32_t t = 0; t < s->triangle_count; ++t) {
-            const HiprMaterial& m = c->uploaded_materials[s->instances[s->triangles[t].instance_index].material_index];      // the pool on the device (see uploaded_materials)
-            classes[t] = m.coat != 0 ? 1 : 0;
-            c->any_coated_triangle = c->any_coated_triangle || classes[t] != 0;
+            all_triangles_opaque = all_triangles_opaque && (s->triangles[t].flags & HIPR_TRIANGLE_OPAQUE) != 0;
+            classes[t] = uploaded_materials[s->instances[s->triangles[t].instance_index].material_index].coat != 0 ? 1 : 0;
+            any_coated_triangle = any_coated_triangle || classes[t] != 0;
         }
-        if (c->triangle_class.upload(classes.data(), classes.size(), st)) return HIPR_ERROR_OUT_OF_MEMORY;
-        HIP_TRY(hipStreamSynchronize(st));
+        if (int r = triangle_class.upload(classes.data(), classes.size(), stream)) return r;
+        HIP_TRY(hipStreamSynchronize(stream));      // `classes` is read
+        if (s->triangle_count <= SMALL_SCENE_TRIANGLES || requested_variant == HIPR_TRACE_EXHAUSTIVE) {
+            std::vector<float> items;
+            build_trace_items(s->triangles, s->triangle_count, items);
+            if (int r = trace_items.upload(items.data(), items.size() * sizeof(float), stream)) return r;
+            HIP_TRY(hipStreamSynchronize(stream));
+            args.trace_items = trace_items.as<float4>();
+            args.trace_item_count = uint32_t(items.size() / 16);
+        }
     }
-    d.trace_items = nullptr;
-    d.trace_item_count = 0;
-    if (s->triangle_count && (s->triangle_count <= SMALL_SCENE_TRIANGLES || c->trace_variant == HIPR_TRACE_EXHAUSTIVE)) {
-        std::vector<float> items;
-        build_trace_items(s->triangles, s->triangle_count, items);
-        if (c->trace_items.upload(items.data(), items.size() * sizeof(float), st)) return HIPR_ERROR_OUT_OF_MEMORY;
-        HIP_TRY(hipStreamSynchronize(st));
-        d.trace_items = c->trace_items.as<float4>();
-        d.trace_item_count = uint32_t(items.size() / 16);
-    }
-    return HIPR_OK;
+    if (new_topology || wide8.slot_count)
+        if (int r = upload_wide8(s, checked.wide8_height, cull_backfaces, stream)) return r;
+    return prepare_refit(s, new_topology, stream);
 }
 
 // ---- device refit (wide8_refit.h) -------------------------------------------------------------------------------------------------------------------------
 // refit_scratch: [0, 48) the six reduced bounds, [48, 52) the rebuild flag, [64, 72) the area sum.
 constexpr size_t REFIT_SCRATCH_FLAG = 48, REFIT_SCRATCH_AREA = 64, REFIT_SCRATCH_BYTES = 128;
 
-// Queues passes 2 - 4 on the context's stream. WRITE = false: exact boxes and area only (the slots stay as uploaded).
+// Queues passes 2 - 4. WRITE = false: exact boxes and area only (the slots stay as uploaded).
 template <bool WRITE>
-void queue_refit_tree(HiprContext* c, const float* grid_min, const float* grid_cell) {
-    hipStream_t st = c->stream;
-    HiprSlot8* slots = c->wide8_slots.as<HiprSlot8>();
-    RefitBox* exact = c->refit_exact.as<RefitBox>();
-    char* scratch = c->refit_scratch.as<char>();
-    const uint32_t slot_count = c->wide8.slot_count;
-    if (c->refit_leaf_count)
-        hipLaunchKernelGGL((k_refit_leaves<WRITE>), dim3((c->refit_leaf_count + REFIT_BLOCK - 1) / REFIT_BLOCK), dim3(REFIT_BLOCK), 0, st, slots, c->refit_leaf_slots.as<uint32_t>(), c->refit_leaf_count,
-                           c->triangles.as<HiprTriangle>(), exact, reinterpret_cast<uint32_t*>(scratch + REFIT_SCRATCH_FLAG));
-    for (size_t level = c->refit_level_begin.size() - 1; level-- > 0;) {      // deepest first: a launch per level is the only ordering there is
-        const uint32_t begin = c->refit_level_begin[level], count = c->refit_level_begin[level + 1] - begin;
+void ResidentScene::queue_refit_tree(const float* grid_min, const float* grid_cell, hipStream_t st) const {
+    HiprSlot8* slots = wide8_slots.as<HiprSlot8>();
+    RefitBox* exact = refit_exact.as<RefitBox>();
+    char* scratch = refit_scratch.as<char>();
+    const uint32_t slot_count = wide8.slot_count;
+    if (refit_leaf_count)
+        hipLaunchKernelGGL((k_refit_leaves<WRITE>), dim3((refit_leaf_count + REFIT_BLOCK - 1) / REFIT_BLOCK), dim3(REFIT_BLOCK), 0, st, slots, refit_leaf_slots.as<uint32_t>(), refit_leaf_count,
+                           triangles.as<HiprTriangle>(), exact, reinterpret_cast<uint32_t*>(scratch + REFIT_SCRATCH_FLAG));
+    for (size_t level = refit_level_begin.size() - 1; level-- > 0;) {      // deepest first: a launch per level is the only ordering there is
+        const uint32_t begin = refit_level_begin[level], count = refit_level_begin[level + 1] - begin;
         if (!count) continue;
-        hipLaunchKernelGGL((k_refit_nodes<WRITE>), dim3((count + REFIT_BLOCK - 1) / REFIT_BLOCK), dim3(REFIT_BLOCK), 0, st, slots, c->refit_node_slots.as<uint32_t>() + begin, count, exact,
+        hipLaunchKernelGGL((k_refit_nodes<WRITE>), dim3((count + REFIT_BLOCK - 1) / REFIT_BLOCK), dim3(REFIT_BLOCK), 0, st, slots, refit_node_slots.as<uint32_t>() + begin, count, exact,
                            grid_min[0], grid_min[1], grid_min[2], grid_cell[0], grid_cell[1], grid_cell[2]);
     }
     const uint32_t blocks = (slot_count + REFIT_BLOCK - 1) / REFIT_BLOCK;
-    hipLaunchKernelGGL(k_refit_area, dim3(blocks), dim3(REFIT_BLOCK), 0, st, exact, slot_count, c->refit_partial.as<double>());
-    hipLaunchKernelGGL(k_refit_area_final, dim3(1), dim3(REFIT_BLOCK), 0, st, c->refit_partial.as<double>(), blocks, reinterpret_cast<double*>(scratch + REFIT_SCRATCH_AREA));
+    hipLaunchKernelGGL(k_refit_area, dim3(blocks), dim3(REFIT_BLOCK), 0, st, exact, slot_count, refit_partial.as<double>());
+    hipLaunchKernelGGL(k_refit_area_final, dim3(1), dim3(REFIT_BLOCK), 0, st, refit_partial.as<double>(), blocks, reinterpret_cast<double*>(scratch + REFIT_SCRATCH_AREA));
 }
 
-// After an upload (`new_topology`) or a geometry update of a scene with the 8-wide tree: the slot lists by kind and level, the host copy of the instances and the
+// After an upload (`new_topology`) or a geometry update of a scene with the 8-wide tree: the slot lists by kind and level and the
 // half area the tree starts with, taken by the kernels that take it after a refit.
-int prepare_refit(HiprContext* c, const HiprSceneDesc* s, bool new_topology) {
-    c->tree_stale = false;
-    if (c->wide8.slot_count == 0) {
-        c->uploaded_instances.clear();
-        c->refit_level_begin.clear();
-        c->refit_node_list.clear();
-        c->refit_node_words.clear();
-        c->refit_leaf_count = 0;
-        c->uploaded_half_area = c->current_half_area = 0.0;
+int ResidentScene::prepare_refit(const HiprSceneDesc* s, bool new_topology, hipStream_t st) {
+    tree_stale = false;
+    if (wide8.slot_count == 0) {
+        refit_level_begin.clear();
+        refit_node_list.clear();
+        refit_node_words.clear();
+        refit_leaf_count = 0;
+        uploaded_half_area = current_half_area = 0.0;
         return HIPR_OK;
     }
-    c->uploaded_instances.assign(s->instances, s->instances + s->instance_count);
-    const uint32_t slot_count = c->wide8.slot_count;
-    hipStream_t st = c->stream;
+    const uint32_t slot_count = wide8.slot_count;
     // A geometry update promises the uploaded topology, and hipr_update_scene_geometry has only compared counts and heights: the lists are kept when every node they
     // name carries the topology words they were made from -- from the root down that is the same tree, slot for slot -- and made again otherwise, so that the
     // leaf kernel never takes a node slot for a leaf record.
     if (!new_topology) {
-        new_topology = c->refit_node_list.empty() || c->refit_node_words.size() != c->refit_node_list.size() * 2;
-        for (size_t i = 0; i < c->refit_node_list.size() && !new_topology; ++i) {
-            const HiprNode8& n = s->wide8_slots[c->refit_node_list[i]].node;
-            new_topology = n.base_valid != c->refit_node_words[2 * i] || n.inner_mask != c->refit_node_words[2 * i + 1];
+        new_topology = refit_node_list.empty() || refit_node_words.size() != refit_node_list.size() * 2;
+        for (size_t i = 0; i < refit_node_list.size() && !new_topology; ++i) {
+            const HiprNode8& n = s->wide8_slots[refit_node_list[i]].node;
+            new_topology = n.base_valid != refit_node_words[2 * i] || n.inner_mask != refit_node_words[2 * i + 1];
         }
     }
     if (new_topology) {
         std::vector<uint32_t> nodes = {0u}, leaves;
         nodes.reserve(slot_count / 4 + 1);
         leaves.reserve(slot_count);
-        c->refit_level_begin.assign(1, 0u);
+        refit_level_begin.assign(1, 0u);
         for (size_t begin = 0; begin < nodes.size();) {      // the tree was validated: every child slot is in range and has one parent
             const size_t end = nodes.size();
-            c->refit_level_begin.push_back(uint32_t(end));
+            refit_level_begin.push_back(uint32_t(end));
             for (size_t i = begin; i < end; ++i) {
                 const HiprNode8& n = s->wide8_slots[nodes[i]].node;
                 const uint32_t base = n.base_valid & 0xFFFFFFu, valid = n.base_valid >> 24;
@@ -1035,31 +1133,134 @@ int prepare_refit(HiprContext* c, const HiprSceneDesc* s, bool new_topology) {
             }
             begin = end;
         }
-        c->refit_leaf_count = uint32_t(leaves.size());
-        c->refit_node_list.clear();      // the host copies describe what the device holds: set together, once the uploads below are through
-        c->refit_node_words.clear();
+        refit_leaf_count = uint32_t(leaves.size());
+        refit_node_list.clear();      // the host copies describe what the device holds: set together, once the uploads below are through
+        refit_node_words.clear();
         const size_t triangle_blocks = (size_t(s->triangle_count) + REFIT_BLOCK - 1) / REFIT_BLOCK, slot_blocks = (size_t(slot_count) + REFIT_BLOCK - 1) / REFIT_BLOCK;
         int r = 0;
-        r |= c->refit_node_slots.upload(nodes.data(), nodes.size() * 4, st);
-        r |= c->refit_leaf_slots.upload(leaves.data(), leaves.size() * 4, st);
-        r |= c->refit_exact.resize(size_t(slot_count) * sizeof(RefitBox));
-        r |= c->refit_moved.resize(std::max<size_t>(s->instance_count, 1) * 4);
-        r |= c->refit_partial.resize(std::max(triangle_blocks * 6 * sizeof(RefitBound), slot_blocks * sizeof(double)));
-        r |= c->refit_scratch.resize(REFIT_SCRATCH_BYTES);
+        r |= refit_node_slots.upload(nodes.data(), nodes.size() * 4, st);
+        r |= refit_leaf_slots.upload(leaves.data(), leaves.size() * 4, st);
+        r |= refit_exact.resize(size_t(slot_count) * sizeof(RefitBox));
+        r |= refit_moved.resize(std::max<size_t>(s->instance_count, 1) * 4);
+        r |= refit_partial.resize(std::max(triangle_blocks * 6 * sizeof(RefitBound), slot_blocks * sizeof(double)));
+        r |= refit_scratch.resize(REFIT_SCRATCH_BYTES);
         if (r) return r < 0 ? r : HIPR_ERROR_HIP;
         HIP_TRY(hipStreamSynchronize(st));      // the upload reads the lists
-        c->refit_node_words.resize(nodes.size() * 2);
+        refit_node_words.resize(nodes.size() * 2);
         for (size_t i = 0; i < nodes.size(); ++i) {
-            c->refit_node_words[2 * i] = s->wide8_slots[nodes[i]].node.base_valid;
-            c->refit_node_words[2 * i + 1] = s->wide8_slots[nodes[i]].node.inner_mask;
+            refit_node_words[2 * i] = s->wide8_slots[nodes[i]].node.base_valid;
+            refit_node_words[2 * i + 1] = s->wide8_slots[nodes[i]].node.inner_mask;
         }
-        c->refit_node_list = std::move(nodes);
+        refit_node_list = std::move(nodes);
     }
-    queue_refit_tree<false>(c, c->wide8.grid_min, c->wide8.grid_cell);
+    queue_refit_tree<false>(wide8.grid_min, wide8.grid_cell, st);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&c->uploaded_half_area, c->refit_scratch.as<char>() + REFIT_SCRATCH_AREA, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&uploaded_half_area, refit_scratch.as<char>() + REFIT_SCRATCH_AREA, sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    c->current_half_area = c->uploaded_half_area;
+    current_half_area = uploaded_half_area;
+    return HIPR_OK;
+}
+
+int ResidentScene::upload(const HiprSceneDesc* s, const Preflight& checked, int requested_variant, bool cull_backfaces, hipStream_t stream) {
+    ready = false;
+    if (int r = upload_pools(s, true, stream)) return r;
+    const HiprEnvironment* env = s->environment;
+    args.nodes = nodes.as<float4>();
+    args.node_count = s->node_count;
+    args.wide_nodes = s->wide_nodes && s->wide_node_count ? wide_nodes.as<uint4>() : nullptr;
+    args.wide_node_count = s->wide_nodes ? s->wide_node_count : 0u;
+    args.triangles = triangles.as<float4>();
+    args.triangle_count = s->triangle_count;
+    args.instances = instances.as<HiprInstance>();
+    args.indices = indices.as<uint32_t>();
+    args.geometry = geometry.as<float4>();
+    args.texcoords = texcoords.as<float2>();
+    args.tints = tints.as<uint32_t>();
+    args.emissions = emissions.as<float>();
+    args.materials = materials.as<HiprMaterial>();
+    args.lights = lights.as<HiprLight>();
+    args.light_count = s->light_count;
+    args.textures = textures.as<HiprTexture>();
+    args.texels = texels.as<uint8_t>();
+    args.env_map_ID = env ? env->environment_map_ID : 0;
+    args.env_per_pixel_PDF = env ? environment_PDF.as<float>() : nullptr;
+    args.env_samples = env ? environment_samples.as<float4>() : nullptr;
+    args.env_pdf_width = env ? env->pdf_width : 0u; args.env_pdf_height = env ? env->pdf_height : 0u; args.env_sample_count = env ? env->sample_count : 0u;
+    wide_stack_entries = checked.wide_stack_need;
+    stack_size = s->bvh_max_depth <= 16 ? 16 : (s->bvh_max_depth <= 32 ? 32 : 64);
+    derive_from_pools(s);
+    if (int r = derive_from_triangles(s, checked, true, requested_variant, cull_backfaces, stream)) return r;
+    choose_variant(requested_variant);
+    ready = true;
+    return HIPR_OK;
+}
+
+// The pools it brings again have the uploaded sizes (hipr_update_scene_geometry has compared them): no buffer moves, the pointers and counts in `args` stay.
+int ResidentScene::update_geometry(const HiprSceneDesc* s, const Preflight& checked, int requested_variant, bool cull_backfaces, hipStream_t stream) {
+    ready = false;
+    if (int r = upload_pools(s, false, stream)) return r;
+    if (int r = derive_from_triangles(s, checked, false, requested_variant, cull_backfaces, stream)) return r;      // also ends the state a device refit left
+    ready = true;
+    return HIPR_OK;
+}
+
+// The lights ARE brought again by a geometry update and a device refit (they move), but the kernels were instantiated for the kinds of light the upload brought --
+// environment code or not -- and the environment's own data is not part of either: a light may move, not change its type.
+int ResidentScene::lights_keep_their_types(const char* who, const HiprLight* new_lights, uint32_t count) const {
+    for (uint32_t l = 0; l < count; ++l)
+        if ((new_lights[l].flags & HIPR_LIGHT_TYPE_MASK) != uploaded_light_types[l])
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: light %u changes its type (%u -> %u); upload the scene instead", who, l, uploaded_light_types[l], new_lights[l].flags & HIPR_LIGHT_TYPE_MASK);
+    return HIPR_OK;
+}
+
+// The device work of hipr_refit_scene_transforms, which has checked the arguments against uploaded_instances and uploaded_light_types.
+int ResidentScene::refit_transforms(const HiprInstanceTransform* moved, uint32_t moved_count, const HiprLight* new_lights, uint32_t light_count, hipStream_t st, HiprRefitResult* out) {
+    ready = false;
+    *out = {};
+    if (new_lights && light_count) {
+        if (int r = lights.upload(new_lights, size_t(light_count) * sizeof(HiprLight), st)) return r;
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (moved_count) {
+        std::vector<uint32_t> flags(uploaded_instances.size(), 0u);
+        std::vector<HiprInstance> moved_instances = uploaded_instances;      // becomes the host copy once the device holds it (after the last synchronise)
+        for (uint32_t k = 0; k < moved_count; ++k) {
+            std::memcpy(moved_instances[moved[k].instance_index].object_to_world, moved[k].object_to_world, sizeof(moved[k].object_to_world));
+            flags[moved[k].instance_index] = 1u;
+        }
+        HIP_TRY(hipMemcpyAsync(instances.ptr, moved_instances.data(), moved_instances.size() * sizeof(HiprInstance), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(refit_moved.ptr, flags.data(), flags.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(refit_scratch.ptr, 0, REFIT_SCRATCH_BYTES, st));
+        // pass 1: world-space triangles and the scene's bounds
+        const uint32_t blocks = (args.triangle_count + REFIT_BLOCK - 1) / REFIT_BLOCK;
+        hipLaunchKernelGGL(k_refit_triangles, dim3(blocks), dim3(REFIT_BLOCK), 0, st, triangles.as<HiprTriangle>(), args.triangle_count, instances.as<HiprInstance>(), refit_moved.as<uint32_t>(),
+                           indices.as<uint32_t>(), geometry.as<HiprVertexGeometry>(), refit_partial.as<RefitBound>());
+        hipLaunchKernelGGL(k_refit_bounds_final, dim3(1), dim3(REFIT_BLOCK), 0, st, refit_partial.as<RefitBound>(), blocks, refit_scratch.as<RefitBound>());
+        HIP_TRY(hipGetLastError());
+        RefitBound bounds[6];
+        HIP_TRY(hipMemcpyAsync(bounds, refit_scratch.ptr, sizeof(bounds), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));      // `flags` and the instances are read by now as well
+        const float lo[3] = {bounds[0].v, bounds[1].v, bounds[2].v}, hi[3] = {bounds[3].v, bounds[4].v, bounds[5].v};
+        float grid_min[3], grid_cell[3];
+        refit_grid(lo, hi, grid_min, grid_cell);      // the moved scene's bounds: node origins must not be clamped at the ends of a stale grid
+        // passes 2 - 4, then the records derived from the triangles
+        queue_refit_tree<true>(grid_min, grid_cell, st);
+        queue_triangle_records(st);
+        HIP_TRY(hipGetLastError());
+        struct { uint32_t flag; uint32_t pad[3]; double area; } tail = {};
+        static_assert(REFIT_SCRATCH_AREA - REFIT_SCRATCH_FLAG == 16, "the flag and the area are read back together");
+        HIP_TRY(hipMemcpyAsync(&tail, refit_scratch.as<char>() + REFIT_SCRATCH_FLAG, sizeof(tail), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        uploaded_instances.swap(moved_instances);
+        tree_stale = true;
+        for (int a = 0; a < 3; ++a) { wide8.grid_min[a] = grid_min[a]; wide8.grid_cell[a] = grid_cell[a]; }
+        current_half_area = tail.area;
+        out->needs_rebuild = tail.flag ? 1 : 0;      // a pair parted: this tree cannot hold the scene any more
+    }
+    out->child_half_area = current_half_area;
+    out->uploaded_half_area = uploaded_half_area;
+    for (int a = 0; a < 3; ++a) { out->grid_min[a] = wide8.grid_min[a]; out->grid_cell[a] = wide8.grid_cell[a]; }
+    ready = !out->needs_rebuild;
     return HIPR_OK;
 }
 
@@ -1084,29 +1285,26 @@ int hipr_create(int device_id, HiprContext** out_context) {
     if (n == 0) return fail(HIPR_ERROR_NO_DEVICE, "no HIP device available");
     if (device_id < 0 || device_id >= n) return fail(HIPR_ERROR_INVALID_ARGUMENT, "device %d out of range [0, %d)", device_id, n);
     HIP_TRY(hipSetDevice(device_id));
-    HiprContext* c = new HiprContext();
+    std::unique_ptr<HiprContext, int (*)(HiprContext*)> owner(new HiprContext(), hipr_destroy);      // the one failure exit: whichever return below is taken before release()
+    HiprContext* c = owner.get();
     c->device = device_id;
-    bool ok = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&c->pass_start, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->accumulated, hipEventDisableTiming) == hipSuccess &&
-              hipHostMalloc((void**)&c->pass_slots[0].tail_counts, 2 * 128 * sizeof(uint32_t)) == hipSuccess && hipHostMalloc((void**)&c->pass_slots[1].tail_counts, 2 * 128 * sizeof(uint32_t)) == hipSuccess;
+    c->own_stream = make_stream(); c->copy_stream = make_stream();
+    c->pass_start = make_event(); c->accumulated = make_event();
+    bool ok = c->own_stream && c->copy_stream && c->pass_start && c->accumulated;
+    for (auto& slot : c->pass_slots) { slot.tail_counts = make_pinned_words(2 * 128); ok = ok && slot.tail_counts; }
     c->stream = c->own_stream;
     for (int g = 0; ok && g < MAX_WAVEFRONTS; ++g) {
         Wavefront& w = c->wavefronts[g];
-        if (g > 0) ok = ok && hipStreamCreateWithFlags(&w.own_stream, hipStreamNonBlocking) == hipSuccess;
+        if (g > 0) { w.own_stream = make_stream(); ok = ok && w.own_stream; }
         w.stream = g == 0 ? c->stream : w.own_stream;
-        for (int i = 0; i < 2; ++i)
-            ok = ok && hipEventCreateWithFlags(&w.shade_done[i], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&w.counts_copied[i], hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&w.finished, hipEventDisableTiming) == hipSuccess && hipHostMalloc((void**)&w.host_counts, HOST_COUNT_WORDS * sizeof(uint32_t)) == hipSuccess &&
-             w.queue_counts.resize(COUNT_LINES * COUNT_PAIR_STRIDE * sizeof(uint32_t)) == 0;
+        for (int i = 0; i < 2; ++i) { w.shade_done[i] = make_event(); w.counts_copied[i] = make_event(); ok = ok && w.shade_done[i] && w.counts_copied[i]; }
+        w.finished = make_event();
+        w.host_counts = make_pinned_words(HOST_COUNT_WORDS);
+        ok = ok && w.finished && w.host_counts && w.queue_counts.resize(COUNT_LINES * COUNT_PAIR_STRIDE * sizeof(uint32_t)) == 0;
     }
-    if (!ok) {
-        hipr_destroy(c);
-        return fail(HIPR_ERROR_HIP, "stream / event / pinned allocation failed");
-    }
-    if (c->counters.resize(sizeof(DeviceCounters)) || c->work_counters.resize(2 * WORK_COUNTERS * sizeof(uint32_t))) {
-        hipr_destroy(c);
-        return HIPR_ERROR_OUT_OF_MEMORY;
-    }
+    if (!ok) return fail(HIPR_ERROR_HIP, "stream / event / pinned allocation failed");
+    if (int s = c->counters.resize(sizeof(DeviceCounters))) return s;
+    if (int s = c->work_counters.resize(2 * WORK_COUNTERS * sizeof(uint32_t))) return s;
     c->pass_slots[0].work_index = c->pass_slots[1].work_index = WORK_SETS;   // forces the first launch of either slot to zero its ring
     hipDeviceProp_t props;
     if (hipGetDeviceProperties(&props, device_id) == hipSuccess && props.multiProcessorCount > 0) c->cu_count = props.multiProcessorCount;
@@ -1134,7 +1332,7 @@ int hipr_create(int device_id, HiprContext** out_context) {
     const int primes[4] = {2, 3, 5, 7};
     for (int i = 0; i < 256; ++i)
         for (int d = 0; d < 4; ++d) offsets[4 * i + d] = reverse_halton(primes[d], i);
-    if (int s = c->sample_offsets.upload(offsets, sizeof(offsets), c->stream)) { delete c; return s; }
+    if (int s = c->sample_offsets.upload(offsets, sizeof(offsets), c->stream)) return s;
     // Byte-indexed Sobol tables: entry [d][k][b] = XOR of the direction numbers of dimension d + 1 selected by byte k = b.
     std::vector<uint32_t> sobol(SOBOL_TABLE_WORDS);
     for (int d = 0; d < 3; ++d)
@@ -1145,30 +1343,19 @@ int hipr_create(int device_id, HiprContext** out_context) {
                     if (b & (1 << j)) v ^= SOBOL_DIRECTIONS[d][8 * k + j];
                 sobol[(d * 4 + k) * 256 + b] = v;
             }
-    if (int s = c->sobol_tables.upload(sobol.data(), sobol.size() * 4, c->stream)) { delete c; return s; }
+    if (int s = c->sobol_tables.upload(sobol.data(), sobol.size() * 4, c->stream)) return s;
     if (int finish_status = finish_all(c)) return finish_status;
-    c->scene.sobol_tables = c->sobol_tables.as<uint32_t>();
-    c->scene.sample_offsets = c->sample_offsets.as<float4>();
-    c->scene.next_event_sample_count = 3;   // OR/Renderer.cpp:479
-    *out_context = c;
+    c->scene.args.sobol_tables = c->sobol_tables.as<uint32_t>();
+    c->scene.args.sample_offsets = c->sample_offsets.as<float4>();
+    c->scene.args.next_event_sample_count = 3;   // OR/Renderer.cpp:479
+    *out_context = owner.release();
     return HIPR_OK;
 }
 
 int hipr_destroy(HiprContext* c) {
     if (!c) return HIPR_OK;
     (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    DeviceBuffer* all[] = {&c->refit_leaf_slots, &c->refit_node_slots, &c->refit_exact, &c->refit_moved, &c->refit_partial, &c->refit_scratch, &c->shade_triangles, &c->trace_triangles, &c->trace_items, &c->wide_nodes, &c->wide8_slots, &c->environment_PDF, &c->environment_samples, &c->nodes, &c->triangles, &c->instances, &c->indices, &c->geometry, &c->texcoords, &c->tints, &c->emissions, &c->materials,
-                           &c->lights, &c->textures, &c->texels, &c->ggx_rho, &c->dielectric_rho, &c->alpha, &c->sample_offsets, &c->sobol_tables, &c->radiance, &c->radiance_other,
-                           &c->accumulation, &c->scratch_accumulation, &c->counters, &c->work_counters, &c->debug_a, &c->debug_b, &c->debug_c};
-    for (DeviceBuffer* b : all) b->release();
-    for (Wavefront& w : c->wavefronts) w.release();
-    for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-    if (c->pass_start) (void)hipEventDestroy(c->pass_start);
-    if (c->accumulated) (void)hipEventDestroy(c->accumulated);
-    for (auto& slot : c->pass_slots) if (slot.tail_counts) (void)hipHostFree(slot.tail_counts);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+    (void)hipDeviceSynchronize();      // nothing is freed before this; the members then go in reverse order, the context's streams last
     delete c;
     return HIPR_OK;
 }
@@ -1201,243 +1388,89 @@ int hipr_upload_tables(HiprContext* c, const HiprTables* t) {
     if (int s = c->dielectric_rho.upload(diel.data(), diel.size() * 2, c->stream)) return s;
     if (int s = c->alpha.upload(alpha.data(), alpha.size() * 2, c->stream)) return s;
     if (int finish_status = finish_all(c)) return finish_status;
-    c->scene.tables = {c->ggx_rho.as<ushort2>(), c->dielectric_rho.as<ushort2>(), c->alpha.as<unsigned short>()};
+    c->scene.args.tables = {c->ggx_rho.as<ushort2>(), c->dielectric_rho.as<ushort2>(), c->alpha.as<unsigned short>()};
     c->tables_ready = true;
     return HIPR_OK;
 }
 
 int hipr_validate_scene(const HiprSceneDesc* s) {
-    if (!s) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_validate_scene: null scene");
-    if (s->triangle_count && (!s->nodes || !s->triangles || !s->instances || !s->indices || !s->geometry || !s->materials))
-        return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_validate_scene: missing geometry arrays");
-    uint32_t wide_stack_need = 0;
-    char invalid[256];
-    if (validate_scene(s, wide_stack_need, invalid, sizeof(invalid))) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_validate_scene: %s", invalid);
-    uint32_t wide8_height = 0;
-    if (validate_wide8(s, wide8_height, invalid, sizeof(invalid))) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_validate_scene: %s", invalid);
-    return HIPR_OK;
+    Preflight checked;
+    return preflight_scene("hipr_validate_scene", s, checked);
 }
 
 int hipr_upload_scene(HiprContext* c, const HiprSceneDesc* s) {
     if (int st = check_context(c)) return st;
-    if (!s) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_upload_scene: null scene");
-    if (s->triangle_count && (!s->nodes || !s->triangles || !s->instances || !s->indices || !s->geometry || !s->materials))
-        return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_upload_scene: missing geometry arrays");
+    Preflight checked;
+    if (int st = preflight_scene("hipr_upload_scene", s, checked)) return st;
+    // what the kernels cannot serve (a description hipr_validate_scene finds sound may still meet these)
     if (s->bvh_max_depth > 64) return fail(HIPR_ERROR_UNSUPPORTED, "BVH depth %u exceeds the 64 entry LDS stack", s->bvh_max_depth);
-    uint32_t wide_stack_need = 0;
-    char invalid[256];
-    if (validate_scene(s, wide_stack_need, invalid, sizeof(invalid))) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_upload_scene: %s", invalid);
-    if (wide_stack_need > 32u + uint32_t(TRACE_SPILL_ENTRIES))
-        return fail(HIPR_ERROR_UNSUPPORTED, "the wide BVH needs %u stack entries, more than the %u the traversal kernels provide", wide_stack_need, 32u + uint32_t(TRACE_SPILL_ENTRIES));
-    uint32_t wide8_height = 0;
-    if (validate_wide8(s, wide8_height, invalid, sizeof(invalid))) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_upload_scene: %s", invalid);
-    for (uint32_t i = 0; i < s->instance_count; ++i)
-        if ((s->instances[i].mesh_flags & HIPR_MESH_TEXCOORDS && !s->texcoords) || (s->instances[i].mesh_flags & HIPR_MESH_TINTS && !s->tints) ||
-            (s->instances[i].mesh_flags & HIPR_MESH_EMISSIVE && !s->emissions))
-            return fail(HIPR_ERROR_INVALID_ARGUMENT, "instance %u flags an attribute whose pool is null", i);
-    if (int finish_status = finish_all(c)) return finish_status;
-    hipStream_t st = c->stream;
-    int r = 0;
-    r |= c->nodes.upload(s->nodes, size_t(s->node_count) * sizeof(HiprBvhNode), st);
-    if (s->wide_nodes && s->wide_node_count) r |= c->wide_nodes.upload(s->wide_nodes, size_t(s->wide_node_count) * sizeof(HiprWideNode), st);
-    r |= c->triangles.upload(s->triangles, size_t(s->triangle_count) * sizeof(HiprTriangle), st);
-    r |= c->instances.upload(s->instances, size_t(s->instance_count) * sizeof(HiprInstance), st);
-    r |= c->indices.upload(s->indices, size_t(s->index_count) * 4, st);
-    r |= c->geometry.upload(s->geometry, size_t(s->vertex_count) * sizeof(HiprVertexGeometry), st);
-    if (s->texcoords) r |= c->texcoords.upload(s->texcoords, size_t(s->vertex_count) * 8, st);
-    if (s->tints) r |= c->tints.upload(s->tints, size_t(s->vertex_count) * 4, st);
-    if (s->emissions) r |= c->emissions.upload(s->emissions, size_t(s->vertex_count) * 12, st);
-    r |= c->materials.upload(s->materials, size_t(s->material_count) * sizeof(HiprMaterial), st);
-    r |= c->lights.upload(s->lights, size_t(s->light_count) * sizeof(HiprLight), st);
-    r |= c->textures.upload(s->textures, size_t(s->texture_count) * sizeof(HiprTexture), st);
-    r |= c->texels.upload(s->texels, s->texel_bytes, st);
-    const HiprEnvironment* env = s->environment;
-    if (env) {
-        if (env->environment_map_ID <= 0 || uint32_t(env->environment_map_ID) >= s->texture_count || !env->per_pixel_PDF || !env->samples || env->sample_count == 0 ||
-            env->pdf_width == 0 || env->pdf_height == 0)
-            return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_upload_scene: incomplete environment description");
-        const uint8_t format = s->textures[env->environment_map_ID].format;
+    if (checked.wide_stack_need > 32u + uint32_t(TRACE_SPILL_ENTRIES))
+        return fail(HIPR_ERROR_UNSUPPORTED, "the wide BVH needs %u stack entries, more than the %u the traversal kernels provide", checked.wide_stack_need, 32u + uint32_t(TRACE_SPILL_ENTRIES));
+    if (s->environment) {
+        const uint8_t format = s->textures[s->environment->environment_map_ID].format;
         if (format != HIPR_TEXEL_RGBA8 && format != HIPR_TEXEL_RGBA32F)
             return fail(HIPR_ERROR_UNSUPPORTED, "only environments with 4 channels are supported (OptiXRenderer/Renderer.cpp:1141-1158)");
-        r |= c->environment_PDF.upload(env->per_pixel_PDF, size_t(env->pdf_width) * env->pdf_height * sizeof(float), st);
-        r |= c->environment_samples.upload(env->samples, size_t(env->sample_count) * sizeof(HiprLightSample), st);
     }
-    if (r) return r < 0 ? r : HIPR_ERROR_HIP;
-    HIP_TRY(hipStreamSynchronize(st));
-    DeviceScene& d = c->scene;
-    d.nodes = c->nodes.as<float4>();
-    d.wide_nodes = s->wide_nodes && s->wide_node_count ? c->wide_nodes.as<uint4>() : nullptr;
-    d.wide_node_count = s->wide_nodes ? s->wide_node_count : 0u;
-    c->wide_stack_entries = wide_stack_need;   // derived from the tree (validate_scene), not taken from the caller
-    d.triangles = c->triangles.as<float4>();
-    d.instances = c->instances.as<HiprInstance>();
-    d.indices = c->indices.as<uint32_t>();
-    d.geometry = c->geometry.as<float4>();
-    d.texcoords = c->texcoords.as<float2>();
-    d.tints = c->tints.as<uint32_t>();
-    d.emissions = c->emissions.as<float>();
-    d.materials = c->materials.as<HiprMaterial>();
-    d.lights = c->lights.as<HiprLight>();
-    d.textures = c->textures.as<HiprTexture>();
-    d.texels = c->texels.as<uint8_t>();
-    d.env_map_ID = env ? env->environment_map_ID : 0;
-    d.env_per_pixel_PDF = env ? c->environment_PDF.as<float>() : nullptr;
-    d.env_samples = env ? c->environment_samples.as<float4>() : nullptr;
-    d.env_pdf_width = env ? env->pdf_width : 0u; d.env_pdf_height = env ? env->pdf_height : 0u; d.env_sample_count = env ? env->sample_count : 0u;
-    d.node_count = s->node_count;
-    d.triangle_count = s->triangle_count;
-    d.light_count = s->light_count;
-    if (int status = build_derived_geometry(c, s, true)) return status;
-    if (int status = upload_wide8(c, s, wide8_height)) return status;
-    if (int status = prepare_refit(c, s, true)) return status;
-    c->choose_variant();
-    c->stack_size = s->bvh_max_depth <= 16 ? 16 : (s->bvh_max_depth <= 32 ? 32 : 64);
-    int models = 0;
-    for (uint32_t i = 0; i < s->instance_count; ++i) {
-        const int32_t m = s->instances[i].material_index;
-        if (m < 0 || uint32_t(m) >= s->material_count) return fail(HIPR_ERROR_INVALID_ARGUMENT, "instance %u references material %d of %u", i, m, s->material_count);
-        models |= 1 << std::min<int>(s->materials[m].shading_model, 2);
-    }
-    c->shading_models = models ? models : 7;
-    c->uploaded_instance_bytes = size_t(s->instance_count) * sizeof(HiprInstance);
-    c->uploaded_material_count = s->material_count; c->uploaded_texture_count = s->texture_count; c->uploaded_vertex_count = s->vertex_count;
-    c->uploaded_index_count = s->index_count; c->uploaded_texel_bytes = s->texel_bytes;
-    c->scene_ready = true;
-    return HIPR_OK;
+    if (int finish_status = finish_all(c)) return finish_status;
+    return c->scene.upload(s, checked, c->trace_variant, c->cull_backfaces, c->stream);
 }
 
 int hipr_update_scene_geometry(HiprContext* c, const HiprSceneDesc* s) {
     if (int st = check_context(c)) return st;
-    if (!s) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: null scene");
-    if (!c->scene_ready) return fail(HIPR_ERROR_NOT_READY, "hipr_update_scene_geometry: no scene uploaded");
-    if (s->triangle_count && (!s->nodes || !s->triangles || !s->instances || !s->indices || !s->geometry || !s->materials))
-        return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: missing geometry arrays");
-    // Meshes, materials and textures stay on the device as uploaded: the description is validated against ITS pools below, so those must be the
+    Preflight checked;
+    if (int st = preflight_scene("hipr_update_scene_geometry", s, checked)) return st;
+    const ResidentScene& r = c->scene;
+    if (!r.ready) return fail(HIPR_ERROR_NOT_READY, "hipr_update_scene_geometry: no scene uploaded");
+    // Meshes, materials and textures stay on the device as uploaded: the description was validated against ITS pools, so those must be the
     // uploaded ones in size -- an index that is in range for a larger pool of the description would read out of bounds on the device.
-    if (s->material_count != c->uploaded_material_count || s->texture_count != c->uploaded_texture_count || s->vertex_count != c->uploaded_vertex_count ||
-        s->index_count != c->uploaded_index_count || s->texel_bytes != c->uploaded_texel_bytes)
+    if (s->material_count != r.uploaded_materials.size() || s->texture_count != r.uploaded_texture_count || s->vertex_count != r.uploaded_vertex_count ||
+        s->index_count != r.uploaded_index_count || s->texel_bytes != r.uploaded_texel_bytes)
         return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: material, texture, vertex, index and texel pool sizes must equal the uploaded scene's (those pools are not re-uploaded)");
-    const DeviceScene& d = c->scene;
-    if (s->node_count != d.node_count || s->triangle_count != d.triangle_count || (s->wide_nodes ? s->wide_node_count : 0u) != d.wide_node_count || s->light_count != d.light_count ||
-        size_t(s->instance_count) * sizeof(HiprInstance) != c->uploaded_instance_bytes)
+    if (s->node_count != r.args.node_count || s->triangle_count != r.args.triangle_count || (s->wide_nodes ? s->wide_node_count : 0u) != r.args.wide_node_count ||
+        s->light_count != r.args.light_count || s->instance_count != r.uploaded_instances.size())
         return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: node, triangle, instance and light counts must equal the uploaded scene's (a refit keeps the topology)");
-    uint32_t wide_stack_need = 0;
-    char invalid[256];
-    if (validate_scene(s, wide_stack_need, invalid, sizeof(invalid))) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: %s", invalid);
-    if (wide_stack_need != c->wide_stack_entries) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: the wide BVH's topology changed");
-    uint32_t wide8_height = 0;
-    if (validate_wide8(s, wide8_height, invalid, sizeof(invalid))) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: %s", invalid);
-    if (c->wide8.slot_count && (s->wide8_slot_count != c->wide8.slot_count || wide8_height != c->wide8_height))
+    if (checked.wide_stack_need != r.wide_stack_entries) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: the wide BVH's topology changed");
+    if (r.wide8.slot_count && (s->wide8_slot_count != r.wide8.slot_count || checked.wide8_height != r.wide8_height))
         return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: the 8-wide tree's topology changed");
-    // The lights ARE uploaded again (they move), but the kernels were instantiated for the kinds of light the upload brought -- environment code or not -- and the
-    // environment's own data is not part of a refit: a light may move, not change its type.
-    for (uint32_t l = 0; l < s->light_count; ++l)
-        if ((s->lights[l].flags & HIPR_LIGHT_TYPE_MASK) != c->uploaded_light_types[l])
-            return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: light %u changes its type (%u -> %u); upload the scene instead", l, c->uploaded_light_types[l], s->lights[l].flags & HIPR_LIGHT_TYPE_MASK);
+    if (int st = r.lights_keep_their_types("hipr_update_scene_geometry", s->lights, s->light_count)) return st;
     if (int finish_status = finish_all(c)) return finish_status;      // pipelined passes included: no pending pass may go on over the new geometry
-    hipStream_t st = c->stream;
-    int r = 0;
-    r |= c->nodes.upload(s->nodes, size_t(s->node_count) * sizeof(HiprBvhNode), st);
-    if (d.wide_node_count) r |= c->wide_nodes.upload(s->wide_nodes, size_t(s->wide_node_count) * sizeof(HiprWideNode), st);
-    r |= c->triangles.upload(s->triangles, size_t(s->triangle_count) * sizeof(HiprTriangle), st);
-    r |= c->instances.upload(s->instances, size_t(s->instance_count) * sizeof(HiprInstance), st);
-    r |= c->lights.upload(s->lights, size_t(s->light_count) * sizeof(HiprLight), st);
-    if (r) return r < 0 ? r : HIPR_ERROR_HIP;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (c->wide8.slot_count)
-        if (int status = upload_wide8(c, s, wide8_height)) return status;
-    int models = 0;   // the instances were re-uploaded: a changed material_index may reference another shading model -- of the material pool the DEVICE holds
-    for (uint32_t i = 0; i < s->instance_count; ++i) models |= 1 << std::min<int>(c->uploaded_materials[s->instances[i].material_index].shading_model, 2);
-    c->shading_models = models ? models : 7;
-    if (int status = build_derived_geometry(c, s, false)) return status;
-    return prepare_refit(c, s, false);      // also ends the state a device refit left (hipr_refit_scene_transforms)
+    return c->scene.update_geometry(s, checked, c->trace_variant, c->cull_backfaces, c->stream);
 }
 
 int hipr_refit_scene_transforms(HiprContext* c, const HiprInstanceTransform* moved, uint32_t moved_count, const HiprLight* lights, uint32_t light_count, HiprRefitResult* out) {
     if (int st = check_context(c)) return st;
     if (!out || (moved_count && !moved)) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_refit_scene_transforms: null argument");
-    if (!c->scene_ready) return fail(HIPR_ERROR_NOT_READY, "hipr_refit_scene_transforms: no scene uploaded");
-    const DeviceScene& d = c->scene;
+    const ResidentScene& r = c->scene;
+    if (!r.ready) return fail(HIPR_ERROR_NOT_READY, "hipr_refit_scene_transforms: no scene uploaded");
     // Scenes that are not traced through the 8-wide tree have at most 64 BVH2 nodes (or a tree too high for the kernels, or a search forced for an experiment): the
     // host path costs nothing there, and the arrays their search walks are the ones this call leaves stale. The exhaustive search's items are built on the host.
-    if (c->wide8.slot_count == 0 || !c->use_wide8() || d.trace_item_count != 0 || d.triangle_count > 0x55555555u)
+    if (r.wide8.slot_count == 0 || !c->use_wide8() || r.args.trace_item_count != 0 || r.args.triangle_count > 0x55555555u)
         return fail(HIPR_ERROR_UNSUPPORTED, "hipr_refit_scene_transforms: the uploaded scene is not traced through the 8-wide tree; refit on the host and call hipr_update_scene_geometry");
     for (uint32_t k = 0; k < moved_count; ++k) {
-        if (moved[k].instance_index >= c->uploaded_instances.size())
-            return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_refit_scene_transforms: instance %u of %zu", moved[k].instance_index, c->uploaded_instances.size());
+        if (moved[k].instance_index >= r.uploaded_instances.size())
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_refit_scene_transforms: instance %u of %zu", moved[k].instance_index, r.uploaded_instances.size());
         for (int e = 0; e < 12; ++e)
             if (!std::isfinite(moved[k].object_to_world[e])) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_refit_scene_transforms: the matrix of instance %u is not finite", moved[k].instance_index);
         // A mirrored instance is drawn from index triples of its own (two corners exchanged): that changes the triangle array, which stays the host path's business.
-        if (refit_mirrors(moved[k].object_to_world) != refit_mirrors(c->uploaded_instances[moved[k].instance_index].object_to_world))
+        if (refit_mirrors(moved[k].object_to_world) != refit_mirrors(r.uploaded_instances[moved[k].instance_index].object_to_world))
             return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_refit_scene_transforms: the matrix of instance %u changes its handedness; refit on the host", moved[k].instance_index);
     }
     if (lights) {
-        if (light_count != d.light_count) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_refit_scene_transforms: %u lights given, the uploaded scene has %u", light_count, d.light_count);
-        for (uint32_t l = 0; l < light_count; ++l)
-            if ((lights[l].flags & HIPR_LIGHT_TYPE_MASK) != c->uploaded_light_types[l])
-                return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_refit_scene_transforms: light %u changes its type (%u -> %u); upload the scene instead", l, c->uploaded_light_types[l], lights[l].flags & HIPR_LIGHT_TYPE_MASK);
+        if (light_count != r.args.light_count) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_refit_scene_transforms: %u lights given, the uploaded scene has %u", light_count, r.args.light_count);
+        if (int st = r.lights_keep_their_types("hipr_refit_scene_transforms", lights, light_count)) return st;
     }
     if (int finish_status = finish_all(c)) return finish_status;      // no pending pass may go on over the new geometry
-    hipStream_t st = c->stream;
-    *out = {};
-    if (lights && light_count) {
-        if (int r = c->lights.upload(lights, size_t(light_count) * sizeof(HiprLight), st)) return r;
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    if (moved_count) {
-        std::vector<uint32_t> flags(c->uploaded_instances.size(), 0u);
-        std::vector<HiprInstance> instances = c->uploaded_instances;      // becomes the context's copy once the device holds it (after the last synchronise)
-        for (uint32_t k = 0; k < moved_count; ++k) {
-            std::memcpy(instances[moved[k].instance_index].object_to_world, moved[k].object_to_world, sizeof(moved[k].object_to_world));
-            flags[moved[k].instance_index] = 1u;
-        }
-        HIP_TRY(hipMemcpyAsync(c->instances.ptr, instances.data(), instances.size() * sizeof(HiprInstance), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(c->refit_moved.ptr, flags.data(), flags.size() * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(c->refit_scratch.ptr, 0, REFIT_SCRATCH_BYTES, st));
-        // pass 1: world-space triangles and the scene's bounds
-        const uint32_t blocks = (d.triangle_count + REFIT_BLOCK - 1) / REFIT_BLOCK;
-        hipLaunchKernelGGL(k_refit_triangles, dim3(blocks), dim3(REFIT_BLOCK), 0, st, c->triangles.as<HiprTriangle>(), d.triangle_count, c->instances.as<HiprInstance>(), c->refit_moved.as<uint32_t>(),
-                           c->indices.as<uint32_t>(), c->geometry.as<HiprVertexGeometry>(), c->refit_partial.as<RefitBound>());
-        hipLaunchKernelGGL(k_refit_bounds_final, dim3(1), dim3(REFIT_BLOCK), 0, st, c->refit_partial.as<RefitBound>(), blocks, c->refit_scratch.as<RefitBound>());
-        HIP_TRY(hipGetLastError());
-        RefitBound bounds[6];
-        HIP_TRY(hipMemcpyAsync(bounds, c->refit_scratch.ptr, sizeof(bounds), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));      // `flags` and the instances are read by now as well
-        const float lo[3] = {bounds[0].v, bounds[1].v, bounds[2].v}, hi[3] = {bounds[3].v, bounds[4].v, bounds[5].v};
-        float grid_min[3], grid_cell[3];
-        refit_grid(lo, hi, grid_min, grid_cell);      // the moved scene's bounds: node origins must not be clamped at the ends of a stale grid
-        // passes 2 - 4, then the records derived from the triangles
-        queue_refit_tree<true>(c, grid_min, grid_cell);
-        hipLaunchKernelGGL(k_build_shade_triangles, dim3((d.triangle_count + 255) / 256), dim3(256), 0, st, d, c->shade_triangles.as<float4>());
-        hipLaunchKernelGGL(k_build_trace_triangles, dim3((d.triangle_count + 255) / 256), dim3(256), 0, st, d.triangles, d.triangle_count, c->trace_triangles.as<float4>());
-        HIP_TRY(hipGetLastError());
-        struct { uint32_t flag; uint32_t pad[3]; double area; } tail = {};
-        static_assert(REFIT_SCRATCH_AREA - REFIT_SCRATCH_FLAG == 16, "the flag and the area are read back together");
-        HIP_TRY(hipMemcpyAsync(&tail, c->refit_scratch.as<char>() + REFIT_SCRATCH_FLAG, sizeof(tail), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        c->uploaded_instances.swap(instances);
-        c->tree_stale = true;
-        for (int a = 0; a < 3; ++a) { c->wide8.grid_min[a] = grid_min[a]; c->wide8.grid_cell[a] = grid_cell[a]; }
-        c->current_half_area = tail.area;
-        if (tail.flag) {      // a pair parted: this tree cannot hold the scene any more
-            c->scene_ready = false;
-            out->needs_rebuild = 1;
-        }
-    }
-    out->child_half_area = c->current_half_area;
-    out->uploaded_half_area = c->uploaded_half_area;
-    for (int a = 0; a < 3; ++a) { out->grid_min[a] = c->wide8.grid_min[a]; out->grid_cell[a] = c->wide8.grid_cell[a]; }
-    return HIPR_OK;
+    return c->scene.refit_transforms(moved, moved_count, lights, light_count, c->stream, out);
 }
 
 int hipr_debug_read_scene_buffer(HiprContext* c, int which, void* out, uint64_t capacity_bytes) {
     if (int st = check_context(c)) return st;
     if (!out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: null output");
-    if (c->scene.triangle_count == 0 && c->wide8.slot_count == 0) return fail(HIPR_ERROR_NOT_READY, "hipr_debug_read_scene_buffer: no scene uploaded");
+    if (c->scene.args.triangle_count == 0 && c->scene.wide8.slot_count == 0) return fail(HIPR_ERROR_NOT_READY, "hipr_debug_read_scene_buffer: no scene uploaded");
     const void* from = nullptr;
     uint64_t bytes = 0;
-    if (which == HIPR_SCENE_BUFFER_TRIANGLES) { from = c->triangles.ptr; bytes = uint64_t(c->scene.triangle_count) * sizeof(HiprTriangle); }
-    else if (which == HIPR_SCENE_BUFFER_WIDE8_SLOTS) { from = c->wide8_slots.ptr; bytes = uint64_t(c->wide8.slot_count) * sizeof(HiprSlot8); }
+    if (which == HIPR_SCENE_BUFFER_TRIANGLES) { from = c->scene.triangles.ptr; bytes = uint64_t(c->scene.args.triangle_count) * sizeof(HiprTriangle); }
+    else if (which == HIPR_SCENE_BUFFER_WIDE8_SLOTS) { from = c->scene.wide8_slots.ptr; bytes = uint64_t(c->scene.wide8.slot_count) * sizeof(HiprSlot8); }
     else return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: unknown buffer %d", which);
     if (capacity_bytes < bytes) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: %llu bytes needed, %llu given", (unsigned long long)bytes, (unsigned long long)capacity_bytes);
     if (int finish_status = finish_all(c)) return finish_status;
@@ -1448,8 +1481,8 @@ int hipr_debug_read_scene_buffer(HiprContext* c, int which, void* out, uint64_t 
 int hipr_set_scene_state(HiprContext* c, const HiprSceneState* state) {
     if (int s = check_context(c)) return s;
     if (!state) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null scene state");
-    for (int i = 0; i < 3; ++i) c->scene.env_tint[i] = state->environment_tint[i];
-    c->scene.next_event_sample_count = std::min(std::max(state->next_event_sample_count, 0), 256);
+    for (int i = 0; i < 3; ++i) c->scene.args.env_tint[i] = state->environment_tint[i];
+    c->scene.args.next_event_sample_count = std::min(std::max(state->next_event_sample_count, 0), 256);
     return HIPR_OK;
 }
 
@@ -1457,7 +1490,6 @@ int hipr_set_frame(HiprContext* c, const HiprFrameDesc* f) {
     if (int s = check_context(c)) return s;
     if (!f || f->width == 0 || f->height == 0 || f->tile_stride == 0 || f->tile_phase >= f->tile_stride || f->samples_per_pass == 0)
         return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_set_frame: bad frame description");
-    if (int finish_status = finish_all(c)) return finish_status;
     FrameInfo fi;
     fi.width = f->width; fi.height = f->height;
     fi.tiles_x = (f->width + 7) / 8;
@@ -1468,6 +1500,8 @@ int hipr_set_frame(HiprContext* c, const HiprFrameDesc* f) {
     set_frame_divisors(fi);
     const uint64_t slots = uint64_t(fi.owned_tiles) * 64u * fi.samples_per_pass;
     if (slots == 0 || slots > 0x7FFFFFFFull) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_set_frame: %llu path slots per pass", (unsigned long long)slots);
+    if (int finish_status = finish_all(c)) return finish_status;
+    c->frame_ready = false;      // a failure below leaves HIPR_ERROR_NOT_READY, not the earlier frame's flag over this frame's buffers
     c->frame = fi;
     int r = partition_path_slots(c);
     const size_t acc_bytes = size_t(fi.owned_tiles) * 64 * sizeof(double4);
@@ -1478,8 +1512,8 @@ int hipr_set_frame(HiprContext* c, const HiprFrameDesc* f) {
     if (r) return HIPR_ERROR_OUT_OF_MEMORY;
     HIP_TRY(hipMemsetAsync(c->accumulation.ptr, 0, acc_bytes, c->stream));
     if (int finish_status = finish_all(c)) return finish_status;
-    c->frame_ready = true;
     c->traced_samples = 0;
+    c->frame_ready = true;
     return HIPR_OK;
 }
 
@@ -1541,7 +1575,7 @@ int hipr_render_pass(HiprContext* c, const HiprCameraState* camera, void* out_ha
 int hipr_trace_pass(HiprContext* c, const HiprCameraState* camera) {
     if (int s = check_context(c)) return s;
     if (!camera) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null camera");
-    if (!c->tables_ready || !c->scene_ready || !c->frame_ready) return fail(HIPR_ERROR_NOT_READY, "tables, scene and frame must be set before rendering");
+    if (!c->tables_ready || !c->scene.ready || !c->frame_ready) return fail(HIPR_ERROR_NOT_READY, "tables, scene and frame must be set before rendering");
     if (c->partitioned_for != c->wavefronts_wanted()) {      // the scene uploaded since hipr_set_frame wants another split of the path slots
         if (int s = finish_all(c)) return s;
         for (int g = 0; g < MAX_WAVEFRONTS; ++g) if (c->wavefronts[g].stream) HIP_TRY(hipStreamSynchronize(c->wavefronts[g].stream));
@@ -1746,14 +1780,14 @@ int hipr_get_wavefront_count(HiprContext* c, int* out_count) {
 
 int hipr_get_trace_variant(HiprContext* c, int* out_variant) {
     if (!c || !out_variant) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_get_trace_variant: null argument");
-    *out_variant = c->scene_ready ? c->active_trace_variant() : HIPR_TRACE_BVH2;
+    *out_variant = c->scene.ready ? c->active_trace_variant() : HIPR_TRACE_BVH2;
     return HIPR_OK;
 }
 
 int hipr_set_trace_variant(HiprContext* c, int variant) {
     if (!c) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null context");
     if (variant < -1 || variant > HIPR_TRACE_WIDE8_PERSISTENT) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_set_trace_variant: unknown variant %d", variant);
-    if (c->tree_stale && (variant == HIPR_TRACE_BVH2 || variant == HIPR_TRACE_WIDE_PERSISTENT))
+    if (c->scene.tree_stale && (variant == HIPR_TRACE_BVH2 || variant == HIPR_TRACE_WIDE_PERSISTENT))
         return fail(HIPR_ERROR_UNSUPPORTED, "hipr_set_trace_variant: the BVH2 and 4-wide arrays are stale after hipr_refit_scene_transforms; call hipr_update_scene_geometry or hipr_upload_scene first");
     c->trace_variant = variant;     // the exhaustive search's items are built at upload: upload the scene after this call
     return HIPR_OK;
@@ -1763,7 +1797,7 @@ int hipr_set_backface_culling(HiprContext* c, int enable) {
     if (int s = check_context(c)) return s;
     if (int s = finish_all(c)) return s;
     c->cull_backfaces = enable != 0;
-    c->wide8.cull_backfaces = c->cull_backfaces ? 1u : 0u;
+    c->scene.wide8.cull_backfaces = c->cull_backfaces ? 1u : 0u;
     return HIPR_OK;
 }
 
@@ -1903,7 +1937,6 @@ int hipr_debug_generate(HiprContext* c, const HiprCameraState* camera, uint32_t 
     if (int finish_status = finish_all(c)) return finish_status;
     if (out_origin_tmin) HIP_TRY(hipMemcpy(out_origin_tmin, bo.ptr, size_t(n) * 16, hipMemcpyDeviceToHost));
     if (out_direction) HIP_TRY(hipMemcpy(out_direction, bd.ptr, size_t(n) * 16, hipMemcpyDeviceToHost));
-    bo.release(); bd.release(); bt.release(); bm.release(); br.release();
     if (out_pixel) {
         for (uint32_t k = 0; k < n; ++k) {
             uint32_t tile = (k >> 6) * f.tile_stride + f.tile_phase, lane = k & 63;
@@ -1922,35 +1955,33 @@ int hipr_debug_shading(HiprContext* c, int shading_model, const float* params10,
     DeviceBuffer bp, bw, bi, bo;
     int r = bp.upload(params10, 10 * 4, c->stream) | bw.upload(wo_n3, size_t(n) * 12, c->stream) | bi.upload(in_n3, size_t(n) * 12, c->stream) | bo.resize(size_t(n) * 28);
     if (r) return HIPR_ERROR_OUT_OF_MEMORY;
-    c->shade_unit().debug_shading(c->stream, c->scene.tables, shading_model, bp.as<float>(), bw.as<float>(), bi.as<float>(), int(n), mode, bo.as<float>());
+    c->shade_unit().debug_shading(c->stream, c->scene.args.tables, shading_model, bp.as<float>(), bw.as<float>(), bi.as<float>(), int(n), mode, bo.as<float>());
     HIP_TRY(hipGetLastError());
     if (int finish_status = finish_all(c)) return finish_status;
     HIP_TRY(hipMemcpy(out_n7, bo.ptr, size_t(n) * 28, hipMemcpyDeviceToHost));
-    bp.release(); bw.release(); bi.release(); bo.release();
     return HIPR_OK;
 }
 
 int hipr_debug_shade(HiprContext* c, const HiprCameraState* camera, uint32_t n, const float* rays_n8, const float* throughput_bounces_n4, const float* hits_n4, const uint32_t* last_triangle,
                      const uint32_t* pixel_hash, const uint32_t* accumulation, float* out_n32) {
     if (int s = check_context(c)) return s;
-    if (!c->tables_ready || !c->scene_ready) return fail(HIPR_ERROR_NOT_READY, "hipr_debug_shade needs the tables and a scene");
+    if (!c->tables_ready || !c->scene.ready) return fail(HIPR_ERROR_NOT_READY, "hipr_debug_shade needs the tables and a scene");
     if (!camera || !rays_n8 || !throughput_bounces_n4 || !hits_n4 || !last_triangle || !pixel_hash || !accumulation || !out_n32) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_shade: null argument");
     if (n == 0) return HIPR_OK;
     for (uint32_t i = 0; i < n; ++i) {      // the entries name triangles and lights of the uploaded scene
         uint32_t id;
         std::memcpy(&id, hits_n4 + 4 * size_t(i) + 3, 4);
         if (id == HIPR_HIT_MISS) continue;
-        if ((id & HIPR_HIT_LIGHT) ? (id & ~HIPR_HIT_LIGHT) >= c->scene.light_count : id >= c->scene.triangle_count) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_shade: entry %u names hit %u outside the scene", i, id);
+        if ((id & HIPR_HIT_LIGHT) ? (id & ~HIPR_HIT_LIGHT) >= c->scene.args.light_count : id >= c->scene.args.triangle_count) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_shade: entry %u names hit %u outside the scene", i, id);
     }
     DeviceBuffer br, bt, bh, bl, bp, ba, bo;
     if (br.upload(rays_n8, size_t(n) * 32, c->stream) | bt.upload(throughput_bounces_n4, size_t(n) * 16, c->stream) | bh.upload(hits_n4, size_t(n) * 16, c->stream) |
         bl.upload(last_triangle, size_t(n) * 4, c->stream) | bp.upload(pixel_hash, size_t(n) * 4, c->stream) | ba.upload(accumulation, size_t(n) * 4, c->stream) | bo.resize(size_t(n) * 128))
         return HIPR_ERROR_OUT_OF_MEMORY;
-    c->shade_unit().debug_shade(c->stream, c->scene, *camera, n, br.as<float4>(), bt.as<float4>(), bh.as<float4>(), bl.as<uint32_t>(), bp.as<uint32_t>(), ba.as<uint32_t>(), bo.as<float>());
+    c->shade_unit().debug_shade(c->stream, c->scene.args, *camera, n, br.as<float4>(), bt.as<float4>(), bh.as<float4>(), bl.as<uint32_t>(), bp.as<uint32_t>(), ba.as<uint32_t>(), bo.as<float>());
     HIP_TRY(hipGetLastError());
     if (int finish_status = finish_all(c)) return finish_status;
     HIP_TRY(hipMemcpy(out_n32, bo.ptr, size_t(n) * 128, hipMemcpyDeviceToHost));
-    br.release(); bt.release(); bh.release(); bl.release(); bp.release(); ba.release(); bo.release();
     return HIPR_OK;
 }
 
@@ -1964,7 +1995,6 @@ int hipr_debug_math(HiprContext* c, int function, uint32_t n, const float* x, co
     HIP_TRY(hipGetLastError());
     if (int finish_status = finish_all(c)) return finish_status;
     HIP_TRY(hipMemcpy(out, bo.ptr, size_t(n) * 4, hipMemcpyDeviceToHost));
-    bx.release(); by.release(); bo.release();
     return HIPR_OK;
 }
 
@@ -1979,7 +2009,6 @@ int hipr_debug_light(HiprContext* c, const HiprLight* light, const float* positi
     HIP_TRY(hipGetLastError());
     if (int finish_status = finish_all(c)) return finish_status;
     HIP_TRY(hipMemcpy(out_n8, bo.ptr, size_t(n) * 32, hipMemcpyDeviceToHost));
-    bp.release(); bi.release(); bo.release();
     return HIPR_OK;
 }
 
@@ -2022,9 +2051,8 @@ int hipr_debug_valu_issue_rates(HiprContext* c, double* out3) {
     const uint32_t seed[12] = {0x3f800000u, 0x3f810000u, 0x3f820000u, 0x3f830000u, 0x3f840000u, 0x3f850000u, 0x3f860000u, 0x3f870000u, 0x3f7fff00u, 0x3f7ffe00u, 0x33800000u, 0x33900000u};
     if (int s = c->debug_a.upload(seed, sizeof(seed), c->stream)) return s;
     if (int s = c->debug_b.resize(size_t(blocks) * threads * 4)) return s;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    const Event e0 = make_event(hipEventDefault), e1 = make_event(hipEventDefault);
+    if (!e0 || !e1) return fail(HIPR_ERROR_HIP, "hipEventCreate failed");
     typedef void (*RateKernel)(uint32_t*, const uint32_t*, int);
     const RateKernel kernels[3] = {k_rate_fma, k_rate_max, k_rate_cvt};
     for (int which = 0; which < 3; ++which) {
@@ -2040,8 +2068,6 @@ int hipr_debug_valu_issue_rates(HiprContext* c, double* out3) {
         }
         out3[which] = double(blocks) * (threads / 64) * double(iterations) * 8.0 / (double(best) * 1e-3);
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return HIPR_OK;
 }
 
@@ -2065,7 +2091,7 @@ static int debug_prepare_rays(HiprContext* c, const float* rays, uint32_t n, std
 
 int hipr_debug_trace_closest(HiprContext* c, const float* rays, const uint32_t* skip, uint32_t n, float* out_hits) {
     if (int s = check_context(c)) return s;
-    if (!c->scene_ready) return fail(HIPR_ERROR_NOT_READY, "no scene uploaded");
+    if (!c->scene.ready) return fail(HIPR_ERROR_NOT_READY, "no scene uploaded");
     if (!rays || !out_hits) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return HIPR_OK;
     std::vector<float> o, d;
@@ -2078,22 +2104,21 @@ int hipr_debug_trace_closest(HiprContext* c, const float* rays, const uint32_t* 
     if (r) return HIPR_ERROR_OUT_OF_MEMORY;
     HIP_TRY(hipMemsetAsync(c->counters.ptr, 0, sizeof(DeviceCounters), c->stream));
     PathState in = {bo.as<float4>(), bd.as<float4>(), nullptr, bm.as<uint2>()};
-    Wavefront w;   // borrows the buffers above; never released
+    Wavefront w;
     w.stream = c->stream;
-    w.hits = bh;
+    w.hits = std::move(bh);
     if (c->instrument) launch_trace_closest<true>(c, w, in, bc.as<uint32_t>(), n);
     else launch_trace_closest<false>(c, w, in, bc.as<uint32_t>(), n);
     if (int finish_status = finish_all(c)) return finish_status;
-    HIP_TRY(hipMemcpy(out_hits, bh.ptr, size_t(n) * 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_hits, w.hits.ptr, size_t(n) * 16, hipMemcpyDeviceToHost));
     c->total = {};
     c->total.closest_rays = n;
-    bo.release(); bd.release(); bm.release(); bh.release(); bc.release();
     return HIPR_OK;
 }
 
 int hipr_debug_trace_shadow(HiprContext* c, const float* rays, uint32_t n, float* out_transmittance) {
     if (int s = check_context(c)) return s;
-    if (!c->scene_ready) return fail(HIPR_ERROR_NOT_READY, "no scene uploaded");
+    if (!c->scene.ready) return fail(HIPR_ERROR_NOT_READY, "no scene uploaded");
     if (!rays || !out_transmittance) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return HIPR_OK;
     std::vector<float> o(size_t(n) * 4), d(size_t(n) * 4), rad(size_t(n) * 4, 0.0f), ones(size_t(n) * 4, 1.0f);
@@ -2108,21 +2133,19 @@ int hipr_debug_trace_shadow(HiprContext* c, const float* rays, uint32_t n, float
             bacc.upload(rad.data(), rad.size() * 4, c->stream) | bc.upload(&n, 4, c->stream);
     if (r) return HIPR_ERROR_OUT_OF_MEMORY;
     HIP_TRY(hipMemsetAsync(c->counters.ptr, 0, sizeof(DeviceCounters), c->stream));
-    Wavefront w;   // borrows the buffers above; never released
+    Wavefront w;
     w.stream = c->stream;
-    w.shadow[0] = bo; w.shadow[1] = bd; w.shadow[2] = br;
-    const DeviceBuffer saved_radiance = c->radiance;
-    c->radiance = bacc;
+    w.shadow[0] = std::move(bo); w.shadow[1] = std::move(bd); w.shadow[2] = std::move(br);
+    std::swap(c->radiance, bacc);      // the launch writes the context's radiance buffer: this call's, for its duration
     if (c->instrument) launch_trace_shadow<true>(c, w, bc.as<uint32_t>(), n);
     else launch_trace_shadow<false>(c, w, bc.as<uint32_t>(), n);
-    c->radiance = saved_radiance;
+    std::swap(c->radiance, bacc);
     if (int finish_status = finish_all(c)) return finish_status;
     std::vector<float> result(size_t(n) * 4);
     HIP_TRY(hipMemcpy(result.data(), bacc.ptr, result.size() * 4, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n; ++i) out_transmittance[i] = result[4 * i];
     c->total = {};
     c->total.shadow_rays = n;
-    bo.release(); bd.release(); br.release(); bacc.release(); bc.release();
     return HIPR_OK;
 }
 

@@ -328,11 +328,17 @@ int hipr_set_stream(HiprContext* context, void* hip_stream);
 /* Uploads: the tables of OR/Renderer.cpp:380-467 and the scene of handle_updates :578-1205     */
 /* ------------------------------------------------------------------------------------------- */
 int hipr_upload_tables(HiprContext* context, const HiprTables* tables);
+/* Every refusal -- the checks of hipr_validate_scene, then HIPR_ERROR_UNSUPPORTED for what the kernels cannot serve: a BVH2 deeper than 64, a wide BVH that
+ * needs more stack than the traversal kernels have, an environment map that is not RGBA -- comes before the device is touched and leaves the resident scene as
+ * it was. The same holds for hipr_update_scene_geometry and hipr_refit_scene_transforms. A call of the three that fails AFTER that (out of memory, a HIP error)
+ * leaves no scene: rendering returns HIPR_ERROR_NOT_READY until a hipr_upload_scene succeeds. */
 int hipr_upload_scene(HiprContext* context, const HiprSceneDesc* scene);
 /* The host-side checks hipr_upload_scene runs before anything reaches the device, on their own (no context, no GPU): every index
  * the kernels follow -- material texture IDs, instance material / pool offsets, triangle instance / primitive / vertex indices,
- * texture extents inside the texel pool, BVH2 and wide BVH child and leaf ranges -- must be in range; HIPR_ERROR_INVALID_ARGUMENT
- * and a message in hipr_last_error() otherwise. (OptiX validates its node graph in rtContextValidate; this is the counterpart.) */
+ * texture extents inside the texel pool, BVH2, wide BVH and 8-wide tree child and leaf ranges -- must be in range; an attribute an
+ * instance flags (HIPR_MESH_TEXCOORDS / TINTS / EMISSIVE) must have its pool; an environment description must be complete (a map among
+ * the textures, the per-pixel PDF with its extents, the samples with their count). HIPR_ERROR_INVALID_ARGUMENT and a message in
+ * hipr_last_error() otherwise. (OptiX validates its node graph in rtContextValidate; this is the counterpart.) */
 int hipr_validate_scene(const HiprSceneDesc* scene);
 /* Transform-only update: the same scene after its host refitted the BVH to moved instances (the reference refits its root acceleration
  * structure when a node moves, OR/Renderer.cpp:472,1010-1041). Re-uploads nodes, wide nodes, triangles, instances and lights, whose
@@ -380,7 +386,8 @@ int hipr_set_entry_point(HiprContext* context, int entry);
 int hipr_use_scratch_accumulation(HiprContext* context, int enable);
 
 /* (Re)allocates the f64 accumulation buffer and the wavefront queues for the owned tiles;
- * resets nothing else. Replaces accumulation_buffer->setSize (OR/Renderer.cpp:1215-1219). */
+ * resets nothing else. Replaces accumulation_buffer->setSize (OR/Renderer.cpp:1215-1219). A bad description is refused with the frame
+ * as it was; a failure after that (out of memory) leaves no frame: HIPR_ERROR_NOT_READY until a hipr_set_frame succeeds. */
 int hipr_set_frame(HiprContext* context, const HiprFrameDesc* frame);
 /* Number of pixels this context owns under the current frame description. */
 int hipr_owned_pixel_count(HiprContext* context, uint32_t* out_count);
