@@ -4,6 +4,9 @@
 // path / hit / shadow queues and the f64 accumulation buffer, and drives the per-pass kernel loop
 //   generate -> { trace_closest -> shade(+compact) -> trace_shadow } until no path is alive -> accumulate.
 // Replaces the OptiX context + context->launch() of OR/Renderer.cpp:273-574,1250-1265.
+// A pass (hipr_trace_pass) is begin_pass, start_wavefront for each wavefront, advance_wavefront round robin until none is left (or detach_tail, pipelined);
+// a bounce is enqueue_bounce = launch_trace + launch_shade + the read-back of its sizes, and book_bounce keeps the counters of all of them. What tunes a
+// context is in Knobs; drain() is where every queued pass has ended, on the device and in the books.
 // There is no CPU fallback: every entry point that needs the GPU fails with a status code.
 #include "kernels.h"
 #ifndef HIPR_WIDE8_LOW_BUCKET
@@ -193,6 +196,51 @@ private:
     template <bool WRITE> void queue_refit_tree(const float* grid_min, const float* grid_cell, hipStream_t stream) const;
 };
 
+// What tunes a context: read from the environment once, when the context is made (knobs_from_environment), and written by the setters of the C-ABI that are named here.
+struct Knobs {
+    int wavefront_limit = 0;            // hipr_set_wavefront_count / HIPR_WAVEFRONTS; 0 = by scene: see HiprContext::wavefronts_wanted()
+    int trace_variant = -1;             // hipr_set_trace_variant / HIPR_TRACE_VARIANT: the search of the NEXT upload (HIPR_TRACE_*), -1: pick by BVH size
+    int arithmetic = HIPR_ARITHMETIC_FAST;     // hipr_set_arithmetic / HIPR_ARITHMETIC=exact: which build of the shade unit the context launches (launch.h ShadeUnit)
+    bool cull_backfaces = true;         // hipr_set_backface_culling / HIPR_BACKFACE_CULLING=0
+    bool pipeline_passes = false;       // hipr_set_pass_pipelining / HIPR_PIPELINE_PASSES=1; off by default: measured slower (DESIGN.md section 5)
+    int pipeline_spare_blocks = 1;      // HIPR_PIPELINE_SPARE_BLOCKS: blocks per CU a pipelined pass leaves to the other slot's tail
+    bool lean_trace = true;             // HIPR_LEAN_TRACE=0: always the full kernel
+    bool lean_shade = true;             // HIPR_LEAN_SHADE=0: always the full kernel
+    bool coherence_sort = false;        // HIPR_COHERENCE_SORT=1: the rays of a fused trace launch are taken by (origin cell, octant), ray_sort.hip (built and measured in round 4: profiles/r04_ab_coherence_sort.txt); inert without HIPR_RAY_SORT
+    bool shade_classes = false;         // HIPR_SHADE_CLASSES=1: coated surface hits listed apart (built and measured in round 4: no gain, profiles/r04_ab_shade_classes.txt)
+    int blocks_per_cu_override = 0;     // HIPR_BLOCKS_PER_CU: persistent trace blocks per CU instead of what the occupancy query says
+    int shade_blocks_per_cu = 0;        // persistent shade blocks per CU = waves per SIMD; 0: 3 (what the kernel is compiled for), 2 for all-Diffuse scenes (HIPR_SHADE_BLOCKS_PER_CU)
+    uint32_t shade_ordered_from = 1u << 18;   // bounces with fewer paths than this are shaded in queue order (HIPR_SHADE_ORDERED_FROM)
+    int refill_below = 40;              // persistent kernels refill a wave once fewer lanes than this are busy (HIPR_REFILL_BELOW)
+    bool shade_split = false;           // HIPR_SHADE_SPLIT=1: the shade kernel as two, next event estimation and the rest (shade_kernel.h; measured, DESIGN.md section 5)
+    bool shade_ordered = true;          // k_classify_hits before k_shade (HIPR_SHADE_ORDERED=0: shade in queue order)
+    bool shade_ordered_camera = false;  // ... also before shade(0) (HIPR_SHADE_ORDERED_CAMERA=1; measured: profiles/r04_ab_knobs.txt)
+    bool trace_log = false;             // HIPR_TRACE_LOG=1: the occupancy queries and, with instrumentation on, every bounce on stderr
+};
+
+Knobs knobs_from_environment() {
+    Knobs k;
+    if (const char* v = getenv("HIPR_TRACE_VARIANT")) k.trace_variant = atoi(v);
+    if (const char* v = getenv("HIPR_REFILL_BELOW")) k.refill_below = atoi(v);
+    if (const char* v = getenv("HIPR_SHADE_ORDERED_FROM")) k.shade_ordered_from = uint32_t(atoll(v));
+    if (const char* v = getenv("HIPR_SHADE_BLOCKS_PER_CU")) k.shade_blocks_per_cu = std::max(1, atoi(v));
+    if (const char* v = getenv("HIPR_BLOCKS_PER_CU")) k.blocks_per_cu_override = atoi(v);
+    if (const char* v = getenv("HIPR_WAVEFRONTS")) k.wavefront_limit = std::max(0, std::min(MAX_WAVEFRONTS, atoi(v)));
+    if (const char* v = getenv("HIPR_TRACE_LOG")) k.trace_log = atoi(v) != 0;
+    if (const char* v = getenv("HIPR_SHADE_CLASSES")) k.shade_classes = atoi(v) != 0;
+    if (const char* v = getenv("HIPR_COHERENCE_SORT")) k.coherence_sort = HIPR_RAY_SORT && atoi(v) != 0;      // only in a build with the experiment linked in (tools/experiments/ray_sort.hip)
+    if (const char* v = getenv("HIPR_LEAN_TRACE")) k.lean_trace = atoi(v) != 0;
+    if (const char* v = getenv("HIPR_LEAN_SHADE")) k.lean_shade = atoi(v) != 0;
+    if (const char* v = getenv("HIPR_SHADE_ORDERED")) k.shade_ordered = atoi(v) != 0;
+    if (const char* v = getenv("HIPR_SHADE_ORDERED_CAMERA")) k.shade_ordered_camera = atoi(v) != 0;
+    if (const char* v = getenv("HIPR_SHADE_SPLIT")) k.shade_split = atoi(v) != 0;
+    if (const char* v = getenv("HIPR_ARITHMETIC")) k.arithmetic = (v[0] == 'e' || v[0] == 'E' || v[0] == '1') ? HIPR_ARITHMETIC_EXACT : HIPR_ARITHMETIC_FAST;
+    if (const char* v = getenv("HIPR_BACKFACE_CULLING")) k.cull_backfaces = atoi(v) != 0;
+    if (const char* v = getenv("HIPR_PIPELINE_PASSES")) k.pipeline_passes = atoi(v) != 0;
+    if (const char* v = getenv("HIPR_PIPELINE_SPARE_BLOCKS")) k.pipeline_spare_blocks = std::max(0, atoi(v));
+    return k;
+}
+
 } // namespace
 
 struct HiprContext {
@@ -201,17 +249,12 @@ struct HiprContext {
     hipStream_t stream = nullptr;       // own_stream, or the one hipr_set_stream lent (never destroyed here)
     Event pass_start;
     Wavefront wavefronts[MAX_WAVEFRONTS];
-    int wavefront_limit = 0;                // hipr_set_wavefront_count / HIPR_WAVEFRONTS; 0 = by scene: see wavefronts_wanted()
+    Knobs knobs;
     int wavefront_count = 1;                // set by partition_path_slots: small frames run as one wavefront
     int partitioned_for = 0;                // the wavefronts_wanted() the current partition was made for
 
     ResidentScene scene;                // the uploaded scene and the argument blocks the kernels take (scene.args, scene.wide8)
-    bool lean_trace = true;             // HIPR_LEAN_TRACE=0: always the full kernel
-    bool lean_shade = true;             // HIPR_LEAN_SHADE=0: always the full kernel
-    int arithmetic = HIPR_ARITHMETIC_FAST;     // hipr_set_arithmetic: which build of the shade unit the context launches (launch.h ShadeUnit)
-    const hipr::ShadeUnit& shade_unit() const { return arithmetic == HIPR_ARITHMETIC_EXACT ? hipr::shade_unit_exact() : hipr::shade_unit_fast(); }
-    bool coherence_sort = false;        // HIPR_COHERENCE_SORT=1: the rays of a fused trace launch are taken by (origin cell, octant), ray_sort.hip (built and measured in round 4: profiles/r04_ab_coherence_sort.txt)
-    bool shade_classes = false;         // HIPR_SHADE_CLASSES=1: coated surface hits listed apart (built and measured in round 4: no gain, profiles/r04_ab_shade_classes.txt)
+    const hipr::ShadeUnit& shade_unit() const { return knobs.arithmetic == HIPR_ARITHMETIC_EXACT ? hipr::shade_unit_exact() : hipr::shade_unit_fast(); }
     DeviceBuffer ggx_rho, dielectric_rho, alpha, sample_offsets, sobol_tables;
     bool tables_ready = false;
 
@@ -236,9 +279,7 @@ struct HiprContext {
     int active_slot = 0;                // the slot whose pass is being queued (next_work_counter)
     int traced_slot = 0;                // the slot of the last hipr_trace_pass: what hipr_accumulate_samples folds
     int next_slot = 0;
-    bool pipeline_passes = false;       // hipr_set_pass_pipelining / HIPR_PIPELINE_PASSES=1; off by default: measured slower (DESIGN.md section 5)
-    bool pipelining_now = false;        // the pass being queued is a pipelined one
-    int pipeline_spare_blocks = 1;      // HIPR_PIPELINE_SPARE_BLOCKS
+    bool pipelining_now = false;        // the pass being queued is a pipelined one (Knobs::pipeline_passes, where the scene and the frame allow it)
     Event accumulated;                  // the last hipr_accumulate_samples: the next one (on the other slot's stream) folds after it
     bool accumulated_valid = false;
     DeviceBuffer radiance_other;        // the other slot's radiance (the two swap when the slots do)
@@ -248,7 +289,6 @@ struct HiprContext {
     bool use_scratch = false;
     int entry = HIPR_ENTRY_PATH_TRACING;
     DeviceBuffer& active_accumulation() { return use_scratch ? scratch_accumulation : accumulation; }
-    int trace_variant = -1;             // 1: persistent kernels, 0: one ray per lane, -1: pick by BVH size (HIPR_TRACE_VARIANT)
     uint32_t wide_stack_entries = 0;
     // persistent kernels walk the compressed 4-wide BVH; without one (HiprSceneDesc::wide_nodes == NULL) the plain BVH2 kernels serve every scene
     // Two half-frame wavefronts on two streams overlap one half's shading with the other's tracing. That pays where the trace kernels are short
@@ -262,7 +302,7 @@ struct HiprContext {
     // therefore always one wavefront with full-size queues, the first pass re-partitioned into two, and -- buffers never shrink -- wavefront 0 kept its full-size
     // queues next to wavefront 1's half: about 1.5x the queue memory of a 64-accumulation 1080p pass, plus a redundant allocation and synchronisation).
     int wavefronts_wanted(bool frame_is_set) const {
-        if (wavefront_limit > 0) return wavefront_limit;
+        if (knobs.wavefront_limit > 0) return knobs.wavefront_limit;
         if (scene.ready && use_persistent()) return frame_is_set && uint64_t(frame.owned_tiles) * 64u * frame.samples_per_pass >= TWO_WAVEFRONTS_FROM_SLOTS ? 2 : 1;
         return 2;
     }
@@ -274,21 +314,13 @@ struct HiprContext {
     bool use_exhaustive() const { return scene.chosen_variant == HIPR_TRACE_EXHAUSTIVE; }
     int active_trace_variant() const { return scene.chosen_variant; }
     int cu_count = 256;
-    int blocks_per_cu_override = 0;     // HIPR_BLOCKS_PER_CU
-    int shade_blocks_per_cu = 0;        // persistent shade blocks per CU = waves per SIMD; 0: 3 (what the kernel is compiled for), 2 for all-Diffuse scenes (HIPR_SHADE_BLOCKS_PER_CU)
-    uint32_t shade_ordered_from = 1u << 18;   // bounces with fewer paths than this are shaded in queue order (HIPR_SHADE_ORDERED_FROM)
-    int refill_below = 40;              // persistent kernels refill a wave once fewer lanes than this are busy (HIPR_REFILL_BELOW)
-    bool cull_backfaces = true;         // hipr_set_backface_culling / HIPR_BACKFACE_CULLING=0
-    bool shade_split = false;           // HIPR_SHADE_SPLIT=1: the shade kernel as two, next event estimation and the rest (shade_kernel.h; measured, DESIGN.md section 5)
-    bool shade_ordered = true;          // k_classify_hits before k_shade (HIPR_SHADE_ORDERED=0: shade in queue order)
-    bool shade_ordered_camera = false;  // ... also before shade(0) (HIPR_SHADE_ORDERED_CAMERA=1; measured: profiles/r04_ab_knobs.txt)
+    // resident blocks per CU of the persistent trace kernels, asked of the runtime at the first launch of each (persistent_launch)
     int persistent_blocks_per_cu[3][3] = {{0, 0, 0}, {0, 0, 0}};   // [shadow][stack bucket]
     int wide8_blocks_per_cu[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};   // [mode][stack bucket]
 
     // bookkeeping
     HiprCounters total = {};   // since hipr_reset_counters
     bool instrument = false;
-    bool trace_log = false;
     DeviceCounters trace_log_previous = {};
     bool timing = true;
     std::vector<Event> event_pool;
@@ -415,139 +447,125 @@ uint32_t* next_work_counter(HiprContext* c) {
     return ring + size_t(index++) * WORK_SET_WORDS;
 }
 
-// One persistent launch over the path queue (closest_count != nullptr), the shadow queue (shadow_count != nullptr) or both.
-template <int STACK, int MODE, bool INSTRUMENT, bool OVERFLOW>
-void launch_persistent(HiprContext* c, const Wavefront& w, const PathState& in, const uint32_t* closest_count, const uint32_t* shadow_count, uint32_t upper_bound, int bucket) {
-    int& per_cu = c->persistent_blocks_per_cu[MODE][bucket];
+// The rays of one trace launch.
+struct TraceWork {
+    PathState in;                       // the path queue: the closest-hit rays
+    const uint32_t* closest_count;      // on the device: the entries of `in`; nullptr in a launch over the shadow queue alone
+    const uint32_t* shadow_count;       // on the device: the entries of the wavefront's shadow queue; nullptr in a launch over the path queue alone
+    uint32_t upper_bound;               // of the rays of the launch: sizes the grid
+    const uint32_t* sorted = nullptr;   // ray_sort.hip's listing of the launch's rays (HIPR_RAY_SORT builds)
+};
+
+// Every instantiation of a kernel family has the family's type: picking a kernel is picking a pointer.
+using Wide8Kernel = void (*)(DeviceScene, Wide8Scene, PathState, float4*, ShadowQueue, float4*, const uint32_t*, const uint32_t*, uint32_t*, int, DeviceCounters*, const uint32_t*);
+using Wide4Kernel = void (*)(DeviceScene, PathState, float4*, ShadowQueue, float4*, const uint32_t*, const uint32_t*, uint32_t*, int, DeviceCounters*);
+using ClosestKernel = void (*)(DeviceScene, PathState, float4*, const uint32_t*, DeviceCounters*);
+using ShadowKernel = void (*)(DeviceScene, ShadowQueue, float4*, const uint32_t*, DeviceCounters*);
+
+// The grid and the claim counters of one persistent launch. The grid: the blocks that stay resident -- asked of the runtime once per family, mode and stack
+// bucket (`per_cu`), HIPR_BLOCKS_PER_CU instead where set -- less `spare_per_cu` of them per CU, and no more than the rays of the launch can occupy.
+struct PersistentLaunch { uint32_t grid; uint32_t* work_counter; };
+template <typename Kernel>
+PersistentLaunch persistent_launch(HiprContext* c, Kernel kernel, const char* family, int stack, int mode, int& per_cu, int spare_per_cu, uint32_t upper_bound) {
     if (per_cu == 0) {
         int blocks = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_persistent<STACK, MODE, INSTRUMENT, OVERFLOW>, TRACE_BLOCK, 0) != hipSuccess || blocks <= 0) blocks = 4;
-        if (c->trace_log) fprintf(stderr, "[hipr] k_trace_persistent<%d, %d>: occupancy query says %d blocks of %d threads per CU\n", STACK, MODE, blocks, TRACE_BLOCK);
-        if (c->blocks_per_cu_override > 0) blocks = c->blocks_per_cu_override;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, TRACE_BLOCK, 0) != hipSuccess || blocks <= 0) blocks = 4;
+        if (c->knobs.trace_log) fprintf(stderr, "[hipr] %s<%d, %d>: occupancy query says %d blocks of %d threads per CU\n", family, stack, mode, blocks, TRACE_BLOCK);
+        if (c->knobs.blocks_per_cu_override > 0) blocks = c->knobs.blocks_per_cu_override;
         per_cu = blocks;
     }
     const uint32_t waves_per_block = TRACE_BLOCK / 64;
-    uint32_t grid = uint32_t(c->cu_count) * uint32_t(per_cu);
-    grid = std::max(1u, std::min(grid, (upper_bound + 63u) / 64u / waves_per_block + 1u));
-    hipLaunchKernelGGL((k_trace_persistent<STACK, MODE, INSTRUMENT, OVERFLOW>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, in, w.hits.as<float4>(), w.shadow_queue(),
-                       c->radiance.as<float4>(), closest_count, shadow_count, next_work_counter(c), c->refill_below, c->counters.as<DeviceCounters>());
+    const uint32_t grid = uint32_t(c->cu_count) * uint32_t(per_cu > 2 ? per_cu - spare_per_cu : per_cu);
+    return {std::max(1u, std::min(grid, (upper_bound + 63u) / 64u / waves_per_block + 1u)), next_work_counter(c)};
 }
 
-// One persistent launch over the 8-wide tree (wide8_kernels.h). The LDS stack is sized by the tree's height: a ray keeps at most one group per level.
+// One persistent launch over the 8-wide tree (wide8_kernels.h).
 template <int STACK, int MODE, bool INSTRUMENT>
-void launch_wide8(HiprContext* c, const Wavefront& w, const PathState& in, const uint32_t* closest_count, const uint32_t* shadow_count, uint32_t upper_bound, int bucket, const uint32_t* sorted = nullptr) {
-    int& per_cu = c->wide8_blocks_per_cu[MODE][bucket];
-    if (per_cu == 0) {
-        int blocks = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_wide8<STACK, MODE, INSTRUMENT>, TRACE_BLOCK, 0) != hipSuccess || blocks <= 0) blocks = 4;
-        if (c->trace_log) fprintf(stderr, "[hipr] k_trace_wide8<%d, %d>: occupancy query says %d blocks of %d threads per CU\n", STACK, MODE, blocks, TRACE_BLOCK);
-        if (c->blocks_per_cu_override > 0) blocks = c->blocks_per_cu_override;
-        per_cu = blocks;
-    }
-    const uint32_t waves_per_block = TRACE_BLOCK / 64;
+void launch_wide8(HiprContext* c, const Wavefront& w, const TraceWork& work, int bucket) {
+    Wide8Kernel kernel = k_trace_wide8<STACK, MODE, INSTRUMENT>;      // the one with all the code: its occupancy sizes the grid of the lean ones below too
     // pipelined passes: one block slot per CU stays free, so that the other slot's tail launches find room next to this pass's persistent blocks
-    uint32_t grid = uint32_t(c->cu_count) * uint32_t(c->pipelining_now && per_cu > 2 ? per_cu - c->pipeline_spare_blocks : per_cu);
-    grid = std::max(1u, std::min(grid, (upper_bound + 63u) / 64u / waves_per_block + 1u));
+    const PersistentLaunch p = persistent_launch(c, kernel, "k_trace_wide8", STACK, MODE, c->wide8_blocks_per_cu[MODE][bucket], c->pipelining_now ? c->knobs.pipeline_spare_blocks : 0, work.upper_bound);
+    // The lean instantiations serve launches that can reach the coverage code and count nothing: without that code for scenes whose triangles are all statically
+    // opaque, with the sampler for 8-bit single-channel textures only where every coverage texture is one.
+    const bool opaque = c->scene.all_triangles_opaque, lean = c->knobs.lean_trace && !INSTRUMENT && MODE != TRACE_CLOSEST && !work.sorted;
 #if HIPR_RAY_SORT
-    if constexpr (MODE == TRACE_FUSED && !INSTRUMENT) if (sorted) {     // ray_sort.hip listed the launch's rays
-        if (c->scene.all_triangles_opaque && c->lean_trace)
-            hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT, false, true>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, c->scene.wide8, in, w.hits.as<float4>(), w.shadow_queue(),
-                               c->radiance.as<float4>(), closest_count, shadow_count, next_work_counter(c), c->refill_below, c->counters.as<DeviceCounters>(), sorted);
-        else
-            hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT, true, true>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, c->scene.wide8, in, w.hits.as<float4>(), w.shadow_queue(),
-                               c->radiance.as<float4>(), closest_count, shadow_count, next_work_counter(c), c->refill_below, c->counters.as<DeviceCounters>(), sorted);
-        return;
-    }
+    if constexpr (MODE == TRACE_FUSED && !INSTRUMENT) if (work.sorted) kernel = opaque && c->knobs.lean_trace ? k_trace_wide8<STACK, MODE, INSTRUMENT, false, true> : k_trace_wide8<STACK, MODE, INSTRUMENT, true, true>;
 #endif
-    if constexpr (!INSTRUMENT && MODE != TRACE_CLOSEST) if (!sorted && !c->scene.all_triangles_opaque && c->scene.coverage_textures_r8 && c->lean_trace) {     // the coverage sampler for 8-bit single-channel textures only
-        hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT, true, false, true>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, c->scene.wide8, in, w.hits.as<float4>(), w.shadow_queue(),
-                           c->radiance.as<float4>(), closest_count, shadow_count, next_work_counter(c), c->refill_below, c->counters.as<DeviceCounters>());
-        return;
-    }
-    // scenes whose triangles are all statically opaque run the kernel without the coverage code (closest-only launches never reach it anyway)
-    if (!INSTRUMENT && MODE != TRACE_CLOSEST && c->scene.all_triangles_opaque && c->lean_trace)
-        hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT, false>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, c->scene.wide8, in, w.hits.as<float4>(), w.shadow_queue(),
-                           c->radiance.as<float4>(), closest_count, shadow_count, next_work_counter(c), c->refill_below, c->counters.as<DeviceCounters>());
-    else
-    hipLaunchKernelGGL((k_trace_wide8<STACK, MODE, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, c->scene.wide8, in, w.hits.as<float4>(), w.shadow_queue(),
-                       c->radiance.as<float4>(), closest_count, shadow_count, next_work_counter(c), c->refill_below, c->counters.as<DeviceCounters>());
+    if constexpr (!INSTRUMENT && MODE != TRACE_CLOSEST) if (lean && !opaque && c->scene.coverage_textures_r8) kernel = k_trace_wide8<STACK, MODE, INSTRUMENT, true, false, true>;
+    if (lean && opaque) kernel = k_trace_wide8<STACK, MODE, INSTRUMENT, false>;
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, c->scene.wide8, work.in, w.hits.as<float4>(), w.shadow_queue(), c->radiance.as<float4>(),
+                       work.closest_count, work.shadow_count, p.work_counter, c->knobs.refill_below, c->counters.as<DeviceCounters>(), work.sorted);
 }
 
-template <int MODE, bool INSTRUMENT>
-void launch_persistent_for_stack(HiprContext* c, const Wavefront& w, const PathState& in, const uint32_t* closest_count, const uint32_t* shadow_count, uint32_t upper_bound, const uint32_t* sorted = nullptr) {
-    // LDS stack entries by the worst case of the wide tree. Trees that need up to 32 entries run with 16 in LDS and the rest in a per-lane scratch
-    // array (traversals rarely get past 16): 4 KB of LDS per wave instead of 8 lets a sixth wave per SIMD stay resident, and the kernel is bound by
-    // the latency of its dependent gathers (atrium, 260 k triangles: 61.0 -> 57.7 ms of trace time per step). Deeper trees (the 10 M triangle
-    // atrium) spill often enough that 32 LDS entries + scratch is the faster split (116.7 vs 119.9 ms).
-    if (c->use_wide8()) {       // height h: at most h - 1 groups wait on the stack
-#if HIPR_WIDE8_LOW_BUCKET
-        if (c->scene.wide8_height <= 9u) launch_wide8<8, MODE, INSTRUMENT>(c, w, in, closest_count, shadow_count, upper_bound, 3, sorted);
-        else
-#endif
-        if (c->scene.wide8_height <= uint32_t(WIDE8_STACK_SHALLOW) + 1u) launch_wide8<WIDE8_STACK_SHALLOW, MODE, INSTRUMENT>(c, w, in, closest_count, shadow_count, upper_bound, 0, sorted);
-        else if (c->scene.wide8_height <= 17u) launch_wide8<16, MODE, INSTRUMENT>(c, w, in, closest_count, shadow_count, upper_bound, 1, sorted);
-        else launch_wide8<32, MODE, INSTRUMENT>(c, w, in, closest_count, shadow_count, upper_bound, 2, sorted);
-        return;
-    }
+// One persistent launch over the 4-wide tree (kernels.h).
+template <int STACK, int MODE, bool INSTRUMENT, bool OVERFLOW>
+void launch_wide4(HiprContext* c, const Wavefront& w, const TraceWork& work, int bucket) {
+    const Wide4Kernel kernel = k_trace_persistent<STACK, MODE, INSTRUMENT, OVERFLOW>;
+    const PersistentLaunch p = persistent_launch(c, kernel, "k_trace_persistent", STACK, MODE, c->persistent_blocks_per_cu[MODE][bucket], 0, work.upper_bound);
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, work.in, w.hits.as<float4>(), w.shadow_queue(), c->radiance.as<float4>(),
+                       work.closest_count, work.shadow_count, p.work_counter, c->knobs.refill_below, c->counters.as<DeviceCounters>());
+}
+
+// One ray per lane: the exhaustive search of tiny scenes, or the BVH2 kernel with the LDS stack the tree's depth asks for.
+template <bool INSTRUMENT> ClosestKernel closest_kernel(const HiprContext* c) {
+    if (c->use_exhaustive()) return k_trace_closest_small<INSTRUMENT>;
+    if (c->scene.stack_size == 16) return k_trace_closest<16, INSTRUMENT>;
+    if (c->scene.stack_size == 32) return k_trace_closest<32, INSTRUMENT>;
+    return k_trace_closest<64, INSTRUMENT>;
+}
+template <bool INSTRUMENT> ShadowKernel shadow_kernel(const HiprContext* c) {
+    if (c->use_exhaustive()) return k_trace_shadow_small<INSTRUMENT>;
+    if (c->scene.stack_size == 16) return k_trace_shadow<16, INSTRUMENT>;
+    if (c->scene.stack_size == 32) return k_trace_shadow<32, INSTRUMENT>;
+    return k_trace_shadow<64, INSTRUMENT>;
+}
+
 #ifndef HIPR_STACK_MID
 #define HIPR_STACK_MID 16
 #endif
-    if (c->scene.wide_stack_entries <= 16) launch_persistent<16, MODE, INSTRUMENT, false>(c, w, in, closest_count, shadow_count, upper_bound, 0);
-    else if (c->scene.wide_stack_entries <= 32) launch_persistent<HIPR_STACK_MID, MODE, INSTRUMENT, true>(c, w, in, closest_count, shadow_count, upper_bound, 1);
-    else launch_persistent<32, MODE, INSTRUMENT, true>(c, w, in, closest_count, shadow_count, upper_bound, 2);
-}
-
-template <bool INSTRUMENT>
-void launch_trace_closest(HiprContext* c, const Wavefront& w, const PathState& in, const uint32_t* count_ptr, uint32_t upper_bound) {
-    float4* hits = w.hits.as<float4>();
-    // Scenes whose whole BVH sits in the L1 / scalar cache (a few dozen nodes) are VALU-issue bound and run fastest with
-    // the plain one-ray-per-lane kernel; everything larger wants the persistent kernel (measured: profiles/).
-    if (c->use_persistent()) { launch_persistent_for_stack<TRACE_CLOSEST, INSTRUMENT>(c, w, in, count_ptr, nullptr, upper_bound); return; }
-    DeviceCounters* dc = c->counters.as<DeviceCounters>();
-    if (c->use_exhaustive()) {
-        hipLaunchKernelGGL((k_trace_closest_small<INSTRUMENT>), dim3(grid_for(upper_bound, 256, 256u * 16u)), dim3(256), 0, w.stream, c->scene.args, in, hits, count_ptr, dc);
-        return;
-    }
-    const uint32_t grid = grid_for(upper_bound, TRACE_BLOCK, 256u * 16u);
-    switch (c->scene.stack_size) {
-    case 16: hipLaunchKernelGGL((k_trace_closest<16, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, in, hits, count_ptr, dc); break;
-    case 32: hipLaunchKernelGGL((k_trace_closest<32, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, in, hits, count_ptr, dc); break;
-    default: hipLaunchKernelGGL((k_trace_closest<64, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, in, hits, count_ptr, dc); break;
-    }
-}
-
-template <bool INSTRUMENT>
-void launch_trace_shadow(HiprContext* c, const Wavefront& w, const uint32_t* count_ptr, uint32_t upper_bound) {
-    if (c->use_persistent()) { launch_persistent_for_stack<TRACE_SHADOW, INSTRUMENT>(c, w, PathState{}, nullptr, count_ptr, upper_bound); return; }
-    DeviceCounters* dc = c->counters.as<DeviceCounters>();
-    float4* rad = c->radiance.as<float4>();
-    ShadowQueue q = w.shadow_queue();
-    if (c->use_exhaustive()) {
-        hipLaunchKernelGGL((k_trace_shadow_small<INSTRUMENT>), dim3(grid_for(upper_bound, 256, 256u * 16u)), dim3(256), 0, w.stream, c->scene.args, q, rad, count_ptr, dc);
-        return;
-    }
-    const uint32_t grid = grid_for(upper_bound, TRACE_BLOCK, 256u * 16u);
-    switch (c->scene.stack_size) {
-    case 16: hipLaunchKernelGGL((k_trace_shadow<16, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, q, rad, count_ptr, dc); break;
-    case 32: hipLaunchKernelGGL((k_trace_shadow<32, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, q, rad, count_ptr, dc); break;
-    default: hipLaunchKernelGGL((k_trace_shadow<64, INSTRUMENT>), dim3(grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, q, rad, count_ptr, dc); break;
-    }
-}
-
-// The closest-hit rays of this bounce and the shadow rays the previous bounce queued, as one persistent launch.
-template <bool INSTRUMENT>
-void launch_trace_fused(HiprContext* c, const Wavefront& w, const PathState& in, const uint32_t* closest_count, const uint32_t* shadow_count, uint32_t upper_bound) {
-    const uint32_t* sorted = nullptr;
+// One trace launch on the wavefront's stream, over its path queue (TRACE_CLOSEST), its shadow queue (TRACE_SHADOW) or both (TRACE_FUSED: the closest-hit rays of a
+// bounce and the shadow rays the previous bounce queued; persistent kernels only). Scenes whose whole BVH sits in the L1 / scalar cache (a few dozen nodes) are
+// VALU-issue bound and run fastest one ray per lane; everything larger wants a persistent kernel (measured: profiles/).
+template <int MODE, bool INSTRUMENT>
+void launch_trace(HiprContext* c, const Wavefront& w, TraceWork work) {
+    if (c->use_wide8()) {       // the LDS stack by the tree's height h: a ray keeps at most one group per level, so at most h - 1 groups wait on the stack
 #if HIPR_RAY_SORT
-    if (!INSTRUMENT && c->coherence_sort && c->use_wide8() && w.sort_order.ptr) {
-        const ShadowQueue q = w.shadow_queue();
-        hipr::RaySortLaunch a = {w.stream, in.o_tmin, in.d_pdf, q.o_tmax, q.d_slot, closest_count, shadow_count, std::min(upper_bound, 2u * std::max(w.n_slots, 64u)), {}, {},
-                                 w.sort_keys[0].as<uint16_t>(), w.sort_keys[1].as<uint16_t>(), w.sort_order.as<uint32_t>(), w.sort_temp.ptr, w.sort_temp.bytes};
-        for (int k = 0; k < 3; ++k) { a.grid_min[k] = c->scene.wide8.grid_min[k]; a.cells_per_unit[k] = 16.0f / (c->scene.wide8.grid_cell[k] * 2097152.0f); }
-        if (hipr::launch_ray_sort(a) == 0) sorted = w.sort_order.as<uint32_t>();
-    }
+        if constexpr (MODE == TRACE_FUSED && !INSTRUMENT) if (c->knobs.coherence_sort && w.sort_order.ptr) {
+            const ShadowQueue q = w.shadow_queue();
+            hipr::RaySortLaunch a = {w.stream, work.in.o_tmin, work.in.d_pdf, q.o_tmax, q.d_slot, work.closest_count, work.shadow_count, std::min(work.upper_bound, 2u * std::max(w.n_slots, 64u)), {}, {},
+                                     w.sort_keys[0].as<uint16_t>(), w.sort_keys[1].as<uint16_t>(), w.sort_order.as<uint32_t>(), w.sort_temp.ptr, w.sort_temp.bytes};
+            for (int k = 0; k < 3; ++k) { a.grid_min[k] = c->scene.wide8.grid_min[k]; a.cells_per_unit[k] = 16.0f / (c->scene.wide8.grid_cell[k] * 2097152.0f); }
+            if (hipr::launch_ray_sort(a) == 0) work.sorted = w.sort_order.as<uint32_t>();
+        }
 #endif
-    launch_persistent_for_stack<TRACE_FUSED, INSTRUMENT>(c, w, in, closest_count, shadow_count, upper_bound, sorted);
+        const uint32_t height = c->scene.wide8_height;
+#if HIPR_WIDE8_LOW_BUCKET
+        if (height <= 9u) launch_wide8<8, MODE, INSTRUMENT>(c, w, work, 3);
+        else
+#endif
+        if (height <= uint32_t(WIDE8_STACK_SHALLOW) + 1u) launch_wide8<WIDE8_STACK_SHALLOW, MODE, INSTRUMENT>(c, w, work, 0);
+        else if (height <= 17u) launch_wide8<16, MODE, INSTRUMENT>(c, w, work, 1);
+        else launch_wide8<32, MODE, INSTRUMENT>(c, w, work, 2);
+    } else if (c->use_wide4()) {
+        // LDS stack entries by the worst case of the 4-wide tree. Trees that need up to 32 entries run with 16 in LDS and the rest in a per-lane scratch
+        // array (traversals rarely get past 16): 4 KB of LDS per wave instead of 8 lets a sixth wave per SIMD stay resident, and the kernel is bound by
+        // the latency of its dependent gathers (atrium, 260 k triangles: 61.0 -> 57.7 ms of trace time per step). Deeper trees (the 10 M triangle
+        // atrium) spill often enough that 32 LDS entries + scratch is the faster split (116.7 vs 119.9 ms).
+        if (c->scene.wide_stack_entries <= 16) launch_wide4<16, MODE, INSTRUMENT, false>(c, w, work, 0);
+        else if (c->scene.wide_stack_entries <= 32) launch_wide4<HIPR_STACK_MID, MODE, INSTRUMENT, true>(c, w, work, 1);
+        else launch_wide4<32, MODE, INSTRUMENT, true>(c, w, work, 2);
+    } else if constexpr (MODE != TRACE_FUSED) {
+        const uint32_t block = c->use_exhaustive() ? 256u : uint32_t(TRACE_BLOCK), grid = grid_for(work.upper_bound, block, 256u * 16u);
+        if constexpr (MODE == TRACE_CLOSEST) hipLaunchKernelGGL(closest_kernel<INSTRUMENT>(c), dim3(grid), dim3(block), 0, w.stream, c->scene.args, work.in, w.hits.as<float4>(), work.closest_count, c->counters.as<DeviceCounters>());
+        else hipLaunchKernelGGL(shadow_kernel<INSTRUMENT>(c), dim3(grid), dim3(block), 0, w.stream, c->scene.args, w.shadow_queue(), c->radiance.as<float4>(), work.shadow_count, c->counters.as<DeviceCounters>());
+    } else (void)fail(HIPR_ERROR_UNSUPPORTED, "a fused trace launch needs a persistent kernel");      // not reached: enqueue_bounce fuses only where use_persistent()
+}
+
+// The one place where the context's instrumentation flag becomes the kernels' template argument.
+template <int MODE>
+void trace_rays(HiprContext* c, const Wavefront& w, const TraceWork& work) {
+    if (c->instrument) launch_trace<MODE, true>(c, w, work);
+    else launch_trace<MODE, false>(c, w, work);
 }
 
 void launch_shade(HiprContext* c, const Wavefront& w, const HiprCameraState& camera, int cur, uint32_t alive, const uint32_t* in_count, uint32_t* out_counts, uint32_t* zero_pair, bool camera_rays) {
@@ -559,9 +577,9 @@ void launch_shade(HiprContext* c, const Wavefront& w, const HiprCameraState& cam
     // A bounce of a few thousand paths runs one wave per SIMD at most: the order they are taken in changes nothing, the listing pass would cost a launch.
     uint32_t* taken_words = w.queue_counts.as<uint32_t>() + COUNT_PAIR_STRIDE * COUNT_PAIRS;
     // Camera rays need no listing: a wave of them is one pixel's samples (or an 8 x 8 tile's pixels) -- they hit a surface, or miss, together (HIPR_SHADE_ORDERED_CAMERA=1 lists them anyway).
-    if (c->shade_ordered && c->use_persistent() && c->entry == HIPR_ENTRY_PATH_TRACING && alive >= c->shade_ordered_from && (!camera_rays || c->shade_ordered_camera)) {
+    if (c->knobs.shade_ordered && c->use_persistent() && c->entry == HIPR_ENTRY_PATH_TRACING && alive >= c->knobs.shade_ordered_from && (!camera_rays || c->knobs.shade_ordered_camera)) {
         unsigned long long* taken = reinterpret_cast<unsigned long long*>(taken_words + COUNT_PAIR_STRIDE * cur);
-        if (c->shade_classes && c->scene.any_coated_triangle)
+        if (c->knobs.shade_classes && c->scene.any_coated_triangle)
             hipLaunchKernelGGL(k_classify_hits<true>, dim3(grid_for(alive, 256u * CLASSIFY_ROUNDS, uint32_t(c->cu_count) * 8u)), dim3(256), 0, w.stream, w.hits.as<float4>(), in_count, w.order.as<uint32_t>(), taken,
                                c->scene.triangle_class.as<unsigned char>(), w.order_coat.as<uint32_t>());
         else
@@ -573,14 +591,14 @@ void launch_shade(HiprContext* c, const Wavefront& w, const HiprCameraState& cam
     // persistent blocks: three per CU stay resident (3 waves per SIMD), each walks the queue with a grid stride, one batch ahead on its inputs
     // measured: the Default / Transmissive kernels gain from a third wave per SIMD (atrium 29.4 -> 25.9 ms of shading per step), the lighter all-Diffuse
     // kernel loses (Cornell 18 390 -> 17 194 Mrays/s)
-    const bool split = c->shade_split && c->entry == HIPR_ENTRY_PATH_TRACING && c->scene.args.light_count != 0 && w.nee_flags.ptr;
-    const uint32_t blocks_per_cu = c->shade_blocks_per_cu > 0 ? uint32_t(c->shade_blocks_per_cu) : (split ? uint32_t(HIPR_SHADE_SPLIT_WAVES) : (c->scene.shading_models == 2 ? 2u : uint32_t(c->shade_unit().waves_per_simd)));
+    const bool split = c->knobs.shade_split && c->entry == HIPR_ENTRY_PATH_TRACING && c->scene.args.light_count != 0 && w.nee_flags.ptr;
+    const uint32_t blocks_per_cu = c->knobs.shade_blocks_per_cu > 0 ? uint32_t(c->knobs.shade_blocks_per_cu) : (split ? uint32_t(HIPR_SHADE_SPLIT_WAVES) : (c->scene.shading_models == 2 ? 2u : uint32_t(c->shade_unit().waves_per_simd)));
     PathState shaded = w.path_state(cur);
     if (camera_rays) shaded.thr_bounces = nullptr;      // k_generate's queue: throughput 1, no bounce yet -- not stored
     ShadeLaunch a = {grid_for(alive, SHADE_BLOCK, uint32_t(c->cu_count) * blocks_per_cu), w.stream, c->scene.args, camera, c->frame, c->entry, shaded, w.hits.as<float4>(), order, w.order_coat.as<uint32_t>(), listed, w.path_state(1 - cur),
                      w.shadow_queue(), c->radiance.as<float4>(), in_count, reinterpret_cast<unsigned long long*>(out_counts), reinterpret_cast<unsigned long long*>(zero_pair),
                      reinterpret_cast<unsigned long long*>(taken_words + COUNT_PAIR_STRIDE * (1 - cur)), split ? w.nee_flags.as<unsigned char>() : nullptr,
-                     c->counters.as<DeviceCounters>(), c->scene.has_textures || !c->lean_shade, c->scene.has_environment || !c->lean_shade};
+                     c->counters.as<DeviceCounters>(), c->scene.has_textures || !c->knobs.lean_shade, c->scene.has_environment || !c->knobs.lean_shade};
     c->shade_unit().shade(c->scene.shading_models, a);
 }
 
@@ -602,7 +620,7 @@ int partition_path_slots(HiprContext* c) {
         Wavefront& w = c->wavefronts[g];
         w.first_slot = uint32_t(g);           // the wavefront's phase in the deal
         w.n_slots = g >= c->wavefront_count ? 0u : uint32_t((groups + uint64_t(c->wavefront_count) - 1u - uint64_t(g)) / uint64_t(c->wavefront_count) * 64u);
-        const bool second_slot = g == 1 && c->wavefront_count == 1 && c->pipeline_passes && c->partitioned_for == 1;    // the other pass slot: a copy of wavefront 0's share
+        const bool second_slot = g == 1 && c->wavefront_count == 1 && c->knobs.pipeline_passes && c->partitioned_for == 1;    // the other pass slot: a copy of wavefront 0's share
         if (second_slot) { w.first_slot = c->wavefronts[0].first_slot; w.n_slots = c->wavefronts[0].n_slots; }
         const size_t bytes = size_t(std::max(w.n_slots, 64u)) * 16;
         if (g >= c->wavefront_count && !second_slot) {   // queues of wavefronts this pass size does not use go back to the allocator
@@ -616,9 +634,9 @@ int partition_path_slots(HiprContext* c) {
         r |= w.hits.resize(bytes);
         r |= w.order.resize(bytes / 4);
         r |= w.order_coat.resize(bytes / 4);
-        if (c->shade_split) r |= w.nee_flags.resize(bytes / 16);
+        if (c->knobs.shade_split) r |= w.nee_flags.resize(bytes / 16);
 #if HIPR_RAY_SORT
-        if (c->coherence_sort) {      // both queues of a fused launch: 2 x n_slots entries
+        if (c->knobs.coherence_sort) {      // both queues of a fused launch: 2 x n_slots entries
             const size_t entries = bytes / 16 * 2;
             r |= w.sort_keys[0].resize(entries * 2); r |= w.sort_keys[1].resize(entries * 2); r |= w.sort_order.resize(entries * 4);
             r |= w.sort_temp.resize(hipr::ray_sort_temp_bytes(uint32_t(entries)));
@@ -626,7 +644,7 @@ int partition_path_slots(HiprContext* c) {
 #endif
         for (int j = 0; j < 3; ++j) r |= w.shadow[j].resize(bytes);
     }
-    const bool two_slots = c->wavefront_count == 1 && c->pipeline_passes && c->partitioned_for == 1;
+    const bool two_slots = c->wavefront_count == 1 && c->knobs.pipeline_passes && c->partitioned_for == 1;
     if (!two_slots) {
         if (c->traced_slot == 1 && c->radiance_other.ptr) std::swap(c->radiance, c->radiance_other);      // the slots are gone: `radiance` is wavefront 0's again
         c->radiance_other.release();
@@ -670,18 +688,12 @@ int enqueue_bounce(HiprContext* c, Wavefront& w, const HiprCameraState& camera, 
     }
 
     c->begin_timed(HIPR_KERNEL_TRACE_CLOSEST, w.stream);
-    if (k > 0 && fused) {
-        if (c->instrument) launch_trace_fused<true>(c, w, w.path_state(parity), in_count, shadow_in, 2u * bound);
-        else launch_trace_fused<false>(c, w, w.path_state(parity), in_count, shadow_in, 2u * bound);
-    } else {
-        if (c->instrument) launch_trace_closest<true>(c, w, w.path_state(parity), in_count, bound);
-        else launch_trace_closest<false>(c, w, w.path_state(parity), in_count, bound);
-    }
+    if (k > 0 && fused) trace_rays<TRACE_FUSED>(c, w, {w.path_state(parity), in_count, shadow_in, 2u * bound});
+    else trace_rays<TRACE_CLOSEST>(c, w, {w.path_state(parity), in_count, nullptr, bound});
     c->end_timed(w.stream);
     if (k > 0 && !fused) {
         c->begin_timed(HIPR_KERNEL_TRACE_SHADOW, w.stream);
-        if (c->instrument) launch_trace_shadow<true>(c, w, shadow_in, bound);
-        else launch_trace_shadow<false>(c, w, shadow_in, bound);
+        trace_rays<TRACE_SHADOW>(c, w, {PathState{}, nullptr, shadow_in, bound});
         c->end_timed(w.stream);
     }
 
@@ -696,7 +708,7 @@ int enqueue_bounce(HiprContext* c, Wavefront& w, const HiprCameraState& camera, 
     HIP_TRY(hipMemcpyAsync(host_sizes, out_count, 8, hipMemcpyDeviceToHost, c->copy_stream));     // {paths that continue, shadow rays}
     HIP_TRY(hipEventRecord(w.counts_copied[parity], c->copy_stream));
 
-    if (c->instrument && c->trace_log) {   // diagnostic (HIPR_TRACE_LOG=1): per-bounce counters and kernel times; serialises the pass
+    if (c->instrument && c->knobs.trace_log) {   // diagnostic (HIPR_TRACE_LOG=1): per-bounce counters and kernel times; serialises the pass
         HIP_TRY(hipStreamSynchronize(w.stream));
         HIP_TRY(hipStreamSynchronize(c->copy_stream));
         DeviceCounters dc;
@@ -726,6 +738,26 @@ int enqueue_bounce(HiprContext* c, Wavefront& w, const HiprCameraState& camera, 
     return HIPR_OK;
 }
 
+// The books of a pass, kept here and nowhere else: bounce k of a wavefront, which `alive` paths entered and which left `sizes` = {paths that continue, shadow rays
+// queued}, is added to `books`, and `alive` becomes what enters bounce k + 1. A wavefront that is still going after RUNAWAY_BOUNCES is an error.
+constexpr uint32_t RUNAWAY_BOUNCES = 8192;
+int book_bounce(HiprCounters& books, uint32_t k, uint32_t& alive, const uint32_t* sizes) {
+    books.closest_rays += alive;
+    books.shadow_rays += sizes[1];
+    books.iterations += 1;
+    alive = sizes[0];
+    return k > RUNAWAY_BOUNCES ? fail(HIPR_ERROR_HIP, "wavefront loop did not terminate") : HIPR_OK;
+}
+
+// One step of a wavefront: queues bounce `queued`, sized by the paths alive now, waits for the sizes bounce `awaited` produced and books that bounce. A pass runs
+// with queued = awaited + 1 -- the next bounce is queued speculatively (at most `alive` paths continue), so the GPU never idles on the read-back; a wavefront whose
+// paths all ended has, with that last speculative bounce, also traced its last shadow rays. A bounce that no path entered traces shadow rays only and is not booked.
+int advance_wavefront(HiprContext* c, Wavefront& w, const HiprCameraState& camera, uint32_t queued, uint32_t awaited, uint32_t& alive, HiprCounters& books) {
+    if (int s = enqueue_bounce(c, w, camera, queued, std::max(alive, 1u))) return s;
+    HIP_TRY(hipEventSynchronize(w.counts_copied[awaited & 1u]));
+    return alive == 0 ? HIPR_OK : book_bounce(books, awaited, alive, w.host_counts + 2 * (awaited & 1u));
+}
+
 // Brings the books of a pass slot up to date: waits for the tail its last pass left on the slot's stream and adds the rays of the tail's bounces to the
 // totals (their queue sizes were read back bounce by bounce into pinned memory). Should paths have outlived the blind bounces (hits that keep being
 // rejected and retraced do not count as bounces), the pass is finished here bounce by bounce.
@@ -736,14 +768,12 @@ int finish_slot(HiprContext* c, int slot_index) {
     HIP_TRY(hipStreamSynchronize(w.stream));
     HIP_TRY(hipStreamSynchronize(c->copy_stream));
     slot.pending = false;
+    const uint32_t first_bounce = slot.next_bounce - slot.blind_bounces - 1u;      // of the tail
     uint32_t in = slot.alive_at_detach, shadows = 0;
     for (uint32_t t = 0; t <= slot.blind_bounces && in > 0; ++t) {
         const uint32_t* sizes = t == 0 ? w.host_counts + 2 * slot.first_parity : slot.tail_counts + 2 * (t - 1);
-        c->total.closest_rays += in;
-        c->total.shadow_rays += sizes[1];
-        c->total.iterations += 1;
-        in = sizes[0];
         shadows = sizes[1];
+        if (int s = book_bounce(c->total, first_bounce + t, in, sizes)) return s;
     }
     if (in == 0 && shadows == 0) return HIPR_OK;
     // the last blind bounce left paths (or only shadow rays): carry on the ordinary way
@@ -752,16 +782,12 @@ int finish_slot(HiprContext* c, int slot_index) {
     const bool swap = slot_index != c->traced_slot;     // launches write the radiance of the pass being finished
     if (swap) std::swap(c->radiance, c->radiance_other);
     int status = HIPR_OK;
-    for (uint32_t k = slot.next_bounce; status == HIPR_OK; ++k) {
-        status = enqueue_bounce(c, w, slot.camera, k, std::max(in, 1u));
-        if (status == HIPR_OK && hipEventSynchronize(w.counts_copied[k & 1u]) != hipSuccess) status = fail(HIPR_ERROR_HIP, "hipEventSynchronize failed while a pass was being finished");
-        if (status != HIPR_OK || in == 0) break;     // in == 0: that bounce only traced the last shadow rays
-        c->total.closest_rays += in;
-        c->total.shadow_rays += w.host_counts[2 * (k & 1u) + 1];
-        c->total.iterations += 1;
-        in = w.host_counts[2 * (k & 1u)];
-        if (k > 8192) status = fail(HIPR_ERROR_HIP, "wavefront loop did not terminate");
-    }
+    uint32_t k = slot.next_bounce, entered;
+    do {      // nothing is queued ahead here; the last turn is the bounce no path entered: it traces the last shadow rays
+        entered = in;
+        status = advance_wavefront(c, w, slot.camera, k, k, in, c->total);
+        ++k;
+    } while (status == HIPR_OK && entered > 0);
     if (swap) std::swap(c->radiance, c->radiance_other);
     c->active_slot = saved_slot;
     if (status == HIPR_OK) HIP_TRY(hipStreamSynchronize(w.stream));
@@ -775,6 +801,83 @@ int finish_all(HiprContext* c) {
         if (int s = finish_slot(c, slot)) return s;
     for (int g = 0; g < MAX_WAVEFRONTS; ++g) if (c->wavefronts[g].stream) HIP_TRY(hipStreamSynchronize(c->wavefronts[g].stream));
     HIP_TRY(hipStreamSynchronize(c->copy_stream));
+    return HIPR_OK;
+}
+
+// finish_all, and the timed launches of the passes that finished with it are added to the kernel times.
+int drain(HiprContext* c) {
+    if (int s = finish_all(c)) return s;
+    c->collect_times();
+    return HIPR_OK;
+}
+
+// The camera rays of a pass: the pixel-samples inside the frame (edge tiles may hang over it).
+uint64_t camera_rays_of(const FrameInfo& f) {
+    if (f.tile_stride == 1) return uint64_t(f.width) * f.height * f.samples_per_pass;
+    uint64_t valid_pixels = 0;
+    for (uint32_t t = f.tile_phase; t < f.tiles_total; t += f.tile_stride) {
+        const uint32_t tx = t % f.tiles_x, ty = t / f.tiles_x;
+        valid_pixels += uint64_t(std::min(8u, f.width - tx * 8)) * std::min(8u, f.height - ty * 8);
+    }
+    return valid_pixels * f.samples_per_pass;
+}
+
+// What the depth entry point divides by: the distance between the near and far plane centres (SimpleRGPs.cu:247-255).
+float depth_range_of(const HiprCameraState& camera) {
+    const float* ip = camera.inverse_projection_matrix;
+    const float near_z = (ip[8] * 0.0f + ip[9] * 0.0f + ip[10] * -1.0f + ip[11]) / (ip[12] * 0.0f + ip[13] * 0.0f + ip[14] * -1.0f + ip[15]);
+    const float far_z = (ip[8] * 0.0f + ip[9] * 0.0f + ip[10] * 1.0f + ip[11]) / (ip[12] * 0.0f + ip[13] * 0.0f + ip[14] * 1.0f + ip[15]);
+    return far_z - near_z;
+}
+
+// Begins a pass on a pass slot (0 for a pass that is not pipelined): what ran on the slot before -- every pass, where this one is not pipelined -- is finished,
+// `radiance` becomes the slot's buffer, the claim counters the slot's previous pass used are zeroed again, and the streams of the other wavefronts get their start.
+int begin_pass(HiprContext* c, int slot, bool pipelined) {
+    c->pipelining_now = pipelined;
+    if (pipelined) {
+        if (int s = finish_slot(c, slot)) return s;
+        c->next_slot = 1 - slot;
+    } else if (int s = finish_all(c)) return s;
+    if (slot != c->traced_slot) std::swap(c->radiance, c->radiance_other);      // `radiance` is the buffer of the pass being traced / last traced
+    c->traced_slot = c->active_slot = slot;
+    HiprContext::PassSlot& ps = c->pass_slots[slot];
+    if (ps.work_index > 0) {   // the slot's stream is ordered behind its previous pass
+        HIP_TRY(hipMemsetAsync(c->work_counters.as<uint32_t>() + size_t(slot) * WORK_COUNTERS, 0, size_t(std::min(ps.work_index, WORK_SETS)) * WORK_SET_WORDS * sizeof(uint32_t),
+                               c->wavefronts[slot].stream));
+        ps.work_index = 0;
+    }
+    if (!pipelined) HIP_TRY(hipEventRecord(c->pass_start, c->stream));
+    return HIPR_OK;
+}
+
+// Starts a wavefront's share of a pass: its counters, the camera rays and bounce 0.
+int start_wavefront(HiprContext* c, Wavefront& w, const HiprCameraState& camera, bool pipelined) {
+    if (!pipelined && &w != c->wavefronts) HIP_TRY(hipStreamWaitEvent(w.stream, c->pass_start, 0));
+    // the counters at the start of a pass: pair 0 = {paths, 0 shadow rays}, all others zero (pinned image, rewritten only after the syncs of the next pass)
+    memset(w.host_counts + 8, 0, COUNT_LINES * COUNT_PAIR_STRIDE * sizeof(uint32_t));
+    w.host_counts[8] = w.n_slots;
+    HIP_TRY(hipMemcpyAsync(w.queue_counts.as<uint32_t>(), w.host_counts + 8, COUNT_LINES * COUNT_PAIR_STRIDE * sizeof(uint32_t), hipMemcpyHostToDevice, w.stream));
+    c->break_chain(w.stream);
+    c->begin_timed(HIPR_KERNEL_GENERATE, w.stream);
+    hipLaunchKernelGGL(k_generate, dim3((w.n_slots + 255) / 256), dim3(256), 0, w.stream, c->frame, camera, w.path_state(0), c->radiance.as<float4>(), w.first_slot, uint32_t(pipelined ? 1 : c->wavefront_count), w.n_slots);
+    c->end_timed(w.stream);
+    return enqueue_bounce(c, w, camera, 0, w.n_slots);
+}
+
+// Hands the rest of a pipelined pass to the GPU once bounce k left a sliver of `alive` paths (bounce k + 1 is queued for them already): every bounce that can
+// follow is queued now, sized by this count and reading its own on the device -- those the camera's bounce limit allows, one more for the last shadow rays, and a
+// reserve for hits that get rejected and retraced without counting as a bounce (finish_slot() takes over if that reserve runs out).
+int detach_tail(HiprContext* c, Wavefront& w, HiprContext::PassSlot& ps, const HiprCameraState& camera, uint32_t k, uint32_t alive) {
+    const uint32_t reserve = 8u;
+    const uint32_t blind = std::min(120u, (camera.max_bounce_count + 2u > k ? camera.max_bounce_count + 2u - k : 1u) + reserve);
+    for (uint32_t t = 0; t < blind; ++t)
+        if (int s = enqueue_bounce(c, w, camera, k + 2 + t, alive, ps.tail_counts + 2 * t)) return s;
+    ps.pending = true;
+    ps.alive_at_detach = alive;
+    ps.first_parity = (k + 1) & 1u;
+    ps.blind_bounces = blind;
+    ps.next_bounce = k + 2 + blind;
+    ps.camera = camera;
     return HIPR_OK;
 }
 
@@ -1308,24 +1411,7 @@ int hipr_create(int device_id, HiprContext** out_context) {
     c->pass_slots[0].work_index = c->pass_slots[1].work_index = WORK_SETS;   // forces the first launch of either slot to zero its ring
     hipDeviceProp_t props;
     if (hipGetDeviceProperties(&props, device_id) == hipSuccess && props.multiProcessorCount > 0) c->cu_count = props.multiProcessorCount;
-    if (const char* v = getenv("HIPR_TRACE_VARIANT")) c->trace_variant = atoi(v);
-    if (const char* v = getenv("HIPR_REFILL_BELOW")) c->refill_below = atoi(v);
-    if (const char* v = getenv("HIPR_SHADE_ORDERED_FROM")) c->shade_ordered_from = uint32_t(atoll(v));
-    if (const char* v = getenv("HIPR_SHADE_BLOCKS_PER_CU")) c->shade_blocks_per_cu = std::max(1, atoi(v));
-    if (const char* v = getenv("HIPR_BLOCKS_PER_CU")) c->blocks_per_cu_override = atoi(v);
-    if (const char* v = getenv("HIPR_WAVEFRONTS")) c->wavefront_limit = std::max(0, std::min(MAX_WAVEFRONTS, atoi(v)));
-    if (const char* v = getenv("HIPR_TRACE_LOG")) c->trace_log = atoi(v) != 0;
-    if (const char* v = getenv("HIPR_SHADE_CLASSES")) c->shade_classes = atoi(v) != 0;
-    if (const char* v = getenv("HIPR_COHERENCE_SORT")) c->coherence_sort = HIPR_RAY_SORT && atoi(v) != 0;      // only in a build with the experiment linked in (tools/experiments/ray_sort.hip)
-    if (const char* v = getenv("HIPR_LEAN_TRACE")) c->lean_trace = atoi(v) != 0;
-    if (const char* v = getenv("HIPR_LEAN_SHADE")) c->lean_shade = atoi(v) != 0;
-    if (const char* v = getenv("HIPR_SHADE_ORDERED")) c->shade_ordered = atoi(v) != 0;
-    if (const char* v = getenv("HIPR_SHADE_ORDERED_CAMERA")) c->shade_ordered_camera = atoi(v) != 0;
-    if (const char* v = getenv("HIPR_SHADE_SPLIT")) c->shade_split = atoi(v) != 0;
-    if (const char* v = getenv("HIPR_ARITHMETIC")) c->arithmetic = (v[0] == 'e' || v[0] == 'E' || v[0] == '1') ? HIPR_ARITHMETIC_EXACT : HIPR_ARITHMETIC_FAST;
-    if (const char* v = getenv("HIPR_BACKFACE_CULLING")) c->cull_backfaces = atoi(v) != 0;
-    if (const char* v = getenv("HIPR_PIPELINE_PASSES")) c->pipeline_passes = atoi(v) != 0;
-    if (const char* v = getenv("HIPR_PIPELINE_SPARE_BLOCKS")) c->pipeline_spare_blocks = std::max(0, atoi(v));
+    c->knobs = knobs_from_environment();
     HIP_TRY(hipMemsetAsync(c->counters.ptr, 0, sizeof(DeviceCounters), c->stream));
 
     float offsets[256 * 4];
@@ -1362,8 +1448,7 @@ int hipr_destroy(HiprContext* c) {
 
 int hipr_set_stream(HiprContext* c, void* hip_stream) {
     if (int s = check_context(c)) return s;
-    if (int finish_status = finish_all(c)) return finish_status;
-    c->collect_times();
+    if (int s = drain(c)) return s;
     c->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->own_stream;
     c->wavefronts[0].stream = c->stream;
     return HIPR_OK;
@@ -1412,7 +1497,7 @@ int hipr_upload_scene(HiprContext* c, const HiprSceneDesc* s) {
             return fail(HIPR_ERROR_UNSUPPORTED, "only environments with 4 channels are supported (OptiXRenderer/Renderer.cpp:1141-1158)");
     }
     if (int finish_status = finish_all(c)) return finish_status;
-    return c->scene.upload(s, checked, c->trace_variant, c->cull_backfaces, c->stream);
+    return c->scene.upload(s, checked, c->knobs.trace_variant, c->knobs.cull_backfaces, c->stream);
 }
 
 int hipr_update_scene_geometry(HiprContext* c, const HiprSceneDesc* s) {
@@ -1434,7 +1519,7 @@ int hipr_update_scene_geometry(HiprContext* c, const HiprSceneDesc* s) {
         return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: the 8-wide tree's topology changed");
     if (int st = r.lights_keep_their_types("hipr_update_scene_geometry", s->lights, s->light_count)) return st;
     if (int finish_status = finish_all(c)) return finish_status;      // pipelined passes included: no pending pass may go on over the new geometry
-    return c->scene.update_geometry(s, checked, c->trace_variant, c->cull_backfaces, c->stream);
+    return c->scene.update_geometry(s, checked, c->knobs.trace_variant, c->knobs.cull_backfaces, c->stream);
 }
 
 int hipr_refit_scene_transforms(HiprContext* c, const HiprInstanceTransform* moved, uint32_t moved_count, const HiprLight* lights, uint32_t light_count, HiprRefitResult* out) {
@@ -1534,8 +1619,7 @@ int hipr_set_entry_point(HiprContext* c, int entry) {
 int hipr_use_scratch_accumulation(HiprContext* c, int enable) {
     if (int s = check_context(c)) return s;
     if (!c->frame_ready) return fail(HIPR_ERROR_NOT_READY, "no frame set");
-    if (int finish_status = finish_all(c)) return finish_status;
-    c->collect_times();
+    if (int s = drain(c)) return s;
     if (enable) {
         const size_t bytes = size_t(c->frame.owned_tiles) * 64 * sizeof(double4);
         const bool keep = enable == 2 && c->scratch_accumulation.ptr && c->scratch_accumulation.bytes >= bytes;   // a running mean kept across calls
@@ -1559,8 +1643,7 @@ int hipr_set_samples_per_pass(HiprContext* c, uint32_t samples_per_pass) {
     const uint64_t slots = uint64_t(c->frame.owned_tiles) * 64u * samples_per_pass;
     if (samples_per_pass == 0 || slots > 0x7FFFFFFFull) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_set_samples_per_pass: %llu path slots per pass", (unsigned long long)slots);
     if (samples_per_pass == c->frame.samples_per_pass) return HIPR_OK;
-    if (int finish_status = finish_all(c)) return finish_status;      // the queues may move
-    c->collect_times();
+    if (int s = drain(c)) return s;      // the queues may move
     c->frame.samples_per_pass = samples_per_pass;
     set_frame_divisors(c->frame);
     if (partition_path_slots(c)) return HIPR_ERROR_OUT_OF_MEMORY;
@@ -1577,129 +1660,53 @@ int hipr_trace_pass(HiprContext* c, const HiprCameraState* camera) {
     if (!camera) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null camera");
     if (!c->tables_ready || !c->scene.ready || !c->frame_ready) return fail(HIPR_ERROR_NOT_READY, "tables, scene and frame must be set before rendering");
     if (c->partitioned_for != c->wavefronts_wanted()) {      // the scene uploaded since hipr_set_frame wants another split of the path slots
-        if (int s = finish_all(c)) return s;
-        for (int g = 0; g < MAX_WAVEFRONTS; ++g) if (c->wavefronts[g].stream) HIP_TRY(hipStreamSynchronize(c->wavefronts[g].stream));
-        c->collect_times();
+        if (int s = drain(c)) return s;
         if (partition_path_slots(c)) return HIPR_ERROR_OUT_OF_MEMORY;
     }
-
-    const FrameInfo& f = c->frame;
-    const uint32_t n = c->n_slots;
-    HiprCounters pass = {};
-
-    // valid pixel-samples (edge tiles may hang over the frame)
-    uint64_t valid_pixels = 0;
-    if (f.tile_stride == 1) valid_pixels = uint64_t(f.width) * f.height;
-    else {
-        for (uint32_t t = f.tile_phase; t < f.tiles_total; t += f.tile_stride) {
-            uint32_t tx = t % f.tiles_x, ty = t / f.tiles_x;
-            uint32_t w = std::min(8u, f.width - tx * 8), h = std::min(8u, f.height - ty * 8);
-            valid_pixels += uint64_t(w) * h;
-        }
-    }
-    pass.camera_rays = valid_pixels * f.samples_per_pass;
-
     // Pipelined passes (HiprContext::PassSlot): this pass takes the slot the pass before the last one used, whose tail has long drained.
-    const bool pipelined = c->pipeline_passes && c->use_persistent() && c->wavefront_count == 1 && c->radiance_other.ptr && !c->instrument;
+    const bool pipelined = c->knobs.pipeline_passes && c->use_persistent() && c->wavefront_count == 1 && c->radiance_other.ptr && !c->instrument;
     const int slot = pipelined ? c->next_slot : 0;
-    c->pipelining_now = pipelined;
-    if (pipelined) {
-        if (int s = finish_slot(c, slot)) return s;
-        c->next_slot = 1 - slot;
-    } else if (int s = finish_all(c)) return s;
-    if (slot != c->traced_slot) std::swap(c->radiance, c->radiance_other);      // `radiance` is the buffer of the pass being traced / last traced
-    c->traced_slot = slot;
-    c->active_slot = slot;
+    if (int s = begin_pass(c, slot, pipelined)) return s;
     const int first_wavefront = pipelined ? slot : 0, end_wavefront = pipelined ? slot + 1 : c->wavefront_count;
-    hipStream_t lead = c->wavefronts[first_wavefront].stream;
 
-    HiprContext::PassSlot& ps = c->pass_slots[slot];
-    if (ps.work_index > 0) {   // claim counters used by the slot's previous pass (the slot's stream is ordered behind it)
-        HIP_TRY(hipMemsetAsync(c->work_counters.as<uint32_t>() + size_t(slot) * WORK_COUNTERS, 0, size_t(std::min(ps.work_index, WORK_SETS)) * WORK_SET_WORDS * sizeof(uint32_t), lead));
-        ps.work_index = 0;
-    }
-    if (!pipelined) HIP_TRY(hipEventRecord(c->pass_start, c->stream));
-
-    // Start every wavefront: camera rays + bounce 0.
-    uint32_t alive[MAX_WAVEFRONTS] = {}, bounce[MAX_WAVEFRONTS] = {};
-    bool running[MAX_WAVEFRONTS] = {};
+    HiprCounters pass = {};
+    pass.camera_rays = camera_rays_of(c->frame);
+    pass.closest_rays -= c->n_slots - uint32_t(std::min<uint64_t>(c->n_slots, pass.camera_rays));   // dead lanes of partial tiles are queued but never traced
+    uint32_t alive[MAX_WAVEFRONTS] = {}, bounce[MAX_WAVEFRONTS] = {};      // alive: the paths of the wavefront's current bounce; 0: it has ended
     for (int g = first_wavefront; g < end_wavefront; ++g) {
-        Wavefront& w = c->wavefronts[g];
-        if (!pipelined && g > 0) HIP_TRY(hipStreamWaitEvent(w.stream, c->pass_start, 0));
-        // the counters at the start of a pass: pair 0 = {paths, 0 shadow rays}, all others zero (pinned image, rewritten only after the syncs of the next pass)
-        memset(w.host_counts + 8, 0, COUNT_LINES * COUNT_PAIR_STRIDE * sizeof(uint32_t));
-        w.host_counts[8] = w.n_slots;
-        HIP_TRY(hipMemcpyAsync(w.queue_counts.as<uint32_t>(), w.host_counts + 8, COUNT_LINES * COUNT_PAIR_STRIDE * sizeof(uint32_t), hipMemcpyHostToDevice, w.stream));
-        c->break_chain(w.stream);
-        c->begin_timed(HIPR_KERNEL_GENERATE, w.stream);
-        hipLaunchKernelGGL(k_generate, dim3((w.n_slots + 255) / 256), dim3(256), 0, w.stream, f, *camera, w.path_state(0), c->radiance.as<float4>(), w.first_slot, uint32_t(pipelined ? 1 : c->wavefront_count), w.n_slots);
-        c->end_timed(w.stream);
-        alive[g] = w.n_slots;
-        running[g] = true;
-        if (int s = enqueue_bounce(c, w, *camera, 0, alive[g])) return s;
+        if (int s = start_wavefront(c, c->wavefronts[g], *camera, pipelined)) return s;
+        alive[g] = c->wavefronts[g].n_slots;
     }
-    // Round robin over the wavefronts: queue the next bounce speculatively (at most `alive` paths continue), then read the sizes
-    // the current one produced -- the GPU never idles on the read-back. A wavefront whose paths all ended has, with that last speculative
-    // bounce, also traced its last shadow rays.
-    pass.closest_rays -= n - uint32_t(std::min<uint64_t>(n, pass.camera_rays));   // dead lanes of partial tiles are queued but never traced
+    // Round robin over the wavefronts, one bounce of each at a time, until all have ended or the pass's tail is detached.
     bool detached = false;
     for (int remaining = end_wavefront - first_wavefront; remaining > 0 && !detached;) {
-        for (int g = first_wavefront; g < end_wavefront; ++g) {
-            if (!running[g]) continue;
+        for (int g = first_wavefront; g < end_wavefront && !detached; ++g) {
+            if (alive[g] == 0) continue;
             Wavefront& w = c->wavefronts[g];
-            const uint32_t k = bounce[g];
-            if (int s = enqueue_bounce(c, w, *camera, k + 1, alive[g])) return s;
-            HIP_TRY(hipEventSynchronize(w.counts_copied[k & 1u]));
-            pass.closest_rays += alive[g];
-            pass.shadow_rays += w.host_counts[2 * (k & 1u) + 1];
-            pass.iterations += 1;
-            alive[g] = w.host_counts[2 * (k & 1u)];
-            bounce[g] = k + 1;
+            const uint32_t k = bounce[g]++;
+            if (int s = advance_wavefront(c, w, *camera, k + 1, k, alive[g], pass)) return s;
             if (alive[g] == 0) {
-                running[g] = false;
                 --remaining;
                 if (!pipelined && g > 0) {
                     HIP_TRY(hipEventRecord(w.finished, w.stream));
                     HIP_TRY(hipStreamWaitEvent(c->stream, w.finished, 0));
                 }
-            } else if (pipelined && k >= 1 && uint64_t(alive[g]) * 64u < w.n_slots) {
-                // A sliver of the paths is left (bounce k + 1 is queued for them already). Every bounce that can follow is queued now, sized by this
-                // count and reading its own on the device: those the camera's bounce limit allows, one more for the last shadow rays, and a reserve
-                // for hits that get rejected and retraced without counting as a bounce (finish_slot() takes over if that reserve runs out).
-                const uint32_t reserve = 8u;
-                const uint32_t blind = std::min(120u, (camera->max_bounce_count + 2u > k ? camera->max_bounce_count + 2u - k : 1u) + reserve);
-                for (uint32_t t = 0; t < blind; ++t)
-                    if (int s = enqueue_bounce(c, w, *camera, k + 2 + t, alive[g], ps.tail_counts + 2 * t)) return s;
-                ps.pending = true;
-                ps.alive_at_detach = alive[g];
-                ps.first_parity = (k + 1) & 1u;
-                ps.blind_bounces = blind;
-                ps.next_bounce = k + 2 + blind;
-                ps.camera = *camera;
+            } else if (pipelined && k >= 1 && uint64_t(alive[g]) * 64u < w.n_slots) {      // a sliver of the paths is left
+                if (int s = detach_tail(c, w, c->pass_slots[slot], *camera, k, alive[g])) return s;
                 detached = true;
-                break;
             }
-            if (k > 4096) return fail(HIPR_ERROR_HIP, "wavefront loop did not terminate");
         }
     }
 
-    c->pass_depth_normalizer = 0.0f;
-    if (c->entry == HIPR_ENTRY_DEPTH) {   // max depth = distance between the near and far plane centres (SimpleRGPs.cu:247-255)
-        const float* ip = camera->inverse_projection_matrix;
-        const float near_z = (ip[8] * 0.0f + ip[9] * 0.0f + ip[10] * -1.0f + ip[11]) / (ip[12] * 0.0f + ip[13] * 0.0f + ip[14] * -1.0f + ip[15]);
-        const float far_z = (ip[8] * 0.0f + ip[9] * 0.0f + ip[10] * 1.0f + ip[11]) / (ip[12] * 0.0f + ip[13] * 0.0f + ip[14] * 1.0f + ip[15]);
-        c->pass_depth_normalizer = far_z - near_z;
-    }
+    c->pass_depth_normalizer = c->entry == HIPR_ENTRY_DEPTH ? depth_range_of(*camera) : 0.0f;
     HIP_TRY(hipGetLastError());
-    c->traced_samples = f.samples_per_pass;
+    c->traced_samples = c->frame.samples_per_pass;
     c->total.camera_rays += pass.camera_rays;
     c->total.closest_rays += pass.closest_rays;
     c->total.shadow_rays += pass.shadow_rays;
     c->total.iterations += pass.iterations;
-    if (c->instrument || c->timed.size() > 2048) {
-        if (int s = finish_all(c)) return s;
-        c->collect_times();
-    }
+    if (c->instrument || c->timed.size() > 2048)
+        if (int s = drain(c)) return s;
     return HIPR_OK;
 }
 
@@ -1724,24 +1731,21 @@ int hipr_accumulate_samples(HiprContext* c, uint32_t first_sample, uint32_t samp
     HIP_TRY(hipEventRecord(c->accumulated, stream));
     c->accumulated_valid = true;
     if (synchronize || c->instrument || c->timed.size() > 2048) {
-        if (int s = finish_all(c)) return s;
-        c->collect_times();
+        if (int s = drain(c)) return s;
     }
     return HIPR_OK;
 }
 
 int hipr_synchronize(HiprContext* c) {
     if (int s = check_context(c)) return s;
-    if (int finish_status = finish_all(c)) return finish_status;
-    c->collect_times();
+    if (int s = drain(c)) return s;
     return HIPR_OK;
 }
 
 int hipr_get_counters(HiprContext* c, HiprCounters* out) {
     if (int s = check_context(c)) return s;
     if (!out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null counters");
-    if (int finish_status = finish_all(c)) return finish_status;
-    c->collect_times();
+    if (int s = drain(c)) return s;
     DeviceCounters dc;
     HIP_TRY(hipMemcpy(&dc, c->counters.ptr, sizeof(dc), hipMemcpyDeviceToHost));
     *out = c->total;
@@ -1755,8 +1759,7 @@ int hipr_get_counters(HiprContext* c, HiprCounters* out) {
 
 int hipr_reset_counters(HiprContext* c) {
     if (int s = check_context(c)) return s;
-    if (int finish_status = finish_all(c)) return finish_status;
-    c->collect_times();
+    if (int s = drain(c)) return s;
     HIP_TRY(hipMemset(c->counters.ptr, 0, sizeof(DeviceCounters)));
     c->total = {};
     c->trace_log_previous = {};
@@ -1766,7 +1769,7 @@ int hipr_reset_counters(HiprContext* c) {
 int hipr_set_wavefront_count(HiprContext* c, int count) {
     if (!c) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null context");
     if (count < 0 || count > MAX_WAVEFRONTS) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_set_wavefront_count: %d is outside [0, %d]", count, MAX_WAVEFRONTS);
-    c->wavefront_limit = count;   // 0: by scene; takes effect with the next pass
+    c->knobs.wavefront_limit = count;   // 0: by scene; takes effect with the next pass
     return HIPR_OK;
 }
 
@@ -1789,15 +1792,15 @@ int hipr_set_trace_variant(HiprContext* c, int variant) {
     if (variant < -1 || variant > HIPR_TRACE_WIDE8_PERSISTENT) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_set_trace_variant: unknown variant %d", variant);
     if (c->scene.tree_stale && (variant == HIPR_TRACE_BVH2 || variant == HIPR_TRACE_WIDE_PERSISTENT))
         return fail(HIPR_ERROR_UNSUPPORTED, "hipr_set_trace_variant: the BVH2 and 4-wide arrays are stale after hipr_refit_scene_transforms; call hipr_update_scene_geometry or hipr_upload_scene first");
-    c->trace_variant = variant;     // the exhaustive search's items are built at upload: upload the scene after this call
+    c->knobs.trace_variant = variant;     // the exhaustive search's items are built at upload: upload the scene after this call
     return HIPR_OK;
 }
 
 int hipr_set_backface_culling(HiprContext* c, int enable) {
     if (int s = check_context(c)) return s;
     if (int s = finish_all(c)) return s;
-    c->cull_backfaces = enable != 0;
-    c->scene.wide8.cull_backfaces = c->cull_backfaces ? 1u : 0u;
+    c->knobs.cull_backfaces = enable != 0;
+    c->scene.wide8.cull_backfaces = c->knobs.cull_backfaces ? 1u : 0u;
     return HIPR_OK;
 }
 
@@ -1805,19 +1808,19 @@ int hipr_set_arithmetic(HiprContext* c, int arithmetic) {
     if (int s = check_context(c)) return s;
     if (arithmetic != HIPR_ARITHMETIC_FAST && arithmetic != HIPR_ARITHMETIC_EXACT) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_set_arithmetic: unknown mode %d", arithmetic);
     if (int s = finish_all(c)) return s;
-    c->arithmetic = arithmetic;
+    c->knobs.arithmetic = arithmetic;
     return HIPR_OK;
 }
 
 int hipr_get_arithmetic(HiprContext* c) {
     if (int s = check_context(c)) return s;      // statuses are negative
-    return c->arithmetic;
+    return c->knobs.arithmetic;
 }
 
 int hipr_set_pass_pipelining(HiprContext* c, int enable) {
     if (int s = check_context(c)) return s;
     if (int s = finish_all(c)) return s;
-    c->pipeline_passes = enable != 0;
+    c->knobs.pipeline_passes = enable != 0;
     if (c->frame_ready && partition_path_slots(c)) return HIPR_ERROR_OUT_OF_MEMORY;      // the second slot's queues come and go with the setting
     return HIPR_OK;
 }
@@ -1830,8 +1833,7 @@ int hipr_set_instrumentation(HiprContext* c, int count_traversal_steps) {
 
 int hipr_reset_timers(HiprContext* c) {
     if (int s = check_context(c)) return s;
-    if (int finish_status = finish_all(c)) return finish_status;
-    c->collect_times();
+    if (int s = drain(c)) return s;
     c->times = {};
     return HIPR_OK;
 }
@@ -1839,8 +1841,7 @@ int hipr_reset_timers(HiprContext* c) {
 int hipr_get_kernel_times(HiprContext* c, HiprKernelTimes* out) {
     if (int s = check_context(c)) return s;
     if (!out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null output");
-    if (int finish_status = finish_all(c)) return finish_status;
-    c->collect_times();
+    if (int s = drain(c)) return s;
     *out = c->times;
     return HIPR_OK;
 }
@@ -1852,8 +1853,7 @@ int hipr_read_accumulation(HiprContext* c, double* out_rgba, uint64_t capacity_p
     const uint64_t owned = uint64_t(f.owned_tiles) * 64;
     const uint64_t needed = f.tile_stride == 1 ? uint64_t(f.width) * f.height : owned;
     if (!out_rgba || capacity_pixels < needed) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_read_accumulation: need room for %llu pixels", (unsigned long long)needed);
-    if (int finish_status = finish_all(c)) return finish_status;
-    c->collect_times();
+    if (int s = drain(c)) return s;
     if (f.tile_stride != 1) {
         HIP_TRY(hipMemcpy(out_rgba, c->active_accumulation().ptr, owned * 32, hipMemcpyDeviceToHost));
         return HIPR_OK;
@@ -1882,7 +1882,6 @@ int hipr_scatter_tiles(HiprContext* c, const void* compact, uint64_t rank_stride
 int hipr_device_malloc(HiprContext* c, uint64_t bytes, void** out_device_pointer) {
     if (int s = check_context(c)) return s;
     if (!out_device_pointer || bytes == 0) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_device_malloc: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMalloc(out_device_pointer, bytes));
     return HIPR_OK;
 }
@@ -2079,14 +2078,13 @@ int hipr_debug_sample_offsets(HiprContext* c, float* out_256x4) {
     return HIPR_OK;
 }
 
-static int debug_prepare_rays(HiprContext* c, const float* rays, uint32_t n, std::vector<float>& o, std::vector<float>& d) {
+static void debug_prepare_rays(const float* rays, uint32_t n, std::vector<float>& o, std::vector<float>& d) {
     o.resize(size_t(n) * 4);
     d.resize(size_t(n) * 4);
     for (uint32_t i = 0; i < n; ++i) {
         std::memcpy(&o[4 * i], rays + 8 * size_t(i), 16);
         std::memcpy(&d[4 * i], rays + 8 * size_t(i) + 4, 16);
     }
-    return HIPR_OK;
 }
 
 int hipr_debug_trace_closest(HiprContext* c, const float* rays, const uint32_t* skip, uint32_t n, float* out_hits) {
@@ -2094,8 +2092,9 @@ int hipr_debug_trace_closest(HiprContext* c, const float* rays, const uint32_t* 
     if (!c->scene.ready) return fail(HIPR_ERROR_NOT_READY, "no scene uploaded");
     if (!rays || !out_hits) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return HIPR_OK;
+    if (int s = drain(c)) return s;      // the tail of a pipelined pass may still be running: nothing of the context is touched before it has ended
     std::vector<float> o, d;
-    debug_prepare_rays(c, rays, n, o, d);
+    debug_prepare_rays(rays, n, o, d);
     std::vector<uint32_t> meta(size_t(n) * 2);
     for (uint32_t i = 0; i < n; ++i) { meta[2 * i] = i; meta[2 * i + 1] = skip ? skip[i] : HIPR_NO_TRIANGLE; }
     DeviceBuffer bo, bd, bm, bh, bc;
@@ -2107,8 +2106,7 @@ int hipr_debug_trace_closest(HiprContext* c, const float* rays, const uint32_t* 
     Wavefront w;
     w.stream = c->stream;
     w.hits = std::move(bh);
-    if (c->instrument) launch_trace_closest<true>(c, w, in, bc.as<uint32_t>(), n);
-    else launch_trace_closest<false>(c, w, in, bc.as<uint32_t>(), n);
+    trace_rays<TRACE_CLOSEST>(c, w, {in, bc.as<uint32_t>(), nullptr, n});
     if (int finish_status = finish_all(c)) return finish_status;
     HIP_TRY(hipMemcpy(out_hits, w.hits.ptr, size_t(n) * 16, hipMemcpyDeviceToHost));
     c->total = {};
@@ -2121,6 +2119,7 @@ int hipr_debug_trace_shadow(HiprContext* c, const float* rays, uint32_t n, float
     if (!c->scene.ready) return fail(HIPR_ERROR_NOT_READY, "no scene uploaded");
     if (!rays || !out_transmittance) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return HIPR_OK;
+    if (int s = drain(c)) return s;      // as in hipr_debug_trace_closest: the swap of `radiance` below must not meet a pass that is still running
     std::vector<float> o(size_t(n) * 4), d(size_t(n) * 4), rad(size_t(n) * 4, 0.0f), ones(size_t(n) * 4, 1.0f);
     for (uint32_t i = 0; i < n; ++i) {
         std::memcpy(&o[4 * i], rays + 8 * size_t(i), 12);
@@ -2137,8 +2136,7 @@ int hipr_debug_trace_shadow(HiprContext* c, const float* rays, uint32_t n, float
     w.stream = c->stream;
     w.shadow[0] = std::move(bo); w.shadow[1] = std::move(bd); w.shadow[2] = std::move(br);
     std::swap(c->radiance, bacc);      // the launch writes the context's radiance buffer: this call's, for its duration
-    if (c->instrument) launch_trace_shadow<true>(c, w, bc.as<uint32_t>(), n);
-    else launch_trace_shadow<false>(c, w, bc.as<uint32_t>(), n);
+    trace_rays<TRACE_SHADOW>(c, w, {PathState{}, nullptr, bc.as<uint32_t>(), n});
     std::swap(c->radiance, bacc);
     if (int finish_status = finish_all(c)) return finish_status;
     std::vector<float> result(size_t(n) * 4);
