@@ -125,8 +125,37 @@ class HiprRefitResult(C.Structure):
     _fields_ = [("needs_rebuild", c_i32), ("child_half_area", C.c_double), ("uploaded_half_area", C.c_double), ("grid_min", c_f * 3), ("grid_cell", c_f * 3)]
 
 
+class HiprMaterialUpdate(C.Structure):
+    _fields_ = [("material_index", c_u32), ("material", HiprMaterial)]
+
+
+class HiprInstanceMaterial(C.Structure):
+    _fields_ = [("instance_index", c_u32), ("material_index", c_i32)]
+
+
+def material_updates(materials):
+    """(material index, HiprMaterial) pairs as the HiprMaterialUpdate array of hipr_update_scene_materials (one spare element: never a null array)."""
+    materials = list(materials)
+    array = (HiprMaterialUpdate * max(len(materials), 1))()
+    for k, (index, material) in enumerate(materials):
+        array[k].material_index = int(index)
+        C.memmove(C.byref(array[k].material), C.byref(material), C.sizeof(HiprMaterial))
+    return array
+
+
+def instance_materials(assignments):
+    """(instance index, material index) pairs as the HiprInstanceMaterial array of hipr_update_scene_materials."""
+    assignments = list(assignments)
+    array = (HiprInstanceMaterial * max(len(assignments), 1))()
+    for k, (instance, material) in enumerate(assignments):
+        array[k].instance_index = int(instance)
+        array[k].material_index = int(material)
+    return array
+
+
 HIPR_ERROR_INVALID_ARGUMENT, HIPR_ERROR_NOT_READY, HIPR_ERROR_UNSUPPORTED = -1, -5, -6
-SCENE_BUFFER_TRIANGLES, SCENE_BUFFER_WIDE8_SLOTS = 0, 1
+SCENE_BUFFER_TRIANGLES, SCENE_BUFFER_WIDE8_SLOTS, SCENE_BUFFER_TRACE_TRIANGLES, SCENE_BUFFER_SHADE_TRIANGLES, SCENE_BUFFER_TRIANGLE_CLASS, SCENE_BUFFER_MATERIALS, SCENE_BUFFER_INSTANCES = 0, 1, 2, 3, 4, 5, 6
+SCENE_BUFFERS = (SCENE_BUFFER_TRIANGLES, SCENE_BUFFER_WIDE8_SLOTS, SCENE_BUFFER_TRACE_TRIANGLES, SCENE_BUFFER_SHADE_TRIANGLES, SCENE_BUFFER_TRIANGLE_CLASS, SCENE_BUFFER_MATERIALS, SCENE_BUFFER_INSTANCES)
 TRACE_BVH2, TRACE_WIDE_PERSISTENT, TRACE_EXHAUSTIVE, TRACE_WIDE8_PERSISTENT = 0, 1, 2, 3
 SHADING_DEFAULT, SHADING_DIFFUSE, SHADING_TRANSMISSIVE = 0, 1, 2
 MATERIAL_THIN_WALLED, MATERIAL_CUTOUT = 1, 2
@@ -145,7 +174,7 @@ assert C.sizeof(HiprTexture) == 24 and C.sizeof(HiprCameraState) == 180 and C.si
 # Every symbol include/hiprenderer_c.h declares; tests check the library exports all of them.
 C_ABI_SYMBOLS = (
     "hipr_create", "hipr_destroy", "hipr_last_error", "hipr_device_count", "hipr_set_stream",
-    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
+    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
     "hipr_set_frame", "hipr_owned_pixel_count",
     "hipr_render_pass", "hipr_set_samples_per_pass", "hipr_trace_pass", "hipr_accumulate_samples", "hipr_read_accumulation", "hipr_scatter_tiles", "hipr_synchronize", "hipr_get_counters",
     "hipr_device_malloc", "hipr_device_free", "hipr_device_memset", "hipr_copy_to_host", "hipr_present_flipped",
@@ -192,6 +221,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.hipr_group_update_scene_geometry.argtypes = [vp, C.POINTER(HiprSceneDesc)]
     lib.hipr_refit_scene_transforms.argtypes = [vp, C.POINTER(HiprInstanceTransform), c_u32, C.POINTER(HiprLight), c_u32, C.POINTER(HiprRefitResult)]
     lib.hipr_group_refit_scene_transforms.argtypes = [vp, C.POINTER(HiprInstanceTransform), c_u32, C.POINTER(HiprLight), c_u32, C.POINTER(HiprRefitResult)]
+    lib.hipr_update_scene_materials.argtypes = [vp, C.POINTER(HiprMaterialUpdate), c_u32, C.POINTER(HiprInstanceMaterial), c_u32]
+    lib.hipr_group_update_scene_materials.argtypes = [vp, C.POINTER(HiprMaterialUpdate), c_u32, C.POINTER(HiprInstanceMaterial), c_u32]
     lib.hipr_debug_read_scene_buffer.argtypes = [vp, C.c_int, vp, c_u64]
     lib.hipr_set_scene_state.argtypes = [vp, C.POINTER(HiprSceneState)]
     lib.hipr_set_entry_point.argtypes = [vp, C.c_int]

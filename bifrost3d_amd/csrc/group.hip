@@ -37,6 +37,8 @@
 #include <thread>
 #include <vector>
 
+extern "C" int hipr_internal_check_material_update(HiprContext* context, const HiprMaterialUpdate* materials, uint32_t material_count, const HiprInstanceMaterial* assignments,
+                                                   uint32_t assignment_count);   // hiprenderer.hip: the refusals of hipr_update_scene_materials on their own
 extern "C" void hipr_internal_set_last_error(const char* message);   // hiprenderer.hip: hipr_last_error() is per thread; a worker's message is handed to the caller's
 
 namespace {
@@ -337,6 +339,14 @@ int hipr_group_refit_scene_transforms(HiprGroup* g, const HiprInstanceTransform*
             return HIPR_ERROR_HIP;
         }
     return HIPR_OK;
+}
+
+int hipr_group_update_scene_materials(HiprGroup* g, const HiprMaterialUpdate* materials, uint32_t material_count, const HiprInstanceMaterial* assignments, uint32_t assignment_count) {
+    if (!g) return HIPR_ERROR_INVALID_ARGUMENT;
+    // Every member checks before any member writes: an edit one member refuses leaves all of them as they were.
+    for (Member& m : g->members)
+        if (int s = hipr_internal_check_material_update(m.context, materials, material_count, assignments, assignment_count)) return s;
+    return for_each_member(g, [&](Member& m, uint32_t) { return hipr_update_scene_materials(m.context, materials, material_count, assignments, assignment_count); });
 }
 
 int hipr_group_set_scene_state(HiprGroup* g, const HiprSceneState* state) {

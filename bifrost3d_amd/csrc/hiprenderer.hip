@@ -14,6 +14,7 @@
 #endif
 #include "wide8_kernels.h"
 #include "wide8_refit.h"
+#include "material_update.h"
 #include "launch.h"
 
 #include <hip/hip_runtime.h>
@@ -131,8 +132,8 @@ struct Preflight {
 };
 
 // The scene the device holds: the uploaded pools, what is derived from them, the argument blocks the kernels take and the host's copies of what later calls are
-// checked against. Its writers -- upload() (hipr_upload_scene), update_geometry() (hipr_update_scene_geometry) and refit_transforms() (hipr_refit_scene_transforms) --
-// are called once every refusal is behind the entry point and every queued pass has finished, and go: ready = false, device work, publish pointers, counts and
+// checked against. Its writers -- upload() (hipr_upload_scene), update_geometry() (hipr_update_scene_geometry), refit_transforms() (hipr_refit_scene_transforms)
+// and update_materials() (hipr_update_scene_materials) -- are called once every refusal is behind the entry point and every queued pass has finished, and go: ready = false, device work, publish pointers, counts and
 // flags, ready = true. One that fails on the way leaves a scene that answers HIPR_ERROR_NOT_READY until an upload succeeds, never one that names freed memory.
 struct ResidentScene {
     DeviceBuffer nodes, wide_nodes, wide8_slots, triangles, instances, lights;                                     // what a geometry update brings again
@@ -146,6 +147,7 @@ struct ResidentScene {
     int shading_models = 7;             // bit mask of the shading models the scene's instances reference
     // Kernel instantiations picked by what the pools hold. A geometry update leaves the material, texture and environment pools in place, so these keep what
     // the UPLOAD decided: a refit description with other materials or texture formats must not switch the kernels over pools that still hold the old data.
+    // Their second writer is update_materials(), which rewrites the material pool and derives them again from the host copies below.
     bool coverage_textures_r8 = false;  // every coverage texture is HIPR_TEXEL_R8 and linear: k_trace_wide8<..., COVERAGE_R8 = true>
     bool has_environment = true;        // an environment map, a presampled environment light or a float texture: k_shade<..., TEXTURES = 2>; 8-bit textures without those: TEXTURES = 1
     bool has_textures = true;           // a material references a texture, or has_environment: k_shade<..., TEXTURES = true>
@@ -156,6 +158,8 @@ struct ResidentScene {
     std::vector<HiprMaterial> uploaded_materials;
     std::vector<uint32_t> uploaded_light_types;
     std::vector<HiprInstance> uploaded_instances;      // a device refit checks a new matrix's handedness against them
+    std::vector<HiprTexture> uploaded_textures;        // small; a material edit derives the texture switches from it again
+    bool uploaded_environment = false;                 // the upload brought an environment description
     uint32_t uploaded_texture_count = 0, uploaded_vertex_count = 0, uploaded_index_count = 0;
     uint64_t uploaded_texel_bytes = 0;
 
@@ -165,6 +169,7 @@ struct ResidentScene {
     uint32_t refit_leaf_count = 0;
     std::vector<uint32_t> refit_node_list, refit_node_words;      // host copy of refit_node_slots and each node's (base_valid, inner_mask) at the time: the topology the lists hold
     double uploaded_half_area = 0.0, current_half_area = 0.0;
+    DeviceBuffer material_touched, material_scratch;   // update_materials: one word per instance; the two reduction words (material_update.h)
     bool tree_stale = false;            // a device refit left the BVH2 and 4-wide arrays behind: hipr_set_trace_variant refuses them until the next upload / geometry update
 
     bool ready = false;
@@ -184,11 +189,13 @@ struct ResidentScene {
     int upload(const HiprSceneDesc* s, const Preflight& checked, int requested_variant, bool cull_backfaces, hipStream_t stream);
     int update_geometry(const HiprSceneDesc* s, const Preflight& checked, int requested_variant, bool cull_backfaces, hipStream_t stream);
     int refit_transforms(const HiprInstanceTransform* moved, uint32_t moved_count, const HiprLight* new_lights, uint32_t light_count, hipStream_t stream, HiprRefitResult* out);
+    int update_materials(const HiprMaterialUpdate* changed, uint32_t changed_count, const HiprInstanceMaterial* assignments, uint32_t assignment_count, hipStream_t stream);
     int lights_keep_their_types(const char* who, const HiprLight* new_lights, uint32_t count) const;
 
 private:
     int upload_pools(const HiprSceneDesc* s, bool all_pools, hipStream_t stream);
     void derive_from_pools(const HiprSceneDesc* s);
+    void derive_switches_from_pools();
     int derive_from_triangles(const HiprSceneDesc* s, const Preflight& checked, bool new_topology, int requested_variant, bool cull_backfaces, hipStream_t stream);
     void queue_triangle_records(hipStream_t stream) const;
     int upload_wide8(const HiprSceneDesc* s, uint32_t height, bool cull_backfaces, hipStream_t stream);
@@ -884,6 +891,16 @@ int detach_tail(HiprContext* c, Wavefront& w, HiprContext::PassSlot& ps, const H
 // O(n) check of everything the kernels dereference through an index of the description (the header is public: a bad ID must be an
 // error code, not an out-of-bounds read on the GPU). Also derives the worst-case stack need of the wide tree instead of trusting
 // the caller's figure. Returns nullptr when the scene is sound, a message otherwise.
+// What makes ONE material unusable against a texture pool of `texture_count` entries: a texture ID outside it, an unknown shading model. The check of
+// validate_scene for every material of a description, and of hipr_update_scene_materials for every slot it is given. Returns nullptr when sound.
+const char* invalid_material(const HiprMaterial& m, uint32_t index, uint32_t texture_count, char* message, size_t message_size) {
+    const int32_t ids[4] = {m.tint_roughness_texture_ID, m.roughness_texture_ID, m.metallic_texture_ID, m.coverage_texture_ID};
+    for (int32_t id : ids)
+        if (id < 0 || (id > 0 && uint32_t(id) >= texture_count)) { snprintf(message, message_size, "material %u references texture %d of %u", index, id, texture_count); return message; }
+    if (m.shading_model > HIPR_SHADING_TRANSMISSIVE) { snprintf(message, message_size, "material %u has the unknown shading model %u", index, unsigned(m.shading_model)); return message; }
+    return nullptr;
+}
+
 const char* validate_scene(const HiprSceneDesc* s, uint32_t& wide_stack_need, char* message, size_t message_size) {
 #define INVALID(...) do { snprintf(message, message_size, __VA_ARGS__); return message; } while (0)
     wide_stack_need = 0;
@@ -902,13 +919,8 @@ const char* validate_scene(const HiprSceneDesc* s, uint32_t& wide_stack_need, ch
         if (t.texel_offset > s->texel_bytes || bytes > s->texel_bytes - t.texel_offset || t.texel_offset % (size == 16 ? 16 : 4) != 0)
             INVALID("texture %u (%u x %u, offset %llu) does not fit the %llu byte texel pool", i, t.width, t.height, (unsigned long long)t.texel_offset, (unsigned long long)s->texel_bytes);
     }
-    for (uint32_t i = 0; i < s->material_count; ++i) {
-        const HiprMaterial& m = s->materials[i];
-        const int32_t ids[4] = {m.tint_roughness_texture_ID, m.roughness_texture_ID, m.metallic_texture_ID, m.coverage_texture_ID};
-        for (int32_t id : ids)
-            if (id < 0 || (id > 0 && uint32_t(id) >= s->texture_count)) INVALID("material %u references texture %d of %u", i, id, s->texture_count);
-        if (m.shading_model > HIPR_SHADING_TRANSMISSIVE) INVALID("material %u has the unknown shading model %u", i, unsigned(m.shading_model));
-    }
+    for (uint32_t i = 0; i < s->material_count; ++i)
+        if (invalid_material(s->materials[i], i, s->texture_count, message, message_size)) return message;
     const uint32_t primitive_total = s->index_count / 3;
     for (uint32_t i = 0; i < s->instance_count; ++i) {
         const HiprInstance& inst = s->instances[i];
@@ -1106,20 +1118,28 @@ float reverse_halton(int prime, int i) {
 // the pools allow (ResidentScene: a geometry update keeps them).
 void ResidentScene::derive_from_pools(const HiprSceneDesc* s) {
     uploaded_materials.assign(s->materials, s->materials + s->material_count);
+    uploaded_textures.assign(s->textures, s->textures + s->texture_count);
+    uploaded_environment = s->environment != nullptr;
     uploaded_light_types.resize(s->light_count);
     for (uint32_t l = 0; l < s->light_count; ++l) uploaded_light_types[l] = s->lights[l].flags & HIPR_LIGHT_TYPE_MASK;
     uploaded_texture_count = s->texture_count; uploaded_vertex_count = s->vertex_count; uploaded_index_count = s->index_count; uploaded_texel_bytes = s->texel_bytes;
-    has_textures = has_environment = s->environment != nullptr;
+    derive_switches_from_pools();
+}
+
+// The kernel instantiations the material, texture and light pools allow, from the host copies of what the device holds: after an upload, and after a material
+// edit (update_materials) has rewritten slots of the material pool.
+void ResidentScene::derive_switches_from_pools() {
+    has_textures = has_environment = uploaded_environment;
     for (const HiprMaterial& material : uploaded_materials)
         has_textures = has_textures || material.tint_roughness_texture_ID || material.roughness_texture_ID || material.metallic_texture_ID || material.coverage_texture_ID;
     for (uint32_t type : uploaded_light_types) has_environment = has_environment || type == HIPR_LIGHT_PRESAMPLED_ENVIRONMENT;
-    for (uint32_t t = 1; t < s->texture_count; ++t)       // float textures take the generic samplers: TEXTURES = 2 as well
-        has_environment = has_environment || s->textures[t].format == HIPR_TEXEL_R32F || s->textures[t].format == HIPR_TEXEL_RGBA32F;
+    for (size_t t = 1; t < uploaded_textures.size(); ++t)       // float textures take the generic samplers: TEXTURES = 2 as well
+        has_environment = has_environment || uploaded_textures[t].format == HIPR_TEXEL_R32F || uploaded_textures[t].format == HIPR_TEXEL_RGBA32F;
     has_textures = has_textures || has_environment;
     coverage_textures_r8 = true;
     for (const HiprMaterial& material : uploaded_materials)
         if (const int32_t id = material.coverage_texture_ID)
-            coverage_textures_r8 = coverage_textures_r8 && uint32_t(id) < s->texture_count && s->textures[id].format == HIPR_TEXEL_R8 && !s->textures[id].is_sRGB;
+            coverage_textures_r8 = coverage_textures_r8 && uint32_t(id) < uploaded_textures.size() && uploaded_textures[id].format == HIPR_TEXEL_R8 && !uploaded_textures[id].is_sRGB;
 }
 
 // The shade and trace records of every triangle (k_build_shade_triangles: the per-hit attribute chain flattened; k_build_trace_triangles: the vertex + edges form
@@ -1367,6 +1387,58 @@ int ResidentScene::refit_transforms(const HiprInstanceTransform* moved, uint32_t
     return HIPR_OK;
 }
 
+// The device work of hipr_update_scene_materials, which has checked every index against uploaded_materials, uploaded_instances and uploaded_textures.
+int ResidentScene::update_materials(const HiprMaterialUpdate* changed, uint32_t changed_count, const HiprInstanceMaterial* assignments, uint32_t assignment_count, hipStream_t st) {
+    ready = false;
+    // the host copies as they will be once the device holds them (after the last synchronise); the copies below read from them
+    std::vector<HiprMaterial> new_materials = uploaded_materials;
+    std::vector<HiprInstance> new_instances = uploaded_instances;
+    std::vector<bool> rewritten(new_materials.size(), false);
+    std::vector<uint32_t> touched(std::max<size_t>(new_instances.size(), 1), 0u);
+    for (uint32_t k = 0; k < changed_count; ++k) { new_materials[changed[k].material_index] = changed[k].material; rewritten[changed[k].material_index] = true; }
+    for (uint32_t k = 0; k < assignment_count; ++k) { new_instances[assignments[k].instance_index].material_index = assignments[k].material_index; touched[assignments[k].instance_index] = 1u; }
+    for (size_t i = 0; i < new_instances.size(); ++i)
+        if (rewritten[size_t(new_instances[i].material_index)]) touched[i] = 1u;
+    // 1. the changed slots and words
+    for (uint32_t k = 0; k < changed_count; ++k) {
+        const size_t at = changed[k].material_index;
+        HIP_TRY(hipMemcpyAsync(materials.as<HiprMaterial>() + at, &new_materials[at], sizeof(HiprMaterial), hipMemcpyHostToDevice, st));
+    }
+    for (uint32_t k = 0; k < assignment_count; ++k) {
+        const size_t at = assignments[k].instance_index;
+        HIP_TRY(hipMemcpyAsync(&instances.as<HiprInstance>()[at].material_index, &new_instances[at].material_index, sizeof(int32_t), hipMemcpyHostToDevice, st));
+    }
+    uint32_t reduction[2] = {1u, 0u};      // all opaque, none coated: the result for a scene without triangles
+    if (args.triangle_count) {
+        // 2. the two passes
+        if (int r = material_touched.upload(touched.data(), touched.size() * 4, st)) return r;
+        if (int r = material_scratch.resize(64)) return r;
+        uint32_t* words = material_scratch.as<uint32_t>();
+        HIP_TRY(hipMemsetAsync(words, 0, 64, st));
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(words), 1, 1, st));
+        const MaterialUpdateArrays a = {triangles.as<HiprTriangle>(), args.triangle_count, instances.as<HiprInstance>(), materials.as<HiprMaterial>(), indices.as<uint32_t>(),
+                                        reinterpret_cast<const float*>(args.texcoords), textures.as<HiprTexture>(), uint32_t(uploaded_textures.size()), texels.as<uint8_t>(),
+                                        material_touched.as<uint32_t>(), trace_triangles.as<uint32_t>(), shade_triangles.as<uint32_t>(), triangle_class.as<uint8_t>()};
+        hipLaunchKernelGGL(k_update_triangle_materials, dim3((args.triangle_count + MATERIAL_UPDATE_BLOCK - 1) / MATERIAL_UPDATE_BLOCK), dim3(MATERIAL_UPDATE_BLOCK), 0, st, a, words);
+        if (wide8.slot_count && refit_leaf_count)
+            hipLaunchKernelGGL(k_update_leaf_flags, dim3((refit_leaf_count + MATERIAL_UPDATE_BLOCK - 1) / MATERIAL_UPDATE_BLOCK), dim3(MATERIAL_UPDATE_BLOCK), 0, st, wide8_slots.as<HiprSlot8>(),
+                               refit_leaf_slots.as<uint32_t>(), refit_leaf_count, triangles.as<HiprTriangle>());
+        HIP_TRY(hipGetLastError());
+        // 3. the eight reduction bytes
+        HIP_TRY(hipMemcpyAsync(reduction, words, sizeof(reduction), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));      // `touched`, new_materials and new_instances are read by now as well
+    // 4., 5. the host copies in step, and what is derived from them
+    uploaded_materials.swap(new_materials);
+    uploaded_instances.swap(new_instances);
+    shading_models = shading_model_mask(uploaded_instances.data(), uint32_t(uploaded_instances.size()), uploaded_materials.data());
+    derive_switches_from_pools();
+    all_triangles_opaque = reduction[0] != 0;
+    any_coated_triangle = reduction[1] != 0;
+    ready = true;
+    return HIPR_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1548,6 +1620,38 @@ int hipr_refit_scene_transforms(HiprContext* c, const HiprInstanceTransform* mov
     return c->scene.refit_transforms(moved, moved_count, lights, light_count, c->stream, out);
 }
 
+// Not part of the public header: every refusal of hipr_update_scene_materials, and nothing else -- the device and the books stay as they are. The group asks
+// every member before any member writes.
+int hipr_internal_check_material_update(HiprContext* c, const HiprMaterialUpdate* materials, uint32_t material_count, const HiprInstanceMaterial* assignments, uint32_t assignment_count) {
+    if (int st = check_context(c)) return st;
+    const ResidentScene& r = c->scene;
+    if (!r.ready) return fail(HIPR_ERROR_NOT_READY, "hipr_update_scene_materials: no scene uploaded");
+    if ((material_count && !materials) || (assignment_count && !assignments)) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_materials: null array with a non-zero count");
+    for (uint32_t k = 0; k < material_count; ++k) {
+        if (materials[k].material_index >= r.uploaded_materials.size())
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_materials: material %u of %zu (the material pool does not grow; upload the scene instead)", materials[k].material_index, r.uploaded_materials.size());
+        char invalid[256];
+        if (invalid_material(materials[k].material, materials[k].material_index, uint32_t(r.uploaded_textures.size()), invalid, sizeof(invalid)))
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_materials: %s", invalid);
+    }
+    for (uint32_t k = 0; k < assignment_count; ++k) {
+        if (assignments[k].instance_index >= r.uploaded_instances.size())
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_materials: instance %u of %zu", assignments[k].instance_index, r.uploaded_instances.size());
+        if (assignments[k].material_index < 0 || size_t(assignments[k].material_index) >= r.uploaded_materials.size())
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_materials: instance %u is given material %d of %zu", assignments[k].instance_index, assignments[k].material_index, r.uploaded_materials.size());
+    }
+    // The exhaustive search's items pair triangles of equal flags (build_trace_items): there a material edit changes a topology, which only the host builds.
+    if (r.args.trace_item_count != 0)
+        return fail(HIPR_ERROR_UNSUPPORTED, "hipr_update_scene_materials: the uploaded scene carries the exhaustive search's items, which pair triangles by their flags; upload the scene instead");
+    return HIPR_OK;
+}
+
+int hipr_update_scene_materials(HiprContext* c, const HiprMaterialUpdate* materials, uint32_t material_count, const HiprInstanceMaterial* assignments, uint32_t assignment_count) {
+    if (int st = hipr_internal_check_material_update(c, materials, material_count, assignments, assignment_count)) return st;
+    if (int finish_status = finish_all(c)) return finish_status;      // no pending pass may go on over the new materials
+    return c->scene.update_materials(materials, material_count, assignments, assignment_count, c->stream);
+}
+
 int hipr_debug_read_scene_buffer(HiprContext* c, int which, void* out, uint64_t capacity_bytes) {
     if (int st = check_context(c)) return st;
     if (!out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: null output");
@@ -1556,6 +1660,11 @@ int hipr_debug_read_scene_buffer(HiprContext* c, int which, void* out, uint64_t 
     uint64_t bytes = 0;
     if (which == HIPR_SCENE_BUFFER_TRIANGLES) { from = c->scene.triangles.ptr; bytes = uint64_t(c->scene.args.triangle_count) * sizeof(HiprTriangle); }
     else if (which == HIPR_SCENE_BUFFER_WIDE8_SLOTS) { from = c->scene.wide8_slots.ptr; bytes = uint64_t(c->scene.wide8.slot_count) * sizeof(HiprSlot8); }
+    else if (which == HIPR_SCENE_BUFFER_TRACE_TRIANGLES) { from = c->scene.trace_triangles.ptr; bytes = uint64_t(c->scene.args.triangle_count) * 3 * sizeof(float4); }
+    else if (which == HIPR_SCENE_BUFFER_SHADE_TRIANGLES) { from = c->scene.shade_triangles.ptr; bytes = uint64_t(c->scene.args.triangle_count) * SHADE_TRIANGLE_QUADS * sizeof(float4); }
+    else if (which == HIPR_SCENE_BUFFER_TRIANGLE_CLASS) { from = c->scene.triangle_class.ptr; bytes = uint64_t(c->scene.args.triangle_count); }
+    else if (which == HIPR_SCENE_BUFFER_MATERIALS) { from = c->scene.materials.ptr; bytes = uint64_t(c->scene.uploaded_materials.size()) * sizeof(HiprMaterial); }
+    else if (which == HIPR_SCENE_BUFFER_INSTANCES) { from = c->scene.instances.ptr; bytes = uint64_t(c->scene.uploaded_instances.size()) * sizeof(HiprInstance); }
     else return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: unknown buffer %d", which);
     if (capacity_bytes < bytes) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: %llu bytes needed, %llu given", (unsigned long long)bytes, (unsigned long long)capacity_bytes);
     if (int finish_status = finish_all(c)) return finish_status;

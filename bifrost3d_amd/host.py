@@ -28,6 +28,12 @@ def load_host_library() -> C.CDLL:
     lib.hiprh_make_camera.argtypes = [C.POINTER(C.c_float), C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(capi.HiprCameraState)]
     lib.hiprh_scene_move_model.argtypes = [vp, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_double]
     lib.hiprh_scene_model_pose.argtypes = [vp, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_uint), C.POINTER(C.c_float), C.c_uint]
+    lib.hiprh_scene_update_materials.argtypes = [vp, C.POINTER(capi.HiprMaterialUpdate), C.c_uint, C.POINTER(capi.HiprInstanceMaterial), C.c_uint]
+    lib.hiprh_scene_rebuild.argtypes = [vp]
+    lib.hiprh_scene_materials.argtypes = [vp, C.POINTER(C.c_uint)]
+    lib.hiprh_scene_materials.restype = C.POINTER(capi.HiprMaterial)
+    lib.hiprh_scene_instances.argtypes = [vp, C.POINTER(C.c_uint)]
+    lib.hiprh_scene_instances.restype = C.POINTER(capi.HiprInstance)
     lib.hiprh_wide8_quantise_nodes.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_uint), C.POINTER(C.c_float), vp, C.c_uint]
     lib.hiprh_wide8_quantise_nodes.restype = None
     lib.hiprh_scene_destroy.argtypes = [vp]
@@ -133,6 +139,41 @@ class Scene:
         matrices = np.zeros((max(count, 1), 3, 4), np.float32)
         self.lib.hiprh_scene_model_pose(self.handle, model_index, t, r, scale, indices.ctypes.data_as(C.POINTER(C.c_uint)), matrices.ctypes.data_as(C.POINTER(C.c_float)), count)
         return [(int(indices[k]), matrices[k].copy()) for k in range(count)]
+
+    def update_materials(self, materials=(), assignments=()) -> bool:
+        """Material-only update WITHOUT a rebuild (SceneBuilder::update_materials): `materials` is a sequence of (material index, capi.HiprMaterial), `assignments` one
+        of (instance index, material index) -- what Context.update_scene_materials takes. False, with nothing done, when an index is out of range."""
+        materials, assignments = list(materials), list(assignments)
+        status = self.lib.hiprh_scene_update_materials(self.handle, capi.material_updates(materials), len(materials), capi.instance_materials(assignments), len(assignments))
+        if status < 0:
+            raise capi.HiprError("hiprh_scene_update_materials failed")
+        return status == 1
+
+    def rebuild(self):
+        """A fresh build (triangle flags, BVH2, 4-wide and 8-wide trees) over the instances and materials as they stand."""
+        if self.lib.hiprh_scene_rebuild(self.handle) != 0:
+            raise capi.HiprError("hiprh_scene_rebuild failed")
+
+    def materials(self) -> list:
+        """Copies of the scene's materials (capi.HiprMaterial), slot 0 the invalid material."""
+        count = C.c_uint()
+        pointer = self.lib.hiprh_scene_materials(self.handle, C.byref(count))
+        out = []
+        for k in range(count.value):
+            m = capi.HiprMaterial()
+            C.memmove(C.byref(m), C.byref(pointer[k]), C.sizeof(capi.HiprMaterial))
+            out.append(m)
+        return out
+
+    def materials_array(self) -> np.ndarray:
+        count = C.c_uint()
+        pointer = self.lib.hiprh_scene_materials(self.handle, C.byref(count))
+        return np.ctypeslib.as_array(C.cast(pointer, C.POINTER(C.c_uint32)), shape=(count.value, 16)).copy()
+
+    def instances_array(self) -> np.ndarray:
+        count = C.c_uint()
+        pointer = self.lib.hiprh_scene_instances(self.handle, C.byref(count))
+        return np.ctypeslib.as_array(C.cast(pointer, C.POINTER(C.c_uint32)), shape=(count.value, 20)).copy()
 
     def wide8_slots(self) -> np.ndarray:
         d = self.desc

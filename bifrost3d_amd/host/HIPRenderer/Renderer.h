@@ -96,8 +96,9 @@ public:
     // Test / tooling access: the accumulation buffer as RGBA f64 (row-major, row 0 = bottom).
     bool read_accumulation(std::vector<double>& out_rgba) const;
     // ... and how the scene has reached the devices so far, summed over the cameras: whole descriptions uploaded (hipr_upload_scene), host refits sent after
-    // (hipr_update_scene_geometry) and refits done by the devices themselves that needed no rebuild (hipr_refit_scene_transforms).
-    struct SceneUpdateCounts { unsigned int uploads, geometry_updates, device_refits; };
+    // (hipr_update_scene_geometry), refits done by the devices themselves that needed no rebuild (hipr_refit_scene_transforms) and material edits applied to
+    // the resident scene (hipr_update_scene_materials).
+    struct SceneUpdateCounts { unsigned int uploads, geometry_updates, device_refits, material_updates; };
     SceneUpdateCounts scene_update_counts() const;
 
 private:

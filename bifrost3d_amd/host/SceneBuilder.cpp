@@ -1,6 +1,8 @@
 // host/SceneBuilder.cpp -- see SceneBuilder.h.
 #include "SceneBuilder.h"
 
+#include "../csrc/material_rules.h"      // the flag rules, shared with the kernels that apply a material edit on the device
+
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -169,51 +171,6 @@ void SceneBuilder::force_shading_model(uint16_t shading_model) {
     for (size_t i = 1; i < m_materials.size(); ++i) m_materials[i].shading_model = shading_model;
 }
 
-static bool statically_opaque(const HiprMaterial& m) {
-    // get_coverage (OptiXRenderer/Types.h:405-414) with no coverage texture: cutout -> (1 < threshold ? 0 : 1), else coverage.
-    if (m.coverage_texture_ID) return false;
-    if (m.flags & HIPR_MATERIAL_CUTOUT) return !(1.0f < m.coverage);
-    return m.coverage >= 1.0f;
-}
-
-// A triangle of a material that is NOT statically opaque can still be: where its coverage texture covers it everywhere -- a finely tessellated cut-out surface
-// (a fence, a lace banner) has many triangles that lie wholly on solid texels. Those get HIPR_TRIANGLE_OPAQUE too, and a shadow ray that hits one ends without
-// the material -> texture -> texel lookups; get_coverage (OptiXRenderer/Types.h:405-414) would have returned 1 for every point of the triangle, so nothing changes
-// for the reference's any-hit program, the oracle's or the kernels'. Decided conservatively from the texels the sampler can touch for ANY point of the triangle:
-// the texture coordinates of its points lie in the bounding box of its corners' (the interpolation's rounding is covered by a texel of slack on every side), so
-// every texel under that box, plus the bilinear neighbour, must pass. 8-bit linear textures only; boxes of more than 64 x 64 texels are left to the sampler.
-static bool covered_everywhere(const HiprMaterial& m, const HiprTexture& t, const uint8_t* texels, const float (&uv)[3][2]) {
-    if ((t.format != HIPR_TEXEL_R8 && t.format != HIPR_TEXEL_RGBA8) || t.is_sRGB || t.width == 0 || t.height == 0) return false;
-    const bool cutout = (m.flags & HIPR_MATERIAL_CUTOUT) != 0;
-    if (!cutout && !(m.coverage >= 1.0f)) return false;
-    const bool linear = (t.filter & 1) != 0;
-    const int size[2] = {int(t.width), int(t.height)};
-    int first[2], last[2];
-    for (int a = 0; a < 2; ++a) {
-        const float lo = std::min(uv[0][a], std::min(uv[1][a], uv[2][a])) * float(size[a]), hi = std::max(uv[0][a], std::max(uv[1][a], uv[2][a])) * float(size[a]);
-        if (!(std::fabs(lo) < 1048576.0f) || !(std::fabs(hi) < 1048576.0f)) return false;      // also NaN
-        first[a] = int(std::floor(lo - (linear ? 0.5f : 0.0f))) - 1;
-        last[a] = int(std::floor(hi - (linear ? 0.5f : 0.0f))) + (linear ? 1 : 0) + 1;
-        if (last[a] - first[a] + 1 > 64) return false;
-    }
-    const int channels = t.format == HIPR_TEXEL_RGBA8 ? 4 : 1;
-    const uint8_t* base = texels + t.texel_offset;
-    auto wrap = [](int i, int n, bool repeat) { if (repeat) { i %= n; return i < 0 ? i + n : i; } return i < 0 ? 0 : (i >= n ? n - 1 : i); };
-    for (int y = first[1]; y <= last[1]; ++y)
-        for (int x = first[0]; x <= last[0]; ++x) {
-            const uint8_t value = base[(size_t(wrap(y, size[1], t.wrap_v != 0)) * t.width + size_t(wrap(x, size[0], t.wrap_u != 0))) * size_t(channels)];      // the sampler's .x
-            // cut-out: the sampled value must not fall below the threshold -- with a margin that a bilinear blend of passing texels cannot round through;
-            // plain coverage: coverage * texture must be 1, i.e. every texel exactly 1
-            if (cutout ? !(float(value) / 255.0f > m.coverage + 1e-5f) : value != 255) return false;
-        }
-    return true;
-}
-
-// backside_cull of the hit program (OptiXRenderer/Shading/MonteCarlo.cu:147-164): !hit_from_front && !thin_walled && !transmissive, thin_walled = cut-out or thin-walled.
-static bool refuses_hits_from_behind(const HiprMaterial& m) {
-    return !(m.flags & (HIPR_MATERIAL_CUTOUT | HIPR_MATERIAL_THIN_WALLED)) && m.shading_model != HIPR_SHADING_TRANSMISSIVE;
-}
-
 void SceneBuilder::finalize(uint32_t bvh_max_depth) {
     std::vector<HiprTriangle> world;
     m_bounds = AABB::invalid();
@@ -222,8 +179,6 @@ void SceneBuilder::finalize(uint32_t bvh_max_depth) {
         const MeshRecord& mesh = m_meshes[m_instance_mesh[i]];
         const float* M = inst.object_to_world;
         const HiprMaterial& material = m_materials[inst.material_index];
-        const bool opaque = statically_opaque(material);
-        const bool one_sided = refuses_hits_from_behind(m_materials[inst.material_index]);
         auto to_world = [&](uint32_t v, float* out) {
             const float* p = m_geometry[mesh.vertex_offset + v].position;
             for (int r = 0; r < 3; ++r) out[r] = M[4 * r] * p[0] + M[4 * r + 1] * p[1] + M[4 * r + 2] * p[2] + M[4 * r + 3];
@@ -235,14 +190,8 @@ void SceneBuilder::finalize(uint32_t bvh_max_depth) {
             to_world(idx[0], t.v0); to_world(idx[1], t.v1); to_world(idx[2], t.v2);
             t.instance_index = i;
             t.primitive_index = p;
-            bool triangle_opaque = opaque;
-            if (!opaque && material.coverage_texture_ID > 0 && size_t(material.coverage_texture_ID) < m_textures.size()) {      // covered_everywhere: this triangle may still be
-                float uv[3][2] = {{0, 0}, {0, 0}, {0, 0}};
-                if (inst.mesh_flags & HIPR_MESH_TEXCOORDS)
-                    for (int k = 0; k < 3; ++k) { uv[k][0] = m_texcoords[2 * size_t(mesh.vertex_offset + idx[k])]; uv[k][1] = m_texcoords[2 * size_t(mesh.vertex_offset + idx[k]) + 1]; }
-                triangle_opaque = covered_everywhere(material, m_textures[size_t(material.coverage_texture_ID)], m_texels.data(), uv);
-            }
-            t.flags = (triangle_opaque ? HIPR_TRIANGLE_OPAQUE : 0) | (one_sided ? HIPR_TRIANGLE_ONE_SIDED : 0);
+            // covered_everywhere: a triangle of a material that is not statically opaque may still be
+            t.flags = hipr::triangle_flags(material, inst, p, m_indices.data(), m_texcoords.data(), m_textures.data(), uint32_t(m_textures.size()), m_texels.data());
             world.push_back(t);
         }
     }
@@ -355,6 +304,51 @@ bool SceneBuilder::apply_staged_transforms(double rebuild_threshold) {
     if (area < 0.0 || (m_built_bvh_area > 0.0 && area > rebuild_threshold * m_built_bvh_area)) {      // area < 0: a leaf record of the 8-wide tree could not be refitted
         finalize(m_bvh_max_depth_limit);      // the instances already carry the new transforms
         return false;
+    }
+    return true;
+}
+
+bool SceneBuilder::update_materials(const std::vector<HiprMaterialUpdate>& changed, const std::vector<HiprInstanceMaterial>& assignments) {
+    for (const HiprMaterialUpdate& c : changed)
+        if (c.material_index >= m_materials.size()) return false;
+    for (const HiprInstanceMaterial& a : assignments)
+        if (a.instance_index >= m_instances.size() || a.material_index < 0 || size_t(a.material_index) >= m_materials.size()) return false;
+    // `rewritten`: slots whose new contents can give a triangle other flags -- the rules read a material's flags, shading model, coverage and coverage texture and
+    // nothing else, so a roughness slider leaves every triangle and every leaf record alone
+    std::vector<bool> rewritten(m_materials.size(), false), touched(m_instances.size(), false);
+    for (const HiprMaterialUpdate& c : changed) {
+        const HiprMaterial& was = m_materials[c.material_index];
+        if (was.flags != c.material.flags || was.shading_model != c.material.shading_model || std::memcmp(&was.coverage, &c.material.coverage, sizeof(float)) != 0 ||
+            was.coverage_texture_ID != c.material.coverage_texture_ID)
+            rewritten[c.material_index] = true;
+        m_materials[c.material_index] = c.material;
+    }
+    for (const HiprInstanceMaterial& a : assignments) { m_instances[a.instance_index].material_index = a.material_index; touched[a.instance_index] = true; }
+    for (size_t i = 0; i < m_instances.size(); ++i) touched[i] = touched[i] || rewritten[size_t(m_instances[i].material_index)];
+    if (std::find(touched.begin(), touched.end(), true) == touched.end()) return true;
+    bool flags_changed = false;
+    for (HiprTriangle& t : m_triangles) {
+        if (!touched[t.instance_index]) continue;
+        const HiprInstance& inst = m_instances[t.instance_index];
+        const uint32_t before = t.flags;
+        t.flags = hipr::triangle_flags(m_materials[size_t(inst.material_index)], inst, t.primitive_index, m_indices.data(), m_texcoords.data(), m_textures.data(), uint32_t(m_textures.size()), m_texels.data());
+        flags_changed = flags_changed || t.flags != before;
+    }
+    if (!flags_changed) return true;
+    // the leaf records of the 8-wide tree repeat the flags of their triangles; the tree is walked from the root, children in consecutive slots
+    std::vector<HiprSlot8>& slots = m_bvh.wide8.slots;
+    std::vector<uint32_t> nodes;
+    if (!slots.empty()) nodes.push_back(0u);
+    for (size_t i = 0; i < nodes.size(); ++i) {
+        const HiprNode8 n = slots[nodes[i]].node;
+        const uint32_t base = n.base_valid & 0xFFFFFFu, valid = n.base_valid >> 24;
+        uint32_t rank = 0;
+        for (int p = 0; p < 8; ++p) {
+            if (!(valid >> p & 1u)) continue;
+            const uint32_t child = base + rank++;
+            if (n.inner_mask >> p & 1u) nodes.push_back(child);
+            else slots[child].leaf.flags = (slots[child].leaf.flags & ~15u) | hipr::leaf_material_bits(m_triangles.data(), slots[child].leaf);
+        }
     }
     return true;
 }

@@ -87,6 +87,12 @@ public:
     bool apply_staged_transforms(double rebuild_threshold = 1.5);
     bool has_staged_transforms() const { return m_staged; }
     void rebuild();
+    // Material-only update after finalize(): `changed` rewrites material slots, `assignments` gives instances another material. The builder's own description is
+    // kept in step WITHOUT a rebuild -- a material moves no corner and the tree builders read no flag, so the trees and the triangle order are the ones a rebuild
+    // would make: the flags of the touched instances' triangles are recomputed (csrc/material_rules.h) and the leaf records of the 8-wide tree follow them. What
+    // hipr_update_scene_materials does to the resident scene. Returns false, with nothing done, for an index out of range.
+    bool update_materials(const std::vector<HiprMaterialUpdate>& changed, const std::vector<HiprInstanceMaterial>& assignments);
+    const std::vector<HiprMaterial>& materials() const { return m_materials; }
     const std::vector<HiprLight>& lights() const { return m_lights; }
     const std::vector<HiprInstance>& instances() const { return m_instances; }
     // The lights of a finalized scene replaced one for one (moved or re-coloured lights; the count must match).

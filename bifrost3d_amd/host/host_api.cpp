@@ -337,6 +337,37 @@ int hiprh_scene_model_pose(void* scene, unsigned model_index, const float* trans
     return int(count);
 }
 
+// Material-only update of a built scene (SceneBuilder::update_materials): slots of the material pool rewritten, instances given another material; the builder's
+// description follows without a rebuild. Returns 1 when done, 0 when an index was out of range (nothing done), -1 on error.
+int hiprh_scene_update_materials(void* scene, const HiprMaterialUpdate* materials, unsigned material_count, const HiprInstanceMaterial* assignments, unsigned assignment_count) {
+    if (!scene || (material_count && !materials) || (assignment_count && !assignments)) return -1;
+    try {
+        return static_cast<SceneBuilder*>(scene)->update_materials(std::vector<HiprMaterialUpdate>(materials, materials + material_count),
+                                                                   std::vector<HiprInstanceMaterial>(assignments, assignments + assignment_count)) ? 1 : 0;
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_update_materials: %s\n", e.what()); return -1; }
+}
+
+// SceneBuilder::rebuild: a fresh tree over the instances and materials as they stand. Returns 0, -1 on error.
+int hiprh_scene_rebuild(void* scene) {
+    if (!scene) return -1;
+    try { static_cast<SceneBuilder*>(scene)->rebuild(); return 0; }
+    catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_rebuild: %s\n", e.what()); return -1; }
+}
+
+// The builder's material and instance arrays (valid until the scene changes or is destroyed).
+const HiprMaterial* hiprh_scene_materials(void* scene, unsigned* out_count) {
+    if (!scene || !out_count) return nullptr;
+    const std::vector<HiprMaterial>& m = static_cast<SceneBuilder*>(scene)->materials();
+    *out_count = unsigned(m.size());
+    return m.data();
+}
+const HiprInstance* hiprh_scene_instances(void* scene, unsigned* out_count) {
+    if (!scene || !out_count) return nullptr;
+    const std::vector<HiprInstance>& i = static_cast<SceneBuilder*>(scene)->instances();
+    *out_count = unsigned(i.size());
+    return i.data();
+}
+
 // Wide8Builder.cpp's quantise_node on one synthetic node (tests of csrc/wide8_refit.h's restatement).
 void hiprh_wide8_quantise_node(const float* boxes_8x6, unsigned valid, const float* grid_min3, const float* grid_cell3, HiprNode8* out) {
     HIPRenderer::quantise_wide8_node(boxes_8x6, valid, grid_min3, grid_cell3, *out);

@@ -87,11 +87,22 @@ class Context:
         return dict(needs_rebuild=bool(result.needs_rebuild), child_half_area=float(result.child_half_area), uploaded_half_area=float(result.uploaded_half_area),
                     grid_min=np.array(result.grid_min[:], np.float32), grid_cell=np.array(result.grid_cell[:], np.float32))
 
+    def update_scene_materials(self, materials=(), assignments=()):
+        """hipr_update_scene_materials: `materials` is a sequence of (material index, capi.HiprMaterial) that rewrites slots of the uploaded material pool, `assignments`
+        one of (instance index, material index) that gives uploaded instances another material; applied to the resident scene by kernels, no upload."""
+        materials, assignments = list(materials), list(assignments)
+        self._check(self.lib.hipr_update_scene_materials(self.handle, capi.material_updates(materials), len(materials), capi.instance_materials(assignments), len(assignments)),
+                    "hipr_update_scene_materials")
+
     def read_scene_buffer(self, which: int) -> np.ndarray:
-        """The scene array the device holds (hipr_debug_read_scene_buffer): capi.SCENE_BUFFER_TRIANGLES -> (triangles, 12) uint32 words, SCENE_BUFFER_WIDE8_SLOTS -> (slots, 16)."""
+        """The scene array the device holds (hipr_debug_read_scene_buffer): capi.SCENE_BUFFER_TRIANGLES -> (triangles, 12) uint32 words, SCENE_BUFFER_WIDE8_SLOTS -> (slots, 16),
+        _TRACE_TRIANGLES -> (triangles, 12), _SHADE_TRIANGLES -> (triangles, 32), _TRIANGLE_CLASS -> (triangles,) uint8, _MATERIALS -> (materials, 16), _INSTANCES -> (instances, 20)."""
         desc = self._scene.desc
-        rows, words = (desc.triangle_count, 12) if which == capi.SCENE_BUFFER_TRIANGLES else (desc.wide8_slot_count, 16)
-        out = np.zeros((rows, words), np.uint32)
+        shape, dtype = {capi.SCENE_BUFFER_TRIANGLES: ((desc.triangle_count, 12), np.uint32), capi.SCENE_BUFFER_WIDE8_SLOTS: ((desc.wide8_slot_count, 16), np.uint32),
+                        capi.SCENE_BUFFER_TRACE_TRIANGLES: ((desc.triangle_count, 12), np.uint32), capi.SCENE_BUFFER_SHADE_TRIANGLES: ((desc.triangle_count, 32), np.uint32),
+                        capi.SCENE_BUFFER_TRIANGLE_CLASS: ((desc.triangle_count,), np.uint8), capi.SCENE_BUFFER_MATERIALS: ((desc.material_count, 16), np.uint32),
+                        capi.SCENE_BUFFER_INSTANCES: ((desc.instance_count, 20), np.uint32)}.get(which, ((0,), np.uint8))
+        out = np.zeros(shape, dtype)
         self._check(self.lib.hipr_debug_read_scene_buffer(self.handle, int(which), C.c_void_p(out.ctypes.data), out.nbytes), "hipr_debug_read_scene_buffer")
         return out
 

@@ -369,6 +369,23 @@ typedef struct HiprRefitResult {
 } HiprRefitResult;
 int hipr_refit_scene_transforms(HiprContext* context, const HiprInstanceTransform* moved, uint32_t moved_count,
                                 const HiprLight* lights /* NULL: keep */, uint32_t light_count, HiprRefitResult* out);
+/* Material edits WITHOUT a new upload (the reference rewrites one slot of its material buffer, OR/Renderer.cpp:753-850): `materials` rewrites slots of the
+ * uploaded material pool, `assignments` gives uploaded instances another material of that pool. The changed slots and words are copied into the resident pools,
+ * and two short passes bring along everything an upload derives from materials -- HiprTriangle::flags of the touched instances' triangles (the flag rules of
+ * csrc/material_rules.h, which the host's scene builder runs too), their copies in the trace records, the material index in the shading records, the
+ * coat class of the listing pass, bits 0..3 of the 8-wide tree's leaf records -- and the kernel instantiations the context picks by what the pools hold:
+ * afterwards the device holds, byte for byte, what hipr_upload_scene of the edited description would put there (csrc/material_update.h). No tree is touched:
+ * a material moves no box. Checked before anything on the device is touched:
+ *   HIPR_ERROR_NOT_READY          no scene is uploaded;
+ *   HIPR_ERROR_INVALID_ARGUMENT   a null array with a non-zero count; a material or instance index outside the uploaded pools; a new material index outside
+ *                                 the material pool; a material hipr_validate_scene would refuse (a texture ID outside the uploaded textures, an unknown
+ *                                 shading model);
+ *   HIPR_ERROR_UNSUPPORTED        the scene carries the exhaustive search's items (at most 64 triangles), which pair triangles of equal flags: there a
+ *                                 material edit changes a topology. Upload the scene instead; it costs nothing at that size. */
+typedef struct HiprMaterialUpdate   { uint32_t material_index; HiprMaterial material; } HiprMaterialUpdate;
+typedef struct HiprInstanceMaterial { uint32_t instance_index; int32_t material_index; } HiprInstanceMaterial;
+int hipr_update_scene_materials(HiprContext* context, const HiprMaterialUpdate* materials, uint32_t material_count,
+                                const HiprInstanceMaterial* assignments, uint32_t assignment_count);
 int hipr_set_scene_state(HiprContext* context, const HiprSceneState* state);
 
 /* Entry points, numbered like OR/Types.h:33-44. set_backend() of the host renderer maps Backend values onto them
@@ -450,6 +467,8 @@ int hipr_group_upload_scene(HiprGroup* group, const HiprSceneDesc* scene);
 int hipr_group_update_scene_geometry(HiprGroup* group, const HiprSceneDesc* scene);
 int hipr_group_refit_scene_transforms(HiprGroup* group, const HiprInstanceTransform* moved, uint32_t moved_count,
                                       const HiprLight* lights, uint32_t light_count, HiprRefitResult* out);   /* every member; their results must agree */
+int hipr_group_update_scene_materials(HiprGroup* group, const HiprMaterialUpdate* materials, uint32_t material_count,
+                                      const HiprInstanceMaterial* assignments, uint32_t assignment_count);   /* every member checks before any member writes */
 int hipr_group_set_scene_state(HiprGroup* group, const HiprSceneState* state);
 int hipr_group_set_entry_point(HiprGroup* group, int entry);
 int hipr_group_use_scratch_accumulation(HiprGroup* group, int enable);
@@ -585,8 +604,11 @@ int hipr_debug_sample_offsets(HiprContext* context, float* out_256x4);
 int hipr_debug_trace_closest(HiprContext* context, const float* rays, const uint32_t* skip, uint32_t n, float* out_hits);
 /* K4: shadow transmittance for n rays (float4 origin_tmin + float4 direction_tmax) -> one float per ray. */
 int hipr_debug_trace_shadow(HiprContext* context, const float* rays, uint32_t n, float* out_transmittance);
-/* The uploaded (or device-refitted) scene arrays as the device holds them: HiprTriangle[triangle_count] or HiprSlot8[wide8_slot_count]. */
-enum { HIPR_SCENE_BUFFER_TRIANGLES = 0, HIPR_SCENE_BUFFER_WIDE8_SLOTS = 1 };
+/* The uploaded (or device-refitted, or material-updated) scene arrays as the device holds them: HiprTriangle[triangle_count], HiprSlot8[wide8_slot_count], the
+ * trace records (48 bytes per triangle), the shading records (128 bytes per triangle), the class bytes of the listing pass (one per triangle),
+ * HiprMaterial[material_count], HiprInstance[instance_count]. */
+enum { HIPR_SCENE_BUFFER_TRIANGLES = 0, HIPR_SCENE_BUFFER_WIDE8_SLOTS = 1, HIPR_SCENE_BUFFER_TRACE_TRIANGLES = 2, HIPR_SCENE_BUFFER_SHADE_TRIANGLES = 3,
+       HIPR_SCENE_BUFFER_TRIANGLE_CLASS = 4, HIPR_SCENE_BUFFER_MATERIALS = 5, HIPR_SCENE_BUFFER_INSTANCES = 6 };
 int hipr_debug_read_scene_buffer(HiprContext* context, int which, void* out, uint64_t capacity_bytes);
 
 #ifdef __cplusplus
