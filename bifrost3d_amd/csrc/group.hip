@@ -341,6 +341,13 @@ int hipr_group_refit_scene_transforms(HiprGroup* g, const HiprInstanceTransform*
     return HIPR_OK;
 }
 
+// The BVH2 build of hipr_build_bvh2 on member 0: one tree serves every member, which are given the same description afterwards.
+int hipr_group_build_bvh2(HiprGroup* g, const HiprTriangle* triangles, uint32_t count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_node_count,
+                          uint32_t* out_order, uint32_t* out_deepest) {
+    if (!g || g->members.empty()) return HIPR_ERROR_INVALID_ARGUMENT;
+    return hipr_build_bvh2(g->members[0].context, triangles, count, max_depth, out_nodes, node_capacity, out_node_count, out_order, out_deepest);
+}
+
 int hipr_group_update_scene_materials(HiprGroup* g, const HiprMaterialUpdate* materials, uint32_t material_count, const HiprInstanceMaterial* assignments, uint32_t assignment_count) {
     if (!g) return HIPR_ERROR_INVALID_ARGUMENT;
     // Every member checks before any member writes: an edit one member refuses leaves all of them as they were.

@@ -15,11 +15,13 @@
 #include "wide8_kernels.h"
 #include "wide8_refit.h"
 #include "material_update.h"
+#include "bvh2_build.h"
 #include "launch.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -248,6 +250,24 @@ Knobs knobs_from_environment() {
     return k;
 }
 
+// The device scratch of hipr_build_bvh2 (bvh2_build.h), about 240 B per triangle. Up to KEEP_BYTES (a build of a quarter of a million triangles) it stays with the
+// context and the next build reuses it; a larger build gives its scratch back when it returns, whatever its outcome -- 2.4 GB at 10 M triangles are not held on a
+// shared device between two edits that are seconds apart at best.
+struct BuildScratch {
+    static constexpr size_t KEEP_BYTES = size_t(128) << 20;
+    DeviceBuffer triangles, boxes, centroids, order, seg, order_tmp, seg_tmp, ranges[2], acc, setup, split, scan_local, block_sums, nodes, sizes, place, out_nodes, status;
+    double validate_ms = 0.0, upload_ms = 0.0, kernel_ms = 0.0, readback_ms = 0.0;      // of the last build
+    uint32_t levels = 0;
+    void release_if_large() {
+        DeviceBuffer* all[] = {&triangles, &boxes, &centroids, &order, &seg, &order_tmp, &seg_tmp, &ranges[0], &ranges[1], &acc, &setup, &split, &scan_local, &block_sums, &nodes, &sizes, &place, &out_nodes, &status};
+        size_t total = 0;
+        for (const DeviceBuffer* b : all) total += b->bytes;
+        if (total > KEEP_BYTES) for (DeviceBuffer* b : all) b->release();
+    }
+};
+// Gives a large build's scratch back on every way out of hipr_build_bvh2.
+struct BuildScratchGuard { BuildScratch& scratch; ~BuildScratchGuard() { scratch.release_if_large(); } };
+
 } // namespace
 
 struct HiprContext {
@@ -336,6 +356,7 @@ struct HiprContext {
     HiprKernelTimes times = {};
 
     DeviceBuffer debug_a, debug_b, debug_c;
+    BuildScratch build;                 // hipr_build_bvh2; nothing of the resident scene
 
     hipEvent_t next_event() {
         if (events_used == event_pool.size()) {
@@ -1650,6 +1671,128 @@ int hipr_update_scene_materials(HiprContext* c, const HiprMaterialUpdate* materi
     if (int st = hipr_internal_check_material_update(c, materials, material_count, assignments, assignment_count)) return st;
     if (int finish_status = finish_all(c)) return finish_status;      // no pending pass may go on over the new materials
     return c->scene.update_materials(materials, material_count, assignments, assignment_count, c->stream);
+}
+
+// The BVH2 of host/BvhBuilder.cpp built by the kernels of bvh2_build.h. Nothing of the resident scene is read or written; the outputs are written only once the
+// whole build has succeeded.
+int hipr_build_bvh2(HiprContext* c, const HiprTriangle* triangles, uint32_t count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_node_count,
+                    uint32_t* out_order, uint32_t* out_deepest) {
+    if (int st = check_context(c)) return st;
+    const auto t_validate = std::chrono::steady_clock::now();
+    if (!triangles || !count || !out_nodes || !out_node_count || !out_order || !out_deepest) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_bvh2: null argument or no triangles");
+    if (count > BUILD_MAX_TRIANGLES) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_build_bvh2: %u triangles, a leaf reference holds %u", count, BUILD_MAX_TRIANGLES);
+    if (node_capacity < std::max(std::max(count, 1u) - 1u, 1u)) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_bvh2: room for %u nodes, %u triangles can need %u", node_capacity, count, std::max(count - 1u, 1u));
+    for (uint32_t i = 0; i < count; ++i)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(triangles[i].v0[k]) || !std::isfinite(triangles[i].v1[k]) || !std::isfinite(triangles[i].v2[k]))
+                return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_bvh2: triangle %u has a corner that is not finite", i);
+    const uint32_t depth_limit = std::max(max_depth, 8u);
+    const uint32_t max_levels = std::min(depth_limit, count) + 2u;      // a range's depth grows by one per level and never passes the limit
+    const size_t n = count, max_open = n / 4 + 2, max_long = n / BUILD_SHORT_RANGE + 2, blocks = (n + BUILD_BLOCK - 1) / BUILD_BLOCK;
+    const size_t status_words = STATUS_LEVELS + 2 * size_t(max_levels + 2);
+    BuildScratch& b = c->build;
+    const BuildScratchGuard guard{b};
+    hipStream_t stream = c->stream;
+    c->break_chain(stream);
+    const auto t0 = std::chrono::steady_clock::now();
+    if (b.boxes.resize(n * sizeof(BuildBox)) | b.centroids.resize(n * 12) | b.order.resize(n * 4) | b.seg.resize(n * 4) | b.order_tmp.resize(n * 4) | b.seg_tmp.resize(n * 4) |
+        b.ranges[0].resize(max_open * sizeof(BuildRange)) | b.ranges[1].resize(max_open * sizeof(BuildRange)) | b.acc.resize(max_long * ACC_WORDS * 4) | b.setup.resize(max_long * sizeof(BuildSetup)) |
+        b.split.resize(max_long * sizeof(BuildSplit)) | b.scan_local.resize(n * 4) | b.block_sums.resize(blocks * 4) | b.nodes.resize(n * sizeof(HiprBvhNode)) | b.sizes.resize(n * 4) |
+        b.place.resize(n * 4) | b.out_nodes.resize(n * sizeof(HiprBvhNode)) | b.status.resize(status_words * 4))
+        return HIPR_ERROR_OUT_OF_MEMORY;
+    if (int st = b.triangles.upload(triangles, n * sizeof(HiprTriangle), stream)) return st;
+    HIP_TRY(hipStreamSynchronize(stream));
+    const auto t1 = std::chrono::steady_clock::now();
+
+    BuildState S = {};
+    S.triangles = b.triangles.as<HiprTriangle>(); S.count = count; S.depth_limit = depth_limit;
+    S.boxes = b.boxes.as<BuildBox>(); S.centroids = b.centroids.as<float>();
+    S.order = b.order.as<uint32_t>(); S.seg = b.seg.as<uint32_t>(); S.order_tmp = b.order_tmp.as<uint32_t>(); S.seg_tmp = b.seg_tmp.as<uint32_t>();
+    S.acc = b.acc.as<uint32_t>(); S.setup = b.setup.as<BuildSetup>(); S.split = b.split.as<BuildSplit>();
+    S.scan_local = b.scan_local.as<uint32_t>(); S.block_sums = b.block_sums.as<uint32_t>();
+    S.nodes = b.nodes.as<HiprBvhNode>(); S.sizes = b.sizes.as<uint32_t>(); S.place = b.place.as<uint32_t>(); S.out_nodes = b.out_nodes.as<HiprBvhNode>();
+    S.status = b.status.as<uint32_t>();
+
+    std::vector<uint32_t> status(status_words, 0u);
+    status[STATUS_DECLINE] = status[STATUS_DECLINE + 1] = 0xFFFFFFFFu;
+    status[STATUS_LEVELS] = 1u;
+    status[STATUS_LEVELS + 1] = count > BUILD_SHORT_RANGE ? 1u : 0u;
+    HIP_TRY(hipMemcpyAsync(S.status, status.data(), status_words * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(S.nodes, 0, n * sizeof(HiprBvhNode), stream));
+    HIP_TRY(hipMemsetAsync(S.place, 0, 4, stream));
+    const dim3 block(BUILD_BLOCK), per_position{uint32_t(blocks)};
+    hipLaunchKernelGGL(k_build_prepare, per_position, block, 0, stream, S);
+    std::vector<uint32_t> level_nodes;      // the open ranges = new nodes of every level
+    uint32_t node_count = 1;
+    if (count <= BUILD_LEAF_MAX) hipLaunchKernelGGL(k_build_single_leaf, dim3(1), block, 0, stream, S);
+    else {
+        const BuildRange root = {0u, count, 1u, BUILD_NONE, count > BUILD_SHORT_RANGE ? 0u : BUILD_NONE, 0u};
+        HIP_TRY(hipMemcpyAsync(b.ranges[0].ptr, &root, sizeof(root), hipMemcpyHostToDevice, stream));
+        uint32_t open = 1, long_ranges = root.long_index == BUILD_NONE ? 0u : 1u, node_base = 0;
+        for (uint32_t level = 0; open; ++level) {
+            if (level >= max_levels || node_base + open > count - 1u || open > max_open - 2 || long_ranges > max_long - 2)
+                return fail(HIPR_ERROR_HIP, "hipr_build_bvh2: the build left its bounds at level %u (%u open ranges, %u nodes)", level, open, node_base);
+            const BuildLevel L = {b.ranges[level & 1u].as<BuildRange>(), b.ranges[(level + 1u) & 1u].as<BuildRange>(), open, node_base, level};
+            const dim3 per_range((open + BUILD_BLOCK - 1) / BUILD_BLOCK);
+            if (long_ranges) {
+                const uint64_t words = uint64_t(long_ranges) * ACC_WORDS;
+                hipLaunchKernelGGL(k_build_acc_init, dim3(uint32_t((words + BUILD_BLOCK - 1) / BUILD_BLOCK)), block, 0, stream, S.acc, words);
+                hipLaunchKernelGGL(k_build_bounds, per_position, block, 0, stream, S, L);
+                hipLaunchKernelGGL(k_build_range_setup, per_range, block, 0, stream, S, L);
+                hipLaunchKernelGGL(k_build_bins, per_position, block, 0, stream, S, L);
+                hipLaunchKernelGGL(k_build_split, per_range, block, 0, stream, S, L, 1);
+                hipLaunchKernelGGL(k_build_scan_local, per_position, block, 0, stream, S, L);
+                hipLaunchKernelGGL(k_build_scan_sums, dim3(1), block, 0, stream, S.block_sums, uint32_t(blocks));
+                hipLaunchKernelGGL(k_build_scatter, per_position, block, 0, stream, S, L);
+                hipLaunchKernelGGL(k_build_copy_back, per_position, block, 0, stream, S, L);
+                hipLaunchKernelGGL(k_build_leaves, per_range, block, 0, stream, S, L);
+            }
+            hipLaunchKernelGGL(k_build_split, per_range, block, 0, stream, S, L, 0);
+            HIP_TRY(hipMemcpyAsync(status.data(), S.status, (STATUS_LEVELS + 2 * size_t(level + 2)) * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (status[STATUS_DECLINE] != 0xFFFFFFFFu) {
+                b.levels = level + 1;
+                return fail(HIPR_ERROR_UNSUPPORTED, "hipr_build_bvh2: the range [%u, %u) of %u triangles at level %u takes the median path (the depth budget, or coincident centroids) and is longer than the %u a lane sorts; build on the host",
+                            status[STATUS_DECLINE + 1], status[STATUS_DECLINE], status[STATUS_DECLINE] - status[STATUS_DECLINE + 1], level, BUILD_MEDIAN_LANE_LIMIT);
+            }
+            level_nodes.push_back(open);
+            node_base += open;
+            open = status[STATUS_LEVELS + 2 * (level + 1)];
+            long_ranges = status[STATUS_LEVELS + 2 * (level + 1) + 1];
+        }
+        node_count = node_base;
+        std::vector<uint32_t> first(level_nodes.size());
+        for (size_t l = 0, at = 0; l < level_nodes.size(); at += level_nodes[l++]) first[l] = uint32_t(at);
+        for (size_t l = level_nodes.size(); l-- > 0;) hipLaunchKernelGGL(k_build_count, dim3((level_nodes[l] + BUILD_BLOCK - 1) / BUILD_BLOCK), block, 0, stream, S, first[l], level_nodes[l]);
+        for (size_t l = 0; l < level_nodes.size(); ++l) hipLaunchKernelGGL(k_build_place, dim3((level_nodes[l] + BUILD_BLOCK - 1) / BUILD_BLOCK), block, 0, stream, S, first[l], level_nodes[l]);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    const auto t2 = std::chrono::steady_clock::now();
+    if (node_count > node_capacity) return fail(HIPR_ERROR_HIP, "hipr_build_bvh2: %u nodes built, room for %u", node_count, node_capacity);
+    HIP_TRY(hipMemcpyAsync(status.data(), S.status, STATUS_LEVELS * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(out_nodes, S.out_nodes, size_t(node_count) * sizeof(HiprBvhNode), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(out_order, S.order, n * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *out_node_count = node_count;
+    *out_deepest = status[STATUS_DEEPEST];
+    const auto t3 = std::chrono::steady_clock::now();
+    b.validate_ms = std::chrono::duration<double, std::milli>(t0 - t_validate).count();
+    b.upload_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    b.kernel_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    b.readback_ms = std::chrono::duration<double, std::milli>(t3 - t2).count();
+    b.levels = uint32_t(level_nodes.size());
+    if (std::getenv("HIPR_BVH_TIMING"))
+        fprintf(stderr, "[hipr] hipr_build_bvh2: %u triangles, %u nodes, %u levels: argument checks %.3f ms, allocation + upload %.3f ms, kernels %.3f ms, read-back %.3f ms (transfers %.0f %% of %.3f ms)\n", count, node_count, b.levels,
+                b.validate_ms, b.upload_ms, b.kernel_ms, b.readback_ms, 100.0 * (b.upload_ms + b.readback_ms) / (b.validate_ms + b.upload_ms + b.kernel_ms + b.readback_ms),
+                b.validate_ms + b.upload_ms + b.kernel_ms + b.readback_ms);
+    return HIPR_OK;
+}
+
+int hipr_debug_build_times(HiprContext* c, double* out4_ms) {
+    if (!c || !out4_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_build_times: null argument");
+    out4_ms[0] = c->build.validate_ms; out4_ms[1] = c->build.upload_ms; out4_ms[2] = c->build.kernel_ms; out4_ms[3] = c->build.readback_ms;
+    return HIPR_OK;
 }
 
 int hipr_debug_read_scene_buffer(HiprContext* c, int which, void* out, uint64_t capacity_bytes) {

@@ -43,6 +43,12 @@ def load_host_library() -> C.CDLL:
     lib.hiprh_scene_camera.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_float, C.POINTER(capi.HiprCameraState)]
     lib.hiprh_bvh_build.argtypes = [C.POINTER(capi.HiprTriangle), C.c_uint, C.c_uint]
     lib.hiprh_bvh_build.restype = vp
+    lib.hiprh_bvh_build_on_device.argtypes = [vp, C.POINTER(capi.HiprTriangle), C.c_uint, C.c_uint, C.POINTER(C.c_int)]
+    lib.hiprh_bvh_build_on_device.restype = vp
+    lib.hiprh_bvh_median_splits.argtypes = [vp]; lib.hiprh_bvh_median_splits.restype = C.c_uint
+    lib.hiprh_bvh_longest_median_range.argtypes = [vp]; lib.hiprh_bvh_longest_median_range.restype = C.c_uint
+    lib.hiprh_scene_use_device_builder.argtypes = [vp, vp]
+    lib.hiprh_scene_build_counts.argtypes = [vp, C.POINTER(C.c_uint)]
     lib.hiprh_bvh_node_count.argtypes = [vp]; lib.hiprh_bvh_node_count.restype = C.c_uint
     lib.hiprh_bvh_max_depth.argtypes = [vp]; lib.hiprh_bvh_max_depth.restype = C.c_uint
     lib.hiprh_bvh_nodes.argtypes = [vp]; lib.hiprh_bvh_nodes.restype = C.POINTER(capi.HiprBvhNode)
@@ -85,7 +91,10 @@ def make_camera(width: int, height: int, position=(0.0, 0.0, 0.0), rotation=(0.0
 class Scene:
     """A flattened scene owned by the C++ host library (what handle_updates() would hand to hipr_upload_scene)."""
 
-    def __init__(self, name: str, diffuse_only: bool = False, param0: int = 0, param1: int = 0, environment: bool = False, coat: bool = False, spot: bool = False, textured: bool = False):
+    def __init__(self, name: str, diffuse_only: bool = False, param0: int = 0, param1: int = 0, environment: bool = False, coat: bool = False, spot: bool = False, textured: bool = False,
+                 device_builder=None):
+        """`device_builder`: a renderer.Context whose device builds the BVH2 of this scene (hipr_build_bvh2) -- the scene is rebuilt through it at once, and so is every
+        later rebuild; where the device declines, the host builds the same tree and build_counts() says so."""
         self.lib = load_host_library()
         if name.startswith("file:"):    # a model file set up the way SimpleViewer sets up its command-line scene
             self.handle = self.lib.hiprh_scene_load(name[5:].encode(), 1 if diffuse_only else 0)
@@ -96,6 +105,28 @@ class Scene:
             if not self.handle:
                 raise capi.HiprError(f"unknown scene '{name}'")
         self.name = name
+        self._device_builder = None
+        if device_builder is not None:
+            self.use_device_builder(device_builder)
+
+    def use_device_builder(self, context) -> bool:
+        """Installs (None: removes) the context's device build as the BVH2 stage and rebuilds through it. True when the device built the tree, False when the host did."""
+        if context is not None and not context.handle:
+            raise capi.HiprError("use_device_builder: the context is closed")
+        if self._device_builder is not None:
+            self._device_builder.forget_built_scene(self)
+        self._device_builder = context      # the scene's builds call into the context: keep it alive ...
+        if context is not None:
+            context.remember_built_scene(self)      # ... and have its close() take the source out of this scene first, so that a later rebuild() is the host's
+        status = self.lib.hiprh_scene_use_device_builder(self.handle, context.handle if context is not None else None)
+        if status < 0:
+            raise capi.HiprError("hiprh_scene_use_device_builder failed")
+        return status == 1
+
+    def build_counts(self) -> dict:
+        out = (C.c_uint * 3)()
+        self.lib.hiprh_scene_build_counts(self.handle, out)
+        return dict(device_builds=int(out[0]), declined_builds=int(out[1]), longest_median_range=int(out[2]))
 
     def __del__(self):
         if getattr(self, "handle", None):

@@ -96,11 +96,12 @@ struct Builder {
     std::vector<HiprBvhNode> nodes;
     uint32_t max_depth_limit;
     uint32_t deepest = 0;
+    uint32_t median_splits = 0, longest_median = 0;      // ranges split at the median, and the longest of them (BvhBuildResult::longest_median_range)
     unsigned threads = 1;                 // worker threads of the build (the top builder only)
     unsigned range_threads = 1;           // > 1: long ranges are binned and partitioned in this many slices (measured: beyond 8 the top levels get slower)
 
     // Subtrees handed to worker threads (top builder only): ranges at most `subtree_cutoff` long.
-    struct Task { uint32_t begin, end, depth; std::vector<HiprBvhNode> nodes; uint32_t deepest = 0; };
+    struct Task { uint32_t begin, end, depth; std::vector<HiprBvhNode> nodes; uint32_t deepest = 0, median_splits = 0, longest_median = 0; };
     std::vector<Task> tasks;
     uint32_t subtree_cutoff = 0;          // 0: build everything here
 
@@ -254,6 +255,8 @@ struct Builder {
         for (int a = 1; a < 3; ++a)
             if (cb.hi[a] - cb.lo[a] > cb.hi[axis] - cb.lo[axis]) axis = a;
         const uint32_t m = begin + count / 2;
+        ++median_splits;
+        longest_median = std::max(longest_median, count);
         std::stable_sort(order + begin, order + end, [&](uint32_t a, uint32_t b) { return centroids[3 * a + axis] < centroids[3 * b + axis]; });
         return m;
     }
@@ -283,7 +286,7 @@ struct Builder {
                 deepest = std::max(deepest, depth + 1);
             } else if (subtree_cutoff && e - b <= subtree_cutoff) {
                 store_child(scratch, c, box, SUBTREE_MARK | int32_t(tasks.size()));
-                tasks.push_back({b, e, depth + 1, {}, 0});
+                tasks.push_back({b, e, depth + 1, {}, 0, 0, 0});
             } else
                 store_child(scratch, c, box, int32_t(build(b, e, depth + 1)));
         }
@@ -303,8 +306,9 @@ struct Builder {
         }
     }
 
+    static unsigned threads_for(uint32_t n) { return n >= 2 * PARALLEL_RANGE ? build_threads() : 1u; }
     void build_all(uint32_t n) {
-        threads = n >= 2 * PARALLEL_RANGE ? build_threads() : 1u;
+        threads = threads_for(n);
         range_threads = std::min(threads, 8u);
         if (threads == 1) { nodes.reserve(n); build(0, n, 1); return; }
         subtree_cutoff = std::max<uint32_t>(n / (threads * 8u), 4096u);
@@ -325,6 +329,7 @@ struct Builder {
                 sub.build(task.begin, task.end, task.depth);
                 task.nodes = std::move(sub.nodes);
                 task.deepest = sub.deepest;
+                task.median_splits = sub.median_splits; task.longest_median = sub.longest_median;
             }
         };
         Failure failure;
@@ -334,7 +339,7 @@ struct Builder {
         for (std::thread& w : workers) w.join();
         failure.rethrow();
         const auto x2 = std::chrono::steady_clock::now();
-        for (const Task& task : tasks) deepest = std::max(deepest, task.deepest);
+        for (const Task& task : tasks) { deepest = std::max(deepest, task.deepest); median_splits += task.median_splits; longest_median = std::max(longest_median, task.longest_median); }
         std::vector<HiprBvhNode> top = std::move(nodes);
         std::vector<uint32_t> top_at(top.size()), task_at(tasks.size());
         uint32_t total = 0;
@@ -581,26 +586,23 @@ struct WideCollapse {
 
 } // namespace
 
-BvhBuildResult build_bvh(const std::vector<HiprTriangle>& triangles, uint32_t max_depth) {
-    BvhBuildResult result;
-    const uint32_t n = uint32_t(triangles.size());
-    result.max_depth = 0;
-    if (n == 0) return result;
+BvhBuildResult build_bvh(const std::vector<HiprTriangle>& triangles, uint32_t max_depth) { return build_bvh(triangles, max_depth, Bvh2Source(), nullptr); }
 
-    const auto t_start = std::chrono::steady_clock::now();
-    Builder b(triangles, std::max(max_depth, 8u));
+// The host's BVH2 stage: nodes, order and deepest leaf of the binned-SAH tree, left in `b` and `order`.
+static void build_bvh2_on_host(Builder& b, const std::vector<HiprTriangle>& triangles, std::vector<uint32_t>& order) {
+    const uint32_t n = uint32_t(triangles.size());
     std::vector<Box> boxes(n);
     std::vector<float> centroids(3 * size_t(n));
-    result.order.resize(n);
+    order.resize(n);
     for (uint32_t i = 0; i < n; ++i) {
         const HiprTriangle& t = triangles[i];
         Box& box = boxes[i];
         box.reset();
         box.grow(t.v0); box.grow(t.v1); box.grow(t.v2);
         for (int a = 0; a < 3; ++a) centroids[3 * i + a] = 0.5f * (box.lo[a] + box.hi[a]);
-        result.order[i] = i;
+        order[i] = i;
     }
-    b.boxes = boxes.data(); b.centroids = centroids.data(); b.order = result.order.data();
+    b.boxes = boxes.data(); b.centroids = centroids.data(); b.order = order.data();
 
     if (n <= LEAF_MAX) {
         // A single leaf: both children reference it (the duplicate test cannot change the result).
@@ -612,11 +614,45 @@ BvhBuildResult build_bvh(const std::vector<HiprTriangle>& triangles, uint32_t ma
         b.deepest = 1;
     } else
         b.build_all(n);
+    b.boxes = nullptr; b.centroids = nullptr; b.order = nullptr;
+}
+
+BvhBuildResult build_bvh(const std::vector<HiprTriangle>& triangles, uint32_t max_depth, const Bvh2Source& source, Bvh2SourceReport* report) {
+    BvhBuildResult result;
+    const uint32_t n = uint32_t(triangles.size());
+    result.max_depth = 0;
+    if (n == 0) return result;
+
+    const auto t_start = std::chrono::steady_clock::now();
+    Builder b(triangles, std::max(max_depth, 8u));
+    static const int reinsertion_passes = [] { const char* v = std::getenv("HIPR_BVH_REINSERTION"); return v ? std::atoi(v) : 0; }();
+    // The BVH2 stage from the caller's source, which builds THIS builder's default tree: a host configured away from it does not ask.
+    bool from_source = false;
+    if (source && LEAF_MAX == 3u && BIN_COUNT == 16 && reinsertion_passes <= 0) {
+        std::vector<HiprBvhNode> nodes(std::max(n, 2u) - 1u);
+        std::vector<uint32_t> order(n);
+        uint32_t node_count = 0, deepest = 0;
+        const int status = source.build(source.context, triangles.data(), n, max_depth, nodes.data(), uint32_t(nodes.size()), &node_count, order.data(), &deepest);
+        from_source = status == 0 && node_count >= 1 && node_count <= nodes.size();
+        if (report) { report->asked = true; report->status = status; report->used = from_source; report->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); }
+        if (from_source) {
+            nodes.resize(node_count);
+            b.nodes = std::move(nodes);
+            result.order = std::move(order);
+            b.deepest = deepest;
+            b.threads = Builder::threads_for(n);      // of the collapses below, as after the host's stage
+        } else if (report && !report->fall_back) return result;
+        if (std::getenv("HIPR_BVH_TIMING"))
+            fprintf(stderr, "[hipr] build_bvh: BVH2 source %s (status %d) after %.3f s\n", from_source ? "used" : "not used, the host builds", status, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count());
+    }
+    if (!from_source) {
+        build_bvh2_on_host(b, triangles, result.order);
+        result.median_splits = b.median_splits; result.longest_median_range = b.longest_median;
+    }
     // Insertion-based optimisation of the finished BVH2 (BvhOptimizer.h), opt-in: HIPR_BVH_REINSERTION = passes (3 converge), default 0. Measured in round 4
     // (profiles/r04_ab_bvh_reinsertion.txt): the binned-SAH tree of the atrium's evenly tessellated surfaces is close to a local optimum already -- 2 925 of
     // 375 k subtrees move, SAH cost -4.1 %, a closest-hit ray visits 14.3 nodes instead of 14.8 while a shadow ray tests 12.1 triangles instead of 10.9 -- and
     // the step times move by +1.0 % (atrium), -0.9 % (material scene), -0.6 % (1 M triangles): nothing to adopt. Sequential, so never beyond 4 M triangles.
-    static const int reinsertion_passes = [] { const char* v = std::getenv("HIPR_BVH_REINSERTION"); return v ? std::atoi(v) : 0; }();
     if (reinsertion_passes > 0 && n > LEAF_MAX && n <= 4000000u) {
         const ReinsertionStatistics stats = optimise_by_reinsertion(b.nodes, result.order, b.max_depth_limit, b.deepest, reinsertion_passes);
         if (std::getenv("HIPR_BVH_TIMING"))

@@ -18,10 +18,33 @@ struct BvhBuildResult {
     uint32_t wide_stack_entries = 0;  // most entries a traversal of wide_nodes can have on its stack
     // The same tree collapsed to the 8-wide slots of include/hiprenderer_c.h "wide8" (Wide8Builder.cpp): what the persistent kernels walk.
     Wide8Result wide8;
+    // Ranges the BVH2 stage split at the median (the depth budget, or coincident centroids) and the longest of them: what a device build (Bvh2Source) has to sort.
+    // Zero when a source built the BVH2.
+    uint32_t median_splits = 0, longest_median_range = 0;
+};
+
+// A BVH2 stage supplied by the caller in place of the host's binned-SAH builder: hipr_build_bvh2's signature behind a context pointer (csrc/bvh2_build.h builds
+// the host builder's tree byte for byte on the device). Returns HIPR_OK, or the status of a decline or an error, with the outputs untouched.
+struct Bvh2Source {
+    int (*build)(void* context, const HiprTriangle* triangles, uint32_t count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_node_count,
+                 uint32_t* out_order, uint32_t* out_deepest) = nullptr;
+    void* context = nullptr;
+    explicit operator bool() const { return build != nullptr; }
+};
+// What became of the source in one build_bvh. `fall_back` is the consumer's decision: true, a source that declines or fails is followed by the host's BVH2 stage and the
+// build carries on; false, build_bvh returns an empty result and the consumer hands `status` out.
+struct Bvh2SourceReport {
+    bool fall_back = true;
+    bool asked = false;          // the source was called (it is not when the host builder is configured away from leaf size 3 / 16 bins / no reinsertion)
+    bool used = false;           // ... and its tree is the result's
+    int status = 0;              // what it returned
+    double seconds = 0.0;        // ... and how long it took
 };
 
 // `max_depth`: the deepest leaf the builder may produce (root = 1). 62 fits the 64 entry LDS stack.
 BvhBuildResult build_bvh(const std::vector<HiprTriangle>& world_triangles, uint32_t max_depth = 62);
+// The same with the BVH2 stage taken from `source` when one is installed; the 4-wide collapse, the 8-wide collapse and max_depth go on from either tree alike.
+BvhBuildResult build_bvh(const std::vector<HiprTriangle>& world_triangles, uint32_t max_depth, const Bvh2Source& source, Bvh2SourceReport* report);
 
 // Transform-only update: refits every box of `bvh` (BVH2 child boxes and the wide nodes' quantised child boxes) to `triangles`, which are
 // the build's triangles in leaf order with new positions; topology and triangle order are kept. Returns bvh_child_area() of the result, or a negative value when

@@ -211,6 +211,7 @@ struct Renderer::Implementation {
     HiprSceneState scene_state = {{0, 0, 0}, 3};                     // next_event_sample_count = 3, OR/Renderer.cpp:479
     std::unique_ptr<SceneBuilder> scene;
     Renderer::SceneUpdateCounts scene_updates = {0, 0, 0, 0};
+    Renderer::SceneBuildCounts retired_builds = {0, 0};      // of the scene builders that are gone
 
     bool is_valid() const { return device_ID >= 0; }
 
@@ -261,8 +262,30 @@ struct Renderer::Implementation {
         for (uint32_t m = 0; m < hipr_group_size(group); ++m) hipr_set_arithmetic(hipr_group_context(group, m), arithmetic);
     }
 
+    // The scene builder goes; what it counted stays (scene_build_counts).
+    void retire_scene() {
+        if (scene) { retired_builds.device_builds += scene->build_counts().device_builds; retired_builds.declined_builds += scene->build_counts().declined_builds; }
+        scene.reset();
+    }
+
+    // hipr_group_build_bvh2 as the scene builders' BVH2 stage (SceneBuilder::set_bvh2_source). The source's context is this Implementation, never a camera's group:
+    // the group is picked when a build runs -- the first camera that has one NOW -- so a builder that outlives the camera it was first built on (a camera destroyed
+    // in handle_updates, a later transform tick that rebuilds) never calls into a destroyed group. With no camera context at that moment the host builds, and the
+    // build is counted as declined.
+    static int build_bvh2_on_a_live_group(void* implementation, const HiprTriangle* triangles, uint32_t count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity,
+                                          uint32_t* out_node_count, uint32_t* out_order, uint32_t* out_deepest) {
+        for (CameraState& c : static_cast<Implementation*>(implementation)->per_camera_state)
+            if (c.context) return hipr_group_build_bvh2(c.context, triangles, count, max_depth, out_nodes, node_capacity, out_node_count, out_order, out_deepest);
+        return HIPR_ERROR_NOT_READY;
+    }
+
     void rebuild_scene() {
+        retire_scene();
         scene.reset(new SceneBuilder());
+        // HIPR_DEVICE_BUILD=1: the BVH2 of every build of this scene builder comes from a camera's contexts (csrc/bvh2_build.h: the host builder's tree, byte for
+        // byte; where the device declines the host builds it). Off by default until profiles/device_build_vs_host.txt says otherwise.
+        const char* device_build = std::getenv("HIPR_DEVICE_BUILD");
+        if (device_build && std::atoi(device_build) != 0) scene->set_bvh2_source(Bvh2Source{build_bvh2_on_a_live_group, this});
         flatten_bifrost_scene(*scene);
         for (CameraState& c : per_camera_state) c.scene_uploaded = false;
     }
@@ -455,7 +478,7 @@ struct Renderer::Implementation {
                 }
             }
         }
-        if (scene_dirty) scene.reset();   // rebuilt lazily by the next render
+        if (scene_dirty) retire_scene();   // rebuilt lazily by the next render
         if (scene_dirty)
             for (CameraState& c : per_camera_state) c.scene_uploaded = false;
         if (should_reset_accumulations)
@@ -671,6 +694,11 @@ void Renderer::set_AI_denoiser_flags(AIDenoiserFlags flags) { m_impl->AI_denoise
 void Renderer::handle_updates() { m_impl->handle_updates(); }
 
 Renderer::SceneUpdateCounts Renderer::scene_update_counts() const { return m_impl->scene_updates; }
+Renderer::SceneBuildCounts Renderer::scene_build_counts() const {
+    SceneBuildCounts counts = m_impl->retired_builds;
+    if (m_impl->scene) { counts.device_builds += m_impl->scene->build_counts().device_builds; counts.declined_builds += m_impl->scene->build_counts().declined_builds; }
+    return counts;
+}
 
 unsigned int Renderer::render(CameraID camera_ID, void* half4_device_buffer, unsigned int buffer_pitch, Vector2i frame_size) {
     return m_impl->render(camera_ID, half4_device_buffer, buffer_pitch, frame_size);

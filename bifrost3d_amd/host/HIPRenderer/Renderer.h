@@ -100,6 +100,9 @@ public:
     // the resident scene (hipr_update_scene_materials).
     struct SceneUpdateCounts { unsigned int uploads, geometry_updates, device_refits, material_updates; };
     SceneUpdateCounts scene_update_counts() const;
+    // Scene builds whose BVH2 the device made (HIPR_DEVICE_BUILD=1, hipr_build_bvh2), and builds where it was asked and declined, so that the host built the tree.
+    struct SceneBuildCounts { unsigned int device_builds, declined_builds; };
+    SceneBuildCounts scene_build_counts() const;
 
 private:
     Renderer(const std::vector<int>& device_IDs, const std::filesystem::path& data_directory);

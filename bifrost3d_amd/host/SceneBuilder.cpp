@@ -3,6 +3,9 @@
 
 #include "../csrc/material_rules.h"      // the flag rules, shared with the kernels that apply a material edit on the device
 
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -172,6 +175,7 @@ void SceneBuilder::force_shading_model(uint16_t shading_model) {
 }
 
 void SceneBuilder::finalize(uint32_t bvh_max_depth) {
+    const auto t_start = std::chrono::steady_clock::now();
     std::vector<HiprTriangle> world;
     m_bounds = AABB::invalid();
     for (uint32_t i = 0; i < m_instances.size(); ++i) {
@@ -197,7 +201,13 @@ void SceneBuilder::finalize(uint32_t bvh_max_depth) {
     }
 
     m_bvh_max_depth_limit = bvh_max_depth;
-    m_bvh = build_bvh(world, bvh_max_depth);
+    const auto t_flat = std::chrono::steady_clock::now();
+    Bvh2SourceReport report;      // fall_back: a scene builder's build carries on with the host's stage
+    m_bvh = build_bvh(world, bvh_max_depth, m_bvh2_source, &report);
+    if (report.used) ++m_build_counts.device_builds; else if (report.asked) ++m_build_counts.declined_builds;
+    if (std::getenv("HIPR_BVH_TIMING"))
+        fprintf(stderr, "[hipr] finalize: %zu triangles: flatten %.3f s, build_bvh %.3f s (BVH2 source: %s, %.3f s)\n", world.size(), std::chrono::duration<double>(t_flat - t_start).count(),
+                std::chrono::duration<double>(std::chrono::steady_clock::now() - t_flat).count(), report.used ? "used" : (report.asked ? "declined" : "none"), report.seconds);
     m_built_bvh_area = bvh_child_area(m_bvh);
     m_triangles.resize(world.size());
     for (size_t k = 0; k < world.size(); ++k) m_triangles[k] = world[m_bvh.order[k]];

@@ -87,6 +87,13 @@ public:
     bool apply_staged_transforms(double rebuild_threshold = 1.5);
     bool has_staged_transforms() const { return m_staged; }
     void rebuild();
+    // The BVH2 stage of every later finalize() / rebuild() taken from `source` (hipr_build_bvh2 behind a context: the same tree, built on the device). A source that
+    // declines or fails is followed by the host's stage, silently: the scene is the same either way. Bvh2Source() removes it. build_counts(): builds whose BVH2 the
+    // source made, and builds where it was asked and the host built instead.
+    void set_bvh2_source(const Bvh2Source& source) { m_bvh2_source = source; }
+    struct BuildCounts { unsigned device_builds = 0, declined_builds = 0; };
+    BuildCounts build_counts() const { return m_build_counts; }
+    uint32_t longest_median_range() const { return m_bvh.longest_median_range; }
     // Material-only update after finalize(): `changed` rewrites material slots, `assignments` gives instances another material. The builder's own description is
     // kept in step WITHOUT a rebuild -- a material moves no corner and the tree builders read no flag, so the trees and the triangle order are the ones a rebuild
     // would make: the flags of the touched instances' triangles are recomputed (csrc/material_rules.h) and the leaf records of the 8-wide tree follow them. What
@@ -129,6 +136,8 @@ private:
     std::vector<uint32_t> m_instance_mesh;
     std::vector<HiprTriangle> m_triangles;
     BvhBuildResult m_bvh;
+    Bvh2Source m_bvh2_source;
+    BuildCounts m_build_counts;
     double m_built_bvh_area = 0.0;
     uint32_t m_bvh_max_depth_limit = 62;
     std::vector<float> m_environment_PDF;

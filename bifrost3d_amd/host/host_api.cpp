@@ -354,6 +354,29 @@ int hiprh_scene_rebuild(void* scene) {
     catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_rebuild: %s\n", e.what()); return -1; }
 }
 
+static int build_bvh2_on_context(void* context, const HiprTriangle* triangles, uint32_t count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_node_count,
+                                 uint32_t* out_order, uint32_t* out_deepest);
+// Installs hipr_build_bvh2 of `context` (NULL: removes it) as the BVH2 stage of the scene's builds and, with a context, rebuilds the scene through it. A decline
+// or a device error is silent here: the host's stage builds the same tree. Returns 1 when the device built the BVH2, 0 when the host did, -1 on error.
+int hiprh_scene_use_device_builder(void* scene, void* context) {
+    if (!scene) return -1;
+    SceneBuilder* sb = static_cast<SceneBuilder*>(scene);
+    try {
+        sb->set_bvh2_source(context ? Bvh2Source{build_bvh2_on_context, context} : Bvh2Source());
+        if (!context) return 0;
+        const unsigned before = sb->build_counts().device_builds;
+        sb->rebuild();
+        return sb->build_counts().device_builds > before ? 1 : 0;
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_use_device_builder: %s\n", e.what()); return -1; }
+}
+// out[0] = builds whose BVH2 the device made, out[1] = builds where it was asked and the host built instead, out[2] = the longest range the host's last BVH2 stage split at the median.
+int hiprh_scene_build_counts(void* scene, unsigned* out3) {
+    if (!scene || !out3) return -1;
+    const SceneBuilder* sb = static_cast<SceneBuilder*>(scene);
+    out3[0] = sb->build_counts().device_builds; out3[1] = sb->build_counts().declined_builds; out3[2] = sb->longest_median_range();
+    return 0;
+}
+
 // The builder's material and instance arrays (valid until the scene changes or is destroyed).
 const HiprMaterial* hiprh_scene_materials(void* scene, unsigned* out_count) {
     if (!scene || !out_count) return nullptr;
@@ -422,6 +445,31 @@ void* hiprh_bvh_build(const HiprTriangle* triangles, unsigned count, unsigned ma
         return h;
     } catch (const std::exception& e) { fprintf(stderr, "hiprh_bvh_build: %s\n", e.what()); delete h; return nullptr; }
 }
+// hipr_build_bvh2 as a Bvh2Source.
+static int build_bvh2_on_context(void* context, const HiprTriangle* triangles, uint32_t count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_node_count,
+                                 uint32_t* out_order, uint32_t* out_deepest) {
+    return hipr_build_bvh2(static_cast<HiprContext*>(context), triangles, count, max_depth, out_nodes, node_capacity, out_node_count, out_order, out_deepest);
+}
+// The same handle with the BVH2 stage built on the device by `context` (hipr_build_bvh2), the collapses on the host. NULL when the device declines or fails -- this entry
+// does not fall back: the status is in *out_status (HIPR_ERROR_UNSUPPORTED for a decline) and the message in hipr_last_error().
+void* hiprh_bvh_build_on_device(void* context, const HiprTriangle* triangles, unsigned count, unsigned max_depth, int* out_status) {
+    BvhHandle* h = nullptr;
+    if (out_status) *out_status = HIPR_ERROR_INVALID_ARGUMENT;
+    if (!context || !triangles || !count) return nullptr;
+    try {
+        std::vector<HiprTriangle> t(triangles, triangles + count);
+        h = new BvhHandle();
+        Bvh2SourceReport report;
+        report.fall_back = false;
+        h->result = build_bvh(t, max_depth, Bvh2Source{build_bvh2_on_context, context}, &report);
+        if (out_status) *out_status = report.asked ? report.status : HIPR_ERROR_UNSUPPORTED;      // not asked: the host builder is configured away from the device's tree
+        if (!report.used) { delete h; return nullptr; }
+        return h;
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_bvh_build_on_device: %s\n", e.what()); delete h; return nullptr; }
+}
+// Test-only counters of the host's BVH2 stage: the ranges it split at the median and the longest of them.
+unsigned hiprh_bvh_median_splits(void* h) { return static_cast<BvhHandle*>(h)->result.median_splits; }
+unsigned hiprh_bvh_longest_median_range(void* h) { return static_cast<BvhHandle*>(h)->result.longest_median_range; }
 unsigned hiprh_bvh_node_count(void* h) { return unsigned(static_cast<BvhHandle*>(h)->result.nodes.size()); }
 unsigned hiprh_bvh_max_depth(void* h) { return static_cast<BvhHandle*>(h)->result.max_depth; }
 const HiprBvhNode* hiprh_bvh_nodes(void* h) { return static_cast<BvhHandle*>(h)->result.nodes.data(); }

@@ -23,8 +23,21 @@ class Context:
         capi.check(self.lib, self.lib.hipr_upload_tables(self.handle, C.byref(t)), "hipr_upload_tables")
         self.frame = None
 
+    def remember_built_scene(self, scene):
+        """A host.Scene whose builds call hipr_build_bvh2 on this context (Scene.use_device_builder)."""
+        if not hasattr(self, "_built_scenes"):
+            import weakref
+            self._built_scenes = weakref.WeakSet()
+        self._built_scenes.add(scene)
+
+    def forget_built_scene(self, scene):
+        getattr(self, "_built_scenes", set()).discard(scene)
+
     def close(self):
         if self.handle:
+            for scene in list(getattr(self, "_built_scenes", ())):      # no scene keeps a destroyed context as the source of its builds
+                if getattr(scene, "handle", None):
+                    scene.use_device_builder(None)
             self.lib.hipr_destroy(self.handle)
             self.handle = C.c_void_p()
 
@@ -93,6 +106,26 @@ class Context:
         materials, assignments = list(materials), list(assignments)
         self._check(self.lib.hipr_update_scene_materials(self.handle, capi.material_updates(materials), len(materials), capi.instance_materials(assignments), len(assignments)),
                     "hipr_update_scene_materials")
+
+    def build_bvh2(self, triangles: np.ndarray, max_depth: int = 62, nodes: np.ndarray | None = None, order: np.ndarray | None = None):
+        """hipr_build_bvh2: the host builder's BVH2 of `triangles` ((n, 12) uint32 words of HiprTriangle) built on the device. Returns (status, nodes (node_count, 16) uint32,
+        order (n,) uint32, deepest leaf); on a status other than HIPR_OK the arrays are the caller's `nodes` / `order` (or zeros) as the call left them, whole."""
+        triangles = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 12)
+        n = len(triangles)
+        nodes = np.zeros((max(n - 1, 1), 16), np.uint32) if nodes is None else nodes
+        order = np.zeros(n, np.uint32) if order is None else order
+        node_count, deepest = C.c_uint32(0), C.c_uint32(0)
+        status = self.lib.hipr_build_bvh2(self.handle, C.cast(triangles.ctypes.data, C.POINTER(capi.HiprTriangle)), n, max_depth, C.cast(nodes.ctypes.data, C.POINTER(capi.HiprBvhNode)), len(nodes),
+                                          C.byref(node_count), C.cast(order.ctypes.data, C.POINTER(C.c_uint32)), C.byref(deepest))
+        if status != capi.HIPR_OK:
+            return status, nodes, order, 0
+        return status, nodes[:node_count.value], order, deepest.value
+
+    def build_times(self) -> dict:
+        """Milliseconds of the last build_bvh2: argument checks, allocation + upload, kernels, read-back."""
+        out = (C.c_double * 4)()
+        self._check(self.lib.hipr_debug_build_times(self.handle, out), "hipr_debug_build_times")
+        return dict(validate=out[0], upload=out[1], kernels=out[2], readback=out[3])
 
     def read_scene_buffer(self, which: int) -> np.ndarray:
         """The scene array the device holds (hipr_debug_read_scene_buffer): capi.SCENE_BUFFER_TRIANGLES -> (triangles, 12) uint32 words, SCENE_BUFFER_WIDE8_SLOTS -> (slots, 16),

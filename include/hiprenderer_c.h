@@ -386,6 +386,16 @@ typedef struct HiprMaterialUpdate   { uint32_t material_index; HiprMaterial mate
 typedef struct HiprInstanceMaterial { uint32_t instance_index; int32_t material_index; } HiprInstanceMaterial;
 int hipr_update_scene_materials(HiprContext* context, const HiprMaterialUpdate* materials, uint32_t material_count,
                                 const HiprInstanceMaterial* assignments, uint32_t assignment_count);
+/* The binned-SAH BVH2 of a triangle set built on the device (the reference asks OptiX for a "Trbvh" build, which runs on the GPU, OR/Renderer.cpp:161-182,471-476):
+ * byte for byte the nodes, triangle order and deepest leaf the host builder produces (csrc/bvh2_build.h), for the 4-wide and 8-wide collapses to go on from.
+ * Inputs and outputs are host pointers; `node_capacity` of max(count, 1) - 1, or 1, always suffices; max_depth below 8 is taken as 8, as the host builder does.
+ * The call owns its device scratch (about 240 B per triangle; up to 128 MiB it is kept with the context and reused, more is freed when the call returns), leaves the resident scene untouched and needs none. Checked before the device is touched:
+ *   HIPR_ERROR_INVALID_ARGUMENT   a null pointer, no triangles, too little room for the nodes, a corner that is not finite.
+ * A build that meets a range which takes the median path (the depth budget, or coincident centroids) and is longer than one lane sorts DECLINES: it returns
+ * HIPR_ERROR_UNSUPPORTED, writes nothing to the outputs and names the range in hipr_last_error(); the host builder serves such a set. */
+int hipr_build_bvh2(HiprContext* context, const HiprTriangle* triangles, uint32_t count, uint32_t max_depth,
+                    HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_node_count,
+                    uint32_t* out_order /* count words */, uint32_t* out_deepest);
 int hipr_set_scene_state(HiprContext* context, const HiprSceneState* state);
 
 /* Entry points, numbered like OR/Types.h:33-44. set_backend() of the host renderer maps Backend values onto them
@@ -467,6 +477,8 @@ int hipr_group_upload_scene(HiprGroup* group, const HiprSceneDesc* scene);
 int hipr_group_update_scene_geometry(HiprGroup* group, const HiprSceneDesc* scene);
 int hipr_group_refit_scene_transforms(HiprGroup* group, const HiprInstanceTransform* moved, uint32_t moved_count,
                                       const HiprLight* lights, uint32_t light_count, HiprRefitResult* out);   /* every member; their results must agree */
+int hipr_group_build_bvh2(HiprGroup* group, const HiprTriangle* triangles, uint32_t count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity,
+                          uint32_t* out_node_count, uint32_t* out_order, uint32_t* out_deepest);   /* builds on member 0 */
 int hipr_group_update_scene_materials(HiprGroup* group, const HiprMaterialUpdate* materials, uint32_t material_count,
                                       const HiprInstanceMaterial* assignments, uint32_t assignment_count);   /* every member checks before any member writes */
 int hipr_group_set_scene_state(HiprGroup* group, const HiprSceneState* state);
@@ -610,6 +622,9 @@ int hipr_debug_trace_shadow(HiprContext* context, const float* rays, uint32_t n,
 enum { HIPR_SCENE_BUFFER_TRIANGLES = 0, HIPR_SCENE_BUFFER_WIDE8_SLOTS = 1, HIPR_SCENE_BUFFER_TRACE_TRIANGLES = 2, HIPR_SCENE_BUFFER_SHADE_TRIANGLES = 3,
        HIPR_SCENE_BUFFER_TRIANGLE_CLASS = 4, HIPR_SCENE_BUFFER_MATERIALS = 5, HIPR_SCENE_BUFFER_INSTANCES = 6 };
 int hipr_debug_read_scene_buffer(HiprContext* context, int which, void* out, uint64_t capacity_bytes);
+/* Milliseconds of the context's last successful hipr_build_bvh2, which add up to the call: the argument checks (the pass over all corners for one that is not
+ * finite), scratch allocation + upload, kernels, read-back (tools/device_build_probe.py). */
+int hipr_debug_build_times(HiprContext* context, double* out4_ms);
 
 #ifdef __cplusplus
 }
