@@ -348,6 +348,13 @@ int hipr_group_build_bvh2(HiprGroup* g, const HiprTriangle* triangles, uint32_t 
     return hipr_build_bvh2(g->members[0].context, triangles, count, max_depth, out_nodes, node_capacity, out_node_count, out_order, out_deepest);
 }
 
+// The collapse of hipr_build_wide8 on member 0, as the BVH2 build above.
+int hipr_group_build_wide8(HiprGroup* g, const HiprBvhNode* nodes, uint32_t node_count, const HiprTriangle* triangles, const uint32_t* order, uint32_t triangle_count, HiprSlot8* out_slots,
+                           uint32_t slot_capacity, HiprWide8BuildResult* out) {
+    if (!g || g->members.empty()) return HIPR_ERROR_INVALID_ARGUMENT;
+    return hipr_build_wide8(g->members[0].context, nodes, node_count, triangles, order, triangle_count, out_slots, slot_capacity, out);
+}
+
 int hipr_group_update_scene_materials(HiprGroup* g, const HiprMaterialUpdate* materials, uint32_t material_count, const HiprInstanceMaterial* assignments, uint32_t assignment_count) {
     if (!g) return HIPR_ERROR_INVALID_ARGUMENT;
     // Every member checks before any member writes: an edit one member refuses leaves all of them as they were.

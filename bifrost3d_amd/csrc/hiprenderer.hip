@@ -16,6 +16,7 @@
 #include "wide8_refit.h"
 #include "material_update.h"
 #include "bvh2_build.h"
+#include "wide8_build.h"
 #include "launch.h"
 
 #include <hip/hip_runtime.h>
@@ -268,6 +269,22 @@ struct BuildScratch {
 // Gives a large build's scratch back on every way out of hipr_build_bvh2.
 struct BuildScratchGuard { BuildScratch& scratch; ~BuildScratchGuard() { scratch.release_if_large(); } };
 
+// The device scratch of hipr_build_wide8 (wide8_build.h), by the same rule: the input (48 B per triangle, 64 B per BVH2 node), about 170 B per record for the tree, its
+// tables and the records, 68 B per wide node and the slots.
+struct CollapseScratch {
+    DeviceBuffer nodes, triangles, order, level_nodes, counts, block_sums, partial, bounds, box, left, right, cost, split, roots_used, records, record_slot, wide_tree, wide_child, wide_all, wide_size,
+        wide_base, wide_slot, slots, status;
+    double validate_ms = 0.0, upload_ms = 0.0, kernel_ms = 0.0, readback_ms = 0.0;      // of the last collapse
+    void release_if_large() {
+        DeviceBuffer* all[] = {&nodes, &triangles, &order, &level_nodes, &counts, &block_sums, &partial, &bounds, &box, &left, &right, &cost, &split, &roots_used, &records, &record_slot, &wide_tree,
+                               &wide_child, &wide_all, &wide_size, &wide_base, &wide_slot, &slots, &status};
+        size_t total = 0;
+        for (const DeviceBuffer* b : all) total += b->bytes;
+        if (total > BuildScratch::KEEP_BYTES) for (DeviceBuffer* b : all) b->release();
+    }
+};
+struct CollapseScratchGuard { CollapseScratch& scratch; ~CollapseScratchGuard() { scratch.release_if_large(); } };
+
 } // namespace
 
 struct HiprContext {
@@ -357,6 +374,7 @@ struct HiprContext {
 
     DeviceBuffer debug_a, debug_b, debug_c;
     BuildScratch build;                 // hipr_build_bvh2; nothing of the resident scene
+    CollapseScratch collapse;           // hipr_build_wide8; likewise
 
     hipEvent_t next_event() {
         if (events_used == event_pool.size()) {
@@ -1792,6 +1810,139 @@ int hipr_build_bvh2(HiprContext* c, const HiprTriangle* triangles, uint32_t coun
 int hipr_debug_build_times(HiprContext* c, double* out4_ms) {
     if (!c || !out4_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_build_times: null argument");
     out4_ms[0] = c->build.validate_ms; out4_ms[1] = c->build.upload_ms; out4_ms[2] = c->build.kernel_ms; out4_ms[3] = c->build.readback_ms;
+    return HIPR_OK;
+}
+
+// The 8-wide tree of host/Wide8Builder.cpp collapsed from a BVH2 by the kernels of wide8_build.h. Nothing of the resident scene is read or written; the outputs are
+// written only once the whole collapse has succeeded.
+int hipr_build_wide8(HiprContext* c, const HiprBvhNode* nodes, uint32_t node_count, const HiprTriangle* triangles, const uint32_t* order, uint32_t triangle_count, HiprSlot8* out_slots,
+                     uint32_t slot_capacity, HiprWide8BuildResult* out) {
+    if (int st = check_context(c)) return st;
+    const auto t_validate = std::chrono::steady_clock::now();
+    if (!nodes || !node_count || !triangles || !triangle_count || !out_slots || !out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_wide8: null argument, no nodes or no triangles");
+    if (triangle_count > BUILD_MAX_TRIANGLES || node_count > BUILD_MAX_TRIANGLES) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_build_wide8: %u triangles and %u nodes, a leaf reference holds %u", triangle_count, node_count, BUILD_MAX_TRIANGLES);
+    W8Input input;
+    char reason[256] = "";
+    if (const int refused = w8_check_input(nodes, node_count, order, triangle_count, input, reason, sizeof(reason)))
+        return fail(refused == W8_INPUT_DECLINED ? HIPR_ERROR_UNSUPPORTED : HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_wide8: %s", reason);
+    const uint32_t reachable = uint32_t(input.level_nodes.size()), bvh_levels = uint32_t(input.level_first.size()) - 1u;
+    CollapseScratch& b = c->collapse;
+    const CollapseScratchGuard guard{b};
+    hipStream_t stream = c->stream;
+    c->break_chain(stream);
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t T = triangle_count, N = node_count, scan_blocks = (T + W8_BLOCK - 1) / W8_BLOCK;
+    if (b.counts.resize(T * 4) | b.block_sums.resize((scan_blocks + 1) * 4) | b.partial.resize(scan_blocks * 6 * sizeof(RefitBound)) | b.bounds.resize(6 * sizeof(RefitBound)) | b.status.resize(W8_STATUS_WORDS * 4))
+        return HIPR_ERROR_OUT_OF_MEMORY;
+    if (int st = b.nodes.upload(nodes, N * sizeof(HiprBvhNode), stream)) return st;
+    if (int st = b.triangles.upload(triangles, T * sizeof(HiprTriangle), stream)) return st;
+    if (order) if (int st = b.order.upload(order, T * 4, stream)) return st;
+    if (int st = b.level_nodes.upload(input.level_nodes.data(), size_t(reachable) * 4, stream)) return st;
+    HIP_TRY(hipMemsetAsync(b.counts.ptr, 0, T * 4, stream));
+    HIP_TRY(hipMemsetAsync(b.block_sums.ptr, 0, (scan_blocks + 1) * 4, stream));
+    HIP_TRY(hipMemsetAsync(b.status.ptr, 0, W8_STATUS_WORDS * 4, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const auto t1 = std::chrono::steady_clock::now();
+
+    W8State S = {};
+    S.nodes = b.nodes.as<HiprBvhNode>(); S.node_count = node_count;
+    S.triangles = b.triangles.as<HiprTriangle>(); S.order = order ? b.order.as<uint32_t>() : nullptr; S.triangle_count = triangle_count;
+    S.level_nodes = b.level_nodes.as<uint32_t>(); S.reachable = reachable; S.single_leaf = input.single_leaf ? 1u : 0u;
+    S.counts = b.counts.as<uint32_t>(); S.block_sums = b.block_sums.as<uint32_t>(); S.status = b.status.as<uint32_t>();
+    const dim3 block(W8_BLOCK), per_triangle{uint32_t(scan_blocks)}, per_reference((2u * reachable + W8_BLOCK - 1) / W8_BLOCK);
+    auto blocks_for = [](uint32_t threads) { return dim3((threads + W8_BLOCK - 1) / W8_BLOCK); };
+    // 1, 2: the bounds and the record numbers; the host reads both together
+    hipLaunchKernelGGL(k_w8_bounds, per_triangle, block, 0, stream, S.triangles, triangle_count, b.partial.as<RefitBound>(), S.status);
+    hipLaunchKernelGGL(k_refit_bounds_final, dim3(1), block, 0, stream, b.partial.as<RefitBound>(), uint32_t(scan_blocks), b.bounds.as<RefitBound>());
+    hipLaunchKernelGGL(k_w8_count_leaf, per_reference, block, 0, stream, S);
+    hipLaunchKernelGGL(k_w8_scan_local, per_triangle, block, 0, stream, S);
+    hipLaunchKernelGGL(k_build_scan_sums, dim3(1), block, 0, stream, S.block_sums, uint32_t(scan_blocks + 1));
+    RefitBound bounds[6];
+    uint32_t record_total = 0, not_finite = 0;
+    HIP_TRY(hipMemcpyAsync(bounds, b.bounds.ptr, sizeof(bounds), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&record_total, S.block_sums + scan_blocks, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&not_finite, S.status + W8_STATUS_NOT_FINITE, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (not_finite) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_wide8: a triangle corner or a child box is not finite");
+    if (record_total == 0 || record_total > triangle_count) return fail(HIPR_ERROR_HIP, "hipr_build_wide8: %u records of %u triangles", record_total, triangle_count);
+    HiprWide8BuildResult result = {};
+    {
+        const float lo[3] = {bounds[0].v, bounds[1].v, bounds[2].v}, hi[3] = {bounds[3].v, bounds[4].v, bounds[5].v};
+        refit_grid(lo, hi, result.grid_min, result.grid_cell);
+        for (int a = 0; a < 3; ++a) { S.grid_min[a] = result.grid_min[a]; S.grid_cell[a] = result.grid_cell[a]; }
+    }
+    // 3, 4: the tree over the records and its dynamic program
+    const size_t R = record_total, inner = N + R, wide_capacity = R;
+    if (b.box.resize((inner + R) * sizeof(RefitBox)) | b.left.resize(inner * 4) | b.right.resize(inner * 4) | b.cost.resize(inner * 28) | b.split.resize(inner * 7) | b.roots_used.resize(inner * 7) |
+        b.records.resize(R * sizeof(HiprLeaf8)) | b.record_slot.resize(R * 4) | b.wide_tree.resize(wide_capacity * 4) | b.wide_child.resize(wide_capacity * 32) | b.wide_all.resize(wide_capacity * sizeof(RefitBox)) |
+        b.wide_size.resize(wide_capacity * 4) | b.wide_base.resize(wide_capacity * 4) | b.wide_slot.resize(wide_capacity * 4))
+        return HIPR_ERROR_OUT_OF_MEMORY;
+    S.record_total = record_total; S.leaf_base = uint32_t(inner); S.wide_capacity = uint32_t(wide_capacity);
+    S.box = b.box.as<RefitBox>(); S.left = b.left.as<int32_t>(); S.right = b.right.as<int32_t>(); S.cost = b.cost.as<float>(); S.split = b.split.as<uint8_t>(); S.roots_used = b.roots_used.as<uint8_t>();
+    S.records = b.records.as<HiprLeaf8>(); S.record_slot = b.record_slot.as<uint32_t>();
+    S.wide_tree = b.wide_tree.as<uint32_t>(); S.wide_child = b.wide_child.as<int32_t>(); S.wide_all = b.wide_all.as<RefitBox>();
+    S.wide_size = b.wide_size.as<uint32_t>(); S.wide_base = b.wide_base.as<uint32_t>(); S.wide_slot = b.wide_slot.as<uint32_t>();
+    hipLaunchKernelGGL(k_w8_leaf, per_reference, block, 0, stream, S);
+    if (!input.single_leaf)
+        for (uint32_t l = bvh_levels; l-- > 0;) {
+            const uint32_t first = input.level_first[l], count = input.level_first[l + 1] - first;
+            hipLaunchKernelGGL(k_w8_optimise, blocks_for(count), block, 0, stream, S, first, count);
+        }
+    // 5: the wide nodes, level by level
+    std::vector<uint32_t> wide_first, wide_count;
+    uint32_t status[W8_STATUS_WORDS] = {};
+    for (uint32_t level = 0, first = 0, count = 1; count; ++level) {
+        if (level >= W8_MAX_WIDE_LEVELS || size_t(first) + count > wide_capacity) return fail(HIPR_ERROR_HIP, "hipr_build_wide8: the collapse left its bounds at wide level %u (%u nodes from %u, room for %zu)", level, count, first, wide_capacity);
+        hipLaunchKernelGGL(k_w8_prepare, blocks_for(count), block, 0, stream, S, first, count, level);
+        HIP_TRY(hipMemcpyAsync(status, S.status, (W8_STATUS_LEVELS + level + 2) * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (status[W8_STATUS_OVERFLOW]) return fail(HIPR_ERROR_HIP, "hipr_build_wide8: more wide nodes than a tree over %u records holds", record_total);
+        wide_first.push_back(first); wide_count.push_back(count);
+        first += count;
+        count = status[W8_STATUS_LEVELS + level + 1];
+    }
+    const uint32_t wide_total = wide_first.back() + wide_count.back(), wide_levels = uint32_t(wide_first.size());
+    // 6: the sizes; the slots needed are known before one is written
+    for (uint32_t l = wide_levels; l-- > 0;) hipLaunchKernelGGL(k_w8_size, blocks_for(wide_count[l]), block, 0, stream, S, wide_first[l], wide_count[l]);
+    uint32_t size_below_root = 0;
+    HIP_TRY(hipMemcpyAsync(&size_below_root, S.wide_size, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const uint64_t slot_count = 1ull + size_below_root;
+    if (slot_count != uint64_t(wide_total) + record_total) return fail(HIPR_ERROR_HIP, "hipr_build_wide8: %llu slots below the root, %u nodes and %u records", (unsigned long long)slot_count, wide_total, record_total);
+    if (slot_count > W8_MAX_SLOTS) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_build_wide8: the tree needs %llu slots, a node addresses %u", (unsigned long long)slot_count, W8_MAX_SLOTS);
+    if (slot_count > slot_capacity) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_wide8: the tree needs %llu slots, room for %u", (unsigned long long)slot_count, slot_capacity);
+    if (b.slots.resize(size_t(slot_count) * sizeof(HiprSlot8))) return HIPR_ERROR_OUT_OF_MEMORY;
+    S.slots = b.slots.as<HiprSlot8>();
+    // 7, 8: the places, then the slots
+    const uint32_t root_place[2] = {0u, 1u};
+    HIP_TRY(hipMemcpyAsync(S.wide_slot, &root_place[0], 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(S.wide_base, &root_place[1], 4, hipMemcpyHostToDevice, stream));
+    for (uint32_t l = 0; l < wide_levels; ++l) hipLaunchKernelGGL(k_w8_place, blocks_for(wide_count[l]), block, 0, stream, S, wide_first[l], wide_count[l]);
+    hipLaunchKernelGGL(k_w8_emit_nodes, blocks_for(wide_total), block, 0, stream, S, wide_total);
+    hipLaunchKernelGGL(k_w8_emit_leaves, blocks_for(record_total), block, 0, stream, S);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    const auto t2 = std::chrono::steady_clock::now();
+    HIP_TRY(hipMemcpyAsync(out_slots, S.slots, size_t(slot_count) * sizeof(HiprSlot8), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    result.slot_count = uint32_t(slot_count);
+    result.height = wide_levels;
+    result.node_count = wide_total; result.leaf_count = record_total; result.paired_leaves = status[W8_STATUS_PAIRED];
+    *out = result;
+    const auto t3 = std::chrono::steady_clock::now();
+    b.validate_ms = std::chrono::duration<double, std::milli>(t0 - t_validate).count();
+    b.upload_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    b.kernel_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    b.readback_ms = std::chrono::duration<double, std::milli>(t3 - t2).count();
+    if (std::getenv("HIPR_BVH_TIMING"))
+        fprintf(stderr, "[hipr] hipr_build_wide8: %u triangles, %u BVH2 nodes on %u levels, %u records, %u wide nodes on %u levels, %u slots: index walk %.3f ms, allocation + upload %.3f ms, kernels %.3f ms, read-back %.3f ms\n",
+                triangle_count, node_count, bvh_levels, record_total, wide_total, wide_levels, result.slot_count, b.validate_ms, b.upload_ms, b.kernel_ms, b.readback_ms);
+    return HIPR_OK;
+}
+
+int hipr_debug_collapse_times(HiprContext* c, double* out4_ms) {
+    if (!c || !out4_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_collapse_times: null argument");
+    out4_ms[0] = c->collapse.validate_ms; out4_ms[1] = c->collapse.upload_ms; out4_ms[2] = c->collapse.kernel_ms; out4_ms[3] = c->collapse.readback_ms;
     return HIPR_OK;
 }
 

@@ -49,6 +49,7 @@ def load_host_library() -> C.CDLL:
     lib.hiprh_bvh_longest_median_range.argtypes = [vp]; lib.hiprh_bvh_longest_median_range.restype = C.c_uint
     lib.hiprh_scene_use_device_builder.argtypes = [vp, vp]
     lib.hiprh_scene_build_counts.argtypes = [vp, C.POINTER(C.c_uint)]
+    lib.hiprh_scene_collapse_counts.argtypes = [vp, C.POINTER(C.c_uint)]
     lib.hiprh_bvh_node_count.argtypes = [vp]; lib.hiprh_bvh_node_count.restype = C.c_uint
     lib.hiprh_bvh_max_depth.argtypes = [vp]; lib.hiprh_bvh_max_depth.restype = C.c_uint
     lib.hiprh_bvh_nodes.argtypes = [vp]; lib.hiprh_bvh_nodes.restype = C.POINTER(capi.HiprBvhNode)
@@ -56,6 +57,13 @@ def load_host_library() -> C.CDLL:
     lib.hiprh_bvh_wide_node_count.argtypes = [vp]; lib.hiprh_bvh_wide_node_count.restype = C.c_uint
     lib.hiprh_bvh_wide_stack_entries.argtypes = [vp]; lib.hiprh_bvh_wide_stack_entries.restype = C.c_uint
     lib.hiprh_bvh_wide_nodes.argtypes = [vp]; lib.hiprh_bvh_wide_nodes.restype = C.POINTER(capi.HiprWideNode)
+    lib.hiprh_bvh_wide8_slots.argtypes = [vp]; lib.hiprh_bvh_wide8_slots.restype = vp
+    lib.hiprh_bvh_wide8_slot_count.argtypes = [vp]; lib.hiprh_bvh_wide8_slot_count.restype = C.c_uint
+    lib.hiprh_bvh_wide8_height.argtypes = [vp]; lib.hiprh_bvh_wide8_height.restype = C.c_uint
+    lib.hiprh_bvh_wide8_grid.argtypes = [vp, C.POINTER(C.c_float)]; lib.hiprh_bvh_wide8_grid.restype = None
+    lib.hiprh_bvh_wide8_counts.argtypes = [vp, C.POINTER(C.c_uint)]; lib.hiprh_bvh_wide8_counts.restype = None
+    lib.hiprh_wide8_build_on_device.argtypes = [vp, vp, C.c_uint, vp, vp, C.c_uint, C.POINTER(C.c_int)]
+    lib.hiprh_wide8_build_on_device.restype = vp
     lib.hiprh_pmjbn_samples.argtypes = [C.POINTER(C.c_float), C.c_uint, C.c_uint]
     lib.hiprh_bvh_destroy.argtypes = [vp]
     lib.hiprh_renderer_bench.argtypes = [C.c_char_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_double)]
@@ -93,8 +101,9 @@ class Scene:
 
     def __init__(self, name: str, diffuse_only: bool = False, param0: int = 0, param1: int = 0, environment: bool = False, coat: bool = False, spot: bool = False, textured: bool = False,
                  device_builder=None):
-        """`device_builder`: a renderer.Context whose device builds the BVH2 of this scene (hipr_build_bvh2) -- the scene is rebuilt through it at once, and so is every
-        later rebuild; where the device declines, the host builds the same tree and build_counts() says so."""
+        """`device_builder`: a renderer.Context whose device builds the BVH2 of this scene (hipr_build_bvh2) and collapses it to the 8-wide tree (hipr_build_wide8, unless
+        HIPR_DEVICE_COLLAPSE=0) -- the scene is rebuilt through it at once, and so is every later rebuild; where the device declines a stage, the host builds the same
+        tree and build_counts() / collapse_counts() say so."""
         self.lib = load_host_library()
         if name.startswith("file:"):    # a model file set up the way SimpleViewer sets up its command-line scene
             self.handle = self.lib.hiprh_scene_load(name[5:].encode(), 1 if diffuse_only else 0)
@@ -127,6 +136,12 @@ class Scene:
         out = (C.c_uint * 3)()
         self.lib.hiprh_scene_build_counts(self.handle, out)
         return dict(device_builds=int(out[0]), declined_builds=int(out[1]), longest_median_range=int(out[2]))
+
+    def collapse_counts(self) -> dict:
+        """Builds whose 8-wide tree the device collapsed, and builds where it was asked and the host collapsed instead."""
+        out = (C.c_uint * 2)()
+        self.lib.hiprh_scene_collapse_counts(self.handle, out)
+        return dict(device_collapses=int(out[0]), declined_collapses=int(out[1]))
 
     def __del__(self):
         if getattr(self, "handle", None):

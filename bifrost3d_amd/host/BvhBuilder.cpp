@@ -618,6 +618,42 @@ static void build_bvh2_on_host(Builder& b, const std::vector<HiprTriangle>& tria
 }
 
 BvhBuildResult build_bvh(const std::vector<HiprTriangle>& triangles, uint32_t max_depth, const Bvh2Source& source, Bvh2SourceReport* report) {
+    return build_bvh(triangles, max_depth, source, report, Wide8Source(), nullptr);
+}
+
+// The default follows profiles/device_collapse_vs_host.txt.
+static constexpr bool DEVICE_COLLAPSE_DEFAULT = true;
+bool device_collapse_wanted() {
+    const char* v = std::getenv("HIPR_DEVICE_COLLAPSE");
+    return v ? std::atoi(v) != 0 : DEVICE_COLLAPSE_DEFAULT;
+}
+
+// The 8-wide collapse from the caller's source, which collapses to build_wide8's DEFAULT tree: a host configured away from it does not ask. false: build_wide8 serves.
+static bool wide8_from_source(const Wide8Source& source, Wide8SourceReport* report, const std::vector<HiprBvhNode>& nodes, const std::vector<HiprTriangle>& triangles, const std::vector<uint32_t>& order,
+                              Wide8Result& wide8) {
+    if (!source || nodes.empty() || std::getenv("HIPR_WIDE8_LEAF_COST") || std::getenv("HIPR_WIDE8_LAYOUT")) return false;
+    const auto t_start = std::chrono::steady_clock::now();
+    const uint32_t n = uint32_t(triangles.size());
+    // at most one record per triangle and fewer nodes than records; the pages of this room are touched only where the source writes
+    const uint32_t capacity = uint32_t(std::min<uint64_t>(2ull * n, 0xFFFFFFull));
+    struct Room { HiprSlot8* slots; ~Room() { std::free(slots); } } room = {static_cast<HiprSlot8*>(std::malloc(size_t(capacity) * sizeof(HiprSlot8)))};
+    HiprWide8BuildResult built = {};
+    const int status = room.slots ? source.build(source.context, nodes.data(), uint32_t(nodes.size()), triangles.data(), order.data(), n, room.slots, capacity, &built) : HIPR_ERROR_OUT_OF_MEMORY;
+    const bool used = status == 0 && built.slot_count >= 1 && built.slot_count <= capacity;
+    if (used) {
+        wide8.slots.assign(room.slots, room.slots + built.slot_count);
+        wide8.height = built.height;
+        for (int a = 0; a < 3; ++a) { wide8.grid_min[a] = built.grid_min[a]; wide8.grid_cell[a] = built.grid_cell[a]; }
+        wide8.node_count = built.node_count; wide8.leaf_count = built.leaf_count; wide8.paired_leaves = built.paired_leaves;
+    }
+    const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+    if (report) { report->asked = true; report->status = status; report->used = used; report->seconds = seconds; }
+    if (std::getenv("HIPR_BVH_TIMING")) fprintf(stderr, "[hipr] build_bvh: 8-wide source %s (status %d) after %.3f s\n", used ? "used" : "not used, the host collapses", status, seconds);
+    return used;
+}
+
+BvhBuildResult build_bvh(const std::vector<HiprTriangle>& triangles, uint32_t max_depth, const Bvh2Source& source, Bvh2SourceReport* report, const Wide8Source& wide8_source,
+                         Wide8SourceReport* wide8_report) {
     BvhBuildResult result;
     const uint32_t n = uint32_t(triangles.size());
     result.max_depth = 0;
@@ -670,7 +706,8 @@ BvhBuildResult build_bvh(const std::vector<HiprTriangle>& triangles, uint32_t ma
     result.wide_nodes = std::move(collapse.wide);
     result.max_depth = b.deepest + 1;   // stack entries needed is bounded by the node depth; keep one spare
     const auto t_wide = std::chrono::steady_clock::now();
-    result.wide8 = build_wide8(result.nodes, OrderedTriangles{triangles.data(), result.order.data(), n});
+    if (!wide8_from_source(wide8_source, wide8_report, result.nodes, triangles, result.order, result.wide8))
+        result.wide8 = build_wide8(result.nodes, OrderedTriangles{triangles.data(), result.order.data(), n});
     if (std::getenv("HIPR_BVH_TIMING")) {
         const auto t_end = std::chrono::steady_clock::now();
         fprintf(stderr, "[hipr] build_bvh: %u triangles, %u threads: BVH2 %.3f s, 4-wide collapse %.3f s, 8-wide collapse %.3f s (%u nodes, %u leaf records of which %u hold two triangles, height %u)\n", n,

@@ -41,10 +41,32 @@ struct Bvh2SourceReport {
     double seconds = 0.0;        // ... and how long it took
 };
 
+// The 8-wide collapse supplied by the caller in place of build_wide8: hipr_build_wide8's signature behind a context pointer (csrc/wide8_build.h collapses to the host's
+// tree byte for byte on the device, in the default configuration only). Returns HIPR_OK, or the status of a decline or an error, with the outputs untouched.
+struct Wide8Source {
+    int (*build)(void* context, const HiprBvhNode* nodes, uint32_t node_count, const HiprTriangle* triangles, const uint32_t* order, uint32_t triangle_count, HiprSlot8* out_slots,
+                 uint32_t slot_capacity, HiprWide8BuildResult* out) = nullptr;
+    void* context = nullptr;
+    explicit operator bool() const { return build != nullptr; }
+};
+// What became of it in one build_bvh. A source that declines or fails is always followed by build_wide8, silently: the tree is the same either way.
+struct Wide8SourceReport {
+    bool asked = false;          // the source was called (it is not when HIPR_WIDE8_LEAF_COST or HIPR_WIDE8_LAYOUT configure the host's collapse away from its default)
+    bool used = false;           // ... and its tree is the result's
+    int status = 0;              // what it returned
+    double seconds = 0.0;        // ... and how long it took
+};
+
+// Whether a consumer that installs a Bvh2Source installs the Wide8Source with it: HIPR_DEVICE_COLLAPSE (0: the host collapses), else DEVICE_COLLAPSE_DEFAULT.
+bool device_collapse_wanted();
+
 // `max_depth`: the deepest leaf the builder may produce (root = 1). 62 fits the 64 entry LDS stack.
 BvhBuildResult build_bvh(const std::vector<HiprTriangle>& world_triangles, uint32_t max_depth = 62);
 // The same with the BVH2 stage taken from `source` when one is installed; the 4-wide collapse, the 8-wide collapse and max_depth go on from either tree alike.
 BvhBuildResult build_bvh(const std::vector<HiprTriangle>& world_triangles, uint32_t max_depth, const Bvh2Source& source, Bvh2SourceReport* report);
+// ... and the 8-wide collapse from `wide8_source` when one is installed.
+BvhBuildResult build_bvh(const std::vector<HiprTriangle>& world_triangles, uint32_t max_depth, const Bvh2Source& source, Bvh2SourceReport* report, const Wide8Source& wide8_source,
+                         Wide8SourceReport* wide8_report);
 
 // Transform-only update: refits every box of `bvh` (BVH2 child boxes and the wide nodes' quantised child boxes) to `triangles`, which are
 // the build's triangles in leaf order with new positions; topology and triangle order are kept. Returns bvh_child_area() of the result, or a negative value when

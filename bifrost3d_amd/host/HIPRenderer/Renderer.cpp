@@ -212,6 +212,7 @@ struct Renderer::Implementation {
     std::unique_ptr<SceneBuilder> scene;
     Renderer::SceneUpdateCounts scene_updates = {0, 0, 0, 0};
     Renderer::SceneBuildCounts retired_builds = {0, 0};      // of the scene builders that are gone
+    Renderer::SceneCollapseCounts retired_collapses = {0, 0};
 
     bool is_valid() const { return device_ID >= 0; }
 
@@ -264,7 +265,10 @@ struct Renderer::Implementation {
 
     // The scene builder goes; what it counted stays (scene_build_counts).
     void retire_scene() {
-        if (scene) { retired_builds.device_builds += scene->build_counts().device_builds; retired_builds.declined_builds += scene->build_counts().declined_builds; }
+        if (scene) {
+            retired_builds.device_builds += scene->build_counts().device_builds; retired_builds.declined_builds += scene->build_counts().declined_builds;
+            retired_collapses.device_collapses += scene->collapse_counts().device_collapses; retired_collapses.declined_collapses += scene->collapse_counts().declined_collapses;
+        }
         scene.reset();
     }
 
@@ -279,13 +283,25 @@ struct Renderer::Implementation {
         return HIPR_ERROR_NOT_READY;
     }
 
+    // hipr_group_build_wide8 as their 8-wide collapse (SceneBuilder::set_wide8_source), by the same rule.
+    static int build_wide8_on_a_live_group(void* implementation, const HiprBvhNode* nodes, uint32_t node_count, const HiprTriangle* triangles, const uint32_t* order, uint32_t triangle_count,
+                                           HiprSlot8* out_slots, uint32_t slot_capacity, HiprWide8BuildResult* out) {
+        for (CameraState& c : static_cast<Implementation*>(implementation)->per_camera_state)
+            if (c.context) return hipr_group_build_wide8(c.context, nodes, node_count, triangles, order, triangle_count, out_slots, slot_capacity, out);
+        return HIPR_ERROR_NOT_READY;
+    }
+
     void rebuild_scene() {
         retire_scene();
         scene.reset(new SceneBuilder());
         // HIPR_DEVICE_BUILD=1: the BVH2 of every build of this scene builder comes from a camera's contexts (csrc/bvh2_build.h: the host builder's tree, byte for
         // byte; where the device declines the host builds it). Off by default until profiles/device_build_vs_host.txt says otherwise.
         const char* device_build = std::getenv("HIPR_DEVICE_BUILD");
-        if (device_build && std::atoi(device_build) != 0) scene->set_bvh2_source(Bvh2Source{build_bvh2_on_a_live_group, this});
+        if (device_build && std::atoi(device_build) != 0) {
+            scene->set_bvh2_source(Bvh2Source{build_bvh2_on_a_live_group, this});
+            // ... and the 8-wide collapse with it (csrc/wide8_build.h, likewise byte for byte) unless HIPR_DEVICE_COLLAPSE=0 keeps it on the host.
+            if (device_collapse_wanted()) scene->set_wide8_source(Wide8Source{build_wide8_on_a_live_group, this});
+        }
         flatten_bifrost_scene(*scene);
         for (CameraState& c : per_camera_state) c.scene_uploaded = false;
     }
@@ -694,6 +710,11 @@ void Renderer::set_AI_denoiser_flags(AIDenoiserFlags flags) { m_impl->AI_denoise
 void Renderer::handle_updates() { m_impl->handle_updates(); }
 
 Renderer::SceneUpdateCounts Renderer::scene_update_counts() const { return m_impl->scene_updates; }
+Renderer::SceneCollapseCounts Renderer::scene_collapse_counts() const {
+    SceneCollapseCounts counts = m_impl->retired_collapses;
+    if (m_impl->scene) { counts.device_collapses += m_impl->scene->collapse_counts().device_collapses; counts.declined_collapses += m_impl->scene->collapse_counts().declined_collapses; }
+    return counts;
+}
 Renderer::SceneBuildCounts Renderer::scene_build_counts() const {
     SceneBuildCounts counts = m_impl->retired_builds;
     if (m_impl->scene) { counts.device_builds += m_impl->scene->build_counts().device_builds; counts.declined_builds += m_impl->scene->build_counts().declined_builds; }

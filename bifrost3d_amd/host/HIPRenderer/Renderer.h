@@ -103,6 +103,9 @@ public:
     // Scene builds whose BVH2 the device made (HIPR_DEVICE_BUILD=1, hipr_build_bvh2), and builds where it was asked and declined, so that the host built the tree.
     struct SceneBuildCounts { unsigned int device_builds, declined_builds; };
     SceneBuildCounts scene_build_counts() const;
+    // The same for the 8-wide collapse (hipr_build_wide8; HIPR_DEVICE_COLLAPSE=0 keeps it on the host under HIPR_DEVICE_BUILD=1).
+    struct SceneCollapseCounts { unsigned int device_collapses, declined_collapses; };
+    SceneCollapseCounts scene_collapse_counts() const;
 
 private:
     Renderer(const std::vector<int>& device_IDs, const std::filesystem::path& data_directory);

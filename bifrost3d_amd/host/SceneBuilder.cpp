@@ -203,8 +203,10 @@ void SceneBuilder::finalize(uint32_t bvh_max_depth) {
     m_bvh_max_depth_limit = bvh_max_depth;
     const auto t_flat = std::chrono::steady_clock::now();
     Bvh2SourceReport report;      // fall_back: a scene builder's build carries on with the host's stage
-    m_bvh = build_bvh(world, bvh_max_depth, m_bvh2_source, &report);
+    Wide8SourceReport wide8_report;
+    m_bvh = build_bvh(world, bvh_max_depth, m_bvh2_source, &report, m_wide8_source, &wide8_report);
     if (report.used) ++m_build_counts.device_builds; else if (report.asked) ++m_build_counts.declined_builds;
+    if (wide8_report.used) ++m_collapse_counts.device_collapses; else if (wide8_report.asked) ++m_collapse_counts.declined_collapses;
     if (std::getenv("HIPR_BVH_TIMING"))
         fprintf(stderr, "[hipr] finalize: %zu triangles: flatten %.3f s, build_bvh %.3f s (BVH2 source: %s, %.3f s)\n", world.size(), std::chrono::duration<double>(t_flat - t_start).count(),
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t_flat).count(), report.used ? "used" : (report.asked ? "declined" : "none"), report.seconds);

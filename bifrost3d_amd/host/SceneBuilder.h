@@ -94,6 +94,11 @@ public:
     struct BuildCounts { unsigned device_builds = 0, declined_builds = 0; };
     BuildCounts build_counts() const { return m_build_counts; }
     uint32_t longest_median_range() const { return m_bvh.longest_median_range; }
+    // The same for the 8-wide collapse (hipr_build_wide8 behind a context: the same slots, collapsed on the device); a source that declines or fails is followed by
+    // build_wide8, silently. Wide8Source() removes it. collapse_counts(): builds whose 8-wide tree the source made, and builds where it was asked and the host collapsed.
+    void set_wide8_source(const Wide8Source& source) { m_wide8_source = source; }
+    struct CollapseCounts { unsigned device_collapses = 0, declined_collapses = 0; };
+    CollapseCounts collapse_counts() const { return m_collapse_counts; }
     // Material-only update after finalize(): `changed` rewrites material slots, `assignments` gives instances another material. The builder's own description is
     // kept in step WITHOUT a rebuild -- a material moves no corner and the tree builders read no flag, so the trees and the triangle order are the ones a rebuild
     // would make: the flags of the touched instances' triangles are recomputed (csrc/material_rules.h) and the leaf records of the 8-wide tree follow them. What
@@ -137,7 +142,9 @@ private:
     std::vector<HiprTriangle> m_triangles;
     BvhBuildResult m_bvh;
     Bvh2Source m_bvh2_source;
+    Wide8Source m_wide8_source;
     BuildCounts m_build_counts;
+    CollapseCounts m_collapse_counts;
     double m_built_bvh_area = 0.0;
     uint32_t m_bvh_max_depth_limit = 62;
     std::vector<float> m_environment_PDF;

@@ -4,6 +4,7 @@
 // The scene a handle owns is exactly what a Bifrost host would hand to hipr_upload_scene().
 #include "Scenes.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <exception>
 #include <cstring>
@@ -356,13 +357,17 @@ int hiprh_scene_rebuild(void* scene) {
 
 static int build_bvh2_on_context(void* context, const HiprTriangle* triangles, uint32_t count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_node_count,
                                  uint32_t* out_order, uint32_t* out_deepest);
-// Installs hipr_build_bvh2 of `context` (NULL: removes it) as the BVH2 stage of the scene's builds and, with a context, rebuilds the scene through it. A decline
+static int build_wide8_on_context(void* context, const HiprBvhNode* nodes, uint32_t node_count, const HiprTriangle* triangles, const uint32_t* order, uint32_t triangle_count, HiprSlot8* out_slots,
+                                  uint32_t slot_capacity, HiprWide8BuildResult* out);
+// Installs hipr_build_bvh2 of `context` (NULL: removes it) as the BVH2 stage of the scene's builds and hipr_build_wide8 as their 8-wide collapse (unless
+// device_collapse_wanted() says the host collapses), and, with a context, rebuilds the scene through them. A decline
 // or a device error is silent here: the host's stage builds the same tree. Returns 1 when the device built the BVH2, 0 when the host did, -1 on error.
 int hiprh_scene_use_device_builder(void* scene, void* context) {
     if (!scene) return -1;
     SceneBuilder* sb = static_cast<SceneBuilder*>(scene);
     try {
         sb->set_bvh2_source(context ? Bvh2Source{build_bvh2_on_context, context} : Bvh2Source());
+        sb->set_wide8_source(context && device_collapse_wanted() ? Wide8Source{build_wide8_on_context, context} : Wide8Source());
         if (!context) return 0;
         const unsigned before = sb->build_counts().device_builds;
         sb->rebuild();
@@ -374,6 +379,14 @@ int hiprh_scene_build_counts(void* scene, unsigned* out3) {
     if (!scene || !out3) return -1;
     const SceneBuilder* sb = static_cast<SceneBuilder*>(scene);
     out3[0] = sb->build_counts().device_builds; out3[1] = sb->build_counts().declined_builds; out3[2] = sb->longest_median_range();
+    return 0;
+}
+
+// out[0] = builds whose 8-wide tree the device collapsed, out[1] = builds where it was asked and the host collapsed instead.
+int hiprh_scene_collapse_counts(void* scene, unsigned* out2) {
+    if (!scene || !out2) return -1;
+    const SceneBuilder* sb = static_cast<SceneBuilder*>(scene);
+    out2[0] = sb->collapse_counts().device_collapses; out2[1] = sb->collapse_counts().declined_collapses;
     return 0;
 }
 
@@ -466,6 +479,46 @@ void* hiprh_bvh_build_on_device(void* context, const HiprTriangle* triangles, un
         if (!report.used) { delete h; return nullptr; }
         return h;
     } catch (const std::exception& e) { fprintf(stderr, "hiprh_bvh_build_on_device: %s\n", e.what()); delete h; return nullptr; }
+}
+// hipr_build_wide8 as a Wide8Source.
+static int build_wide8_on_context(void* context, const HiprBvhNode* nodes, uint32_t node_count, const HiprTriangle* triangles, const uint32_t* order, uint32_t triangle_count, HiprSlot8* out_slots,
+                                  uint32_t slot_capacity, HiprWide8BuildResult* out) {
+    return hipr_build_wide8(static_cast<HiprContext*>(context), nodes, node_count, triangles, order, triangle_count, out_slots, slot_capacity, out);
+}
+// A handle whose 8-wide tree `context` collapsed on the device (hipr_build_wide8) from the caller's BVH2 and triangles (`order` may be NULL); the handle's other trees
+// are empty. NULL when the device declines or fails -- this entry does not fall back: the status is in *out_status and the message in hipr_last_error().
+void* hiprh_wide8_build_on_device(void* context, const HiprBvhNode* nodes, unsigned node_count, const HiprTriangle* triangles, const unsigned* order, unsigned triangle_count, int* out_status) {
+    BvhHandle* h = nullptr;
+    if (out_status) *out_status = HIPR_ERROR_INVALID_ARGUMENT;
+    if (!context) return nullptr;
+    try {
+        const size_t capacity = size_t(std::min<uint64_t>(2ull * std::max(triangle_count, 1u), 0xFFFFFFull));
+        std::vector<HiprSlot8> slots(capacity);
+        HiprWide8BuildResult built = {};
+        const int status = hipr_build_wide8(static_cast<HiprContext*>(context), nodes, node_count, triangles, order, triangle_count, slots.data(), uint32_t(capacity), &built);
+        if (out_status) *out_status = status;
+        if (status != HIPR_OK) return nullptr;
+        h = new BvhHandle();
+        slots.resize(built.slot_count);
+        Wide8Result& w = h->result.wide8;
+        w.slots = std::move(slots);
+        w.height = built.height;
+        for (int a = 0; a < 3; ++a) { w.grid_min[a] = built.grid_min[a]; w.grid_cell[a] = built.grid_cell[a]; }
+        w.node_count = built.node_count; w.leaf_count = built.leaf_count; w.paired_leaves = built.paired_leaves;
+        return h;
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_wide8_build_on_device: %s\n", e.what()); delete h; return nullptr; }
+}
+// The handle's 8-wide tree: slots, height, grid (min xyz, cell xyz) and counters (nodes, leaf records, records of two triangles).
+const HiprSlot8* hiprh_bvh_wide8_slots(void* h) { return static_cast<BvhHandle*>(h)->result.wide8.slots.data(); }
+unsigned hiprh_bvh_wide8_slot_count(void* h) { return unsigned(static_cast<BvhHandle*>(h)->result.wide8.slots.size()); }
+unsigned hiprh_bvh_wide8_height(void* h) { return static_cast<BvhHandle*>(h)->result.wide8.height; }
+void hiprh_bvh_wide8_grid(void* h, float* out6) {
+    const Wide8Result& w = static_cast<BvhHandle*>(h)->result.wide8;
+    for (int a = 0; a < 3; ++a) { out6[a] = w.grid_min[a]; out6[3 + a] = w.grid_cell[a]; }
+}
+void hiprh_bvh_wide8_counts(void* h, unsigned* out3) {
+    const Wide8Result& w = static_cast<BvhHandle*>(h)->result.wide8;
+    out3[0] = w.node_count; out3[1] = w.leaf_count; out3[2] = w.paired_leaves;
 }
 // Test-only counters of the host's BVH2 stage: the ranges it split at the median and the longest of them.
 unsigned hiprh_bvh_median_splits(void* h) { return static_cast<BvhHandle*>(h)->result.median_splits; }

@@ -24,7 +24,7 @@ class Context:
         self.frame = None
 
     def remember_built_scene(self, scene):
-        """A host.Scene whose builds call hipr_build_bvh2 on this context (Scene.use_device_builder)."""
+        """A host.Scene whose builds call hipr_build_bvh2 and hipr_build_wide8 on this context (Scene.use_device_builder)."""
         if not hasattr(self, "_built_scenes"):
             import weakref
             self._built_scenes = weakref.WeakSet()
@@ -125,6 +125,31 @@ class Context:
         """Milliseconds of the last build_bvh2: argument checks, allocation + upload, kernels, read-back."""
         out = (C.c_double * 4)()
         self._check(self.lib.hipr_debug_build_times(self.handle, out), "hipr_debug_build_times")
+        return dict(validate=out[0], upload=out[1], kernels=out[2], readback=out[3])
+
+    def build_wide8(self, nodes: np.ndarray, triangles: np.ndarray, order: np.ndarray | None = None, slots: np.ndarray | None = None, result: np.ndarray | None = None):
+        """hipr_build_wide8: the host's 8-wide tree over the BVH2 `nodes` ((n, 16) uint32 words of HiprBvhNode), `triangles` ((t, 12) words of HiprTriangle) and the
+        `order` the leaves reference them in (None: as stored), collapsed on the device. Returns (status, slots (slot_count, 16) uint32, result): `result` a dict of
+        slot_count, height, grid_min, grid_cell, node_count, leaf_count, paired_leaves. `slots` ((capacity, 16) uint32) and `result` (12 uint32 words of
+        HiprWide8BuildResult) may be the caller's; on a status other than HIPR_OK both are returned whole as the call left them."""
+        nodes = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 16)
+        triangles = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 12)
+        order = None if order is None else np.ascontiguousarray(order, np.uint32)
+        slots = np.zeros((max(2 * len(triangles), 1), 16), np.uint32) if slots is None else slots
+        raw = np.zeros(C.sizeof(capi.HiprWide8BuildResult) // 4, np.uint32) if result is None else result
+        status = self.lib.hipr_build_wide8(self.handle, C.cast(nodes.ctypes.data, C.POINTER(capi.HiprBvhNode)), len(nodes), C.cast(triangles.ctypes.data, C.POINTER(capi.HiprTriangle)),
+                                           C.cast(order.ctypes.data, C.POINTER(C.c_uint32)) if order is not None else None, len(triangles), slots.ctypes.data, len(slots),
+                                           C.cast(raw.ctypes.data, C.POINTER(capi.HiprWide8BuildResult)))
+        if status != capi.HIPR_OK:
+            return status, slots, raw
+        r = capi.HiprWide8BuildResult.from_buffer_copy(raw.tobytes())
+        return status, slots[:r.slot_count], dict(slot_count=r.slot_count, height=r.height, grid_min=np.array(r.grid_min[:], np.float32), grid_cell=np.array(r.grid_cell[:], np.float32),
+                                                  node_count=r.node_count, leaf_count=r.leaf_count, paired_leaves=r.paired_leaves)
+
+    def collapse_times(self) -> dict:
+        """Milliseconds of the last build_wide8: the walk over the indices, allocation + upload, kernels, read-back."""
+        out = (C.c_double * 4)()
+        self._check(self.lib.hipr_debug_collapse_times(self.handle, out), "hipr_debug_collapse_times")
         return dict(validate=out[0], upload=out[1], kernels=out[2], readback=out[3])
 
     def read_scene_buffer(self, which: int) -> np.ndarray:

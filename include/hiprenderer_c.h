@@ -396,6 +396,24 @@ int hipr_update_scene_materials(HiprContext* context, const HiprMaterialUpdate* 
 int hipr_build_bvh2(HiprContext* context, const HiprTriangle* triangles, uint32_t count, uint32_t max_depth,
                     HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_node_count,
                     uint32_t* out_order /* count words */, uint32_t* out_deepest);
+/* The 8-wide tree of a BVH2 collapsed on the device (the reference asks OptiX for a "Trbvh" build, which runs on the GPU, OR/Renderer.cpp:161-182,471-476): byte for
+ * byte the slots, height, grid and counters of the host's collapse in its default configuration (csrc/wide8_build.h). `triangles` and `order` (may be NULL:
+ * triangles[k]) are the scene's triangles and the order the BVH2's leaves reference them in, element k = triangles[order[k]]; all pointers are host pointers.
+ * The call runs on the context's stream, owns its device scratch (kept with the context up to 128 MiB, freed when the call returns beyond that), leaves the
+ * resident scene untouched and needs none. Checked on the host, by one pass over the indices, before the device is touched:
+ *   HIPR_ERROR_INVALID_ARGUMENT   a null pointer, no nodes or triangles; an order entry, a child index or a leaf range out of bounds; a node referenced twice;
+ *                                 more than 64 levels of nodes; `slot_capacity` below the slots the tree needs (known before a slot is written); a triangle
+ *                                 corner or a child box that is not finite (found by the first passes on the device, which read them anyway).
+ *   HIPR_ERROR_UNSUPPORTED        the tree needs more than 0xFFFFFF slots (the host returns an empty tree there too); or the leaves are not met in ascending
+ *                                 order of their first triangle, which every BVH2 of this library is: the host collapses such a tree.
+ * Every refusal leaves `out_slots` and `out` untouched. */
+typedef struct HiprWide8BuildResult {
+    uint32_t slot_count, height;
+    float grid_min[3], grid_cell[3];
+    uint32_t node_count, leaf_count, paired_leaves;
+} HiprWide8BuildResult;
+int hipr_build_wide8(HiprContext* context, const HiprBvhNode* nodes, uint32_t node_count, const HiprTriangle* triangles, const uint32_t* order /* may be NULL */,
+                     uint32_t triangle_count, HiprSlot8* out_slots, uint32_t slot_capacity, HiprWide8BuildResult* out);
 int hipr_set_scene_state(HiprContext* context, const HiprSceneState* state);
 
 /* Entry points, numbered like OR/Types.h:33-44. set_backend() of the host renderer maps Backend values onto them
@@ -479,6 +497,8 @@ int hipr_group_refit_scene_transforms(HiprGroup* group, const HiprInstanceTransf
                                       const HiprLight* lights, uint32_t light_count, HiprRefitResult* out);   /* every member; their results must agree */
 int hipr_group_build_bvh2(HiprGroup* group, const HiprTriangle* triangles, uint32_t count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity,
                           uint32_t* out_node_count, uint32_t* out_order, uint32_t* out_deepest);   /* builds on member 0 */
+int hipr_group_build_wide8(HiprGroup* group, const HiprBvhNode* nodes, uint32_t node_count, const HiprTriangle* triangles, const uint32_t* order, uint32_t triangle_count,
+                           HiprSlot8* out_slots, uint32_t slot_capacity, HiprWide8BuildResult* out);   /* collapses on member 0 */
 int hipr_group_update_scene_materials(HiprGroup* group, const HiprMaterialUpdate* materials, uint32_t material_count,
                                       const HiprInstanceMaterial* assignments, uint32_t assignment_count);   /* every member checks before any member writes */
 int hipr_group_set_scene_state(HiprGroup* group, const HiprSceneState* state);
@@ -625,6 +645,8 @@ int hipr_debug_read_scene_buffer(HiprContext* context, int which, void* out, uin
 /* Milliseconds of the context's last successful hipr_build_bvh2, which add up to the call: the argument checks (the pass over all corners for one that is not
  * finite), scratch allocation + upload, kernels, read-back (tools/device_build_probe.py). */
 int hipr_debug_build_times(HiprContext* context, double* out4_ms);
+/* The same for the context's last successful hipr_build_wide8: the walk over the indices, allocation + upload, kernels (with the few words read per level), read-back. */
+int hipr_debug_collapse_times(HiprContext* context, double* out4_ms);
 
 #ifdef __cplusplus
 }

@@ -49,7 +49,7 @@ def main():
     p.add_argument("--effects", choices=["preset", "linear"], default="preset")
     p.add_argument("--denoise", action="store_true", help="filter the frame with the denoising backend's filter (albedo feature pass + edge-avoiding a-trous wavelets)")
     p.add_argument("--arithmetic", choices=["fast", "exact"], default="fast", help="hipr_set_arithmetic: exact = IEEE shading arithmetic with specified sin / cos / pow, frames equal to the CPU oracle's bit for bit")
-    p.add_argument("--device-build", action="store_true", help="build the scene's BVH2 on the device (hipr_build_bvh2): the same tree, the same picture; where the device declines the host builds")
+    p.add_argument("--device-build", action="store_true", help="build the scene's BVH2 on the device (hipr_build_bvh2) and collapse it to the 8-wide tree there (hipr_build_wide8, unless HIPR_DEVICE_COLLAPSE=0): the same trees, the same picture; where the device declines a stage the host builds it")
     p.add_argument("--out", default="render.png")
     args = p.parse_args()
     width, height = (int(v) for v in args.size.lower().split("x"))
@@ -69,6 +69,8 @@ def main():
     ctx = Context(0, arithmetic=args.arithmetic)
     if args.device_build:
         print("BVH2 built on the device" if scene.use_device_builder(ctx) else "the device declined the BVH2 build: built on the host")
+        collapses = scene.collapse_counts()
+        print("8-wide tree collapsed on the device" if collapses["device_collapses"] else ("the device declined the 8-wide collapse: collapsed on the host" if collapses["declined_collapses"] else "8-wide tree collapsed on the host"))
     ctx.upload_scene(scene)
     batch = max(1, min(args.spp_per_pass, args.spp))
     ctx.set_frame(width, height, samples_per_pass=batch)
