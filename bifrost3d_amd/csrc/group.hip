@@ -355,6 +355,27 @@ int hipr_group_build_wide8(HiprGroup* g, const HiprBvhNode* nodes, uint32_t node
     return hipr_build_wide8(g->members[0].context, nodes, node_count, triangles, order, triangle_count, out_slots, slot_capacity, out);
 }
 
+// hipr_rebuild_scene_trees on every member: the same kernels over the same arrays give the same trees, so member 0's arrays are the ones handed out and the
+// others rebuild without a read-back. A member that refuses leaves its scene as it was; the members then disagree, and the caller uploads.
+int hipr_group_rebuild_scene_trees(HiprGroup* g, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_order, HiprSlot8* out_slots, uint32_t slot_capacity,
+                                   HiprSceneRebuildResult* out) {
+    if (!g || !out || g->members.empty()) return HIPR_ERROR_INVALID_ARGUMENT;
+    std::vector<HiprSceneRebuildResult> results(g->members.size());
+    const int status = for_each_member(g, [&](Member& m, uint32_t index) {
+        return index == 0 ? hipr_rebuild_scene_trees(m.context, max_depth, out_nodes, node_capacity, out_order, out_slots, slot_capacity, &results[0])
+                          : hipr_rebuild_scene_trees(m.context, max_depth, nullptr, 0, nullptr, nullptr, 0, &results[index]);
+    });
+    if (status) return status;
+    for (const HiprSceneRebuildResult& r : results)
+        if (std::memcmp(&r, &results[0], sizeof(r))) {
+            hipr_internal_set_last_error("hipr_group_rebuild_scene_trees: the members' trees disagree");
+            fprintf(stderr, "hiprenderer: hipr_group_rebuild_scene_trees: the members' trees disagree\n");
+            return HIPR_ERROR_HIP;
+        }
+    *out = results[0];
+    return HIPR_OK;
+}
+
 int hipr_group_update_scene_materials(HiprGroup* g, const HiprMaterialUpdate* materials, uint32_t material_count, const HiprInstanceMaterial* assignments, uint32_t assignment_count) {
     if (!g) return HIPR_ERROR_INVALID_ARGUMENT;
     // Every member checks before any member writes: an edit one member refuses leaves all of them as they were.

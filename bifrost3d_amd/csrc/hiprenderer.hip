@@ -17,6 +17,7 @@
 #include "material_update.h"
 #include "bvh2_build.h"
 #include "wide8_build.h"
+#include "scene_rebuild.h"
 #include "launch.h"
 
 #include <hip/hip_runtime.h>
@@ -176,6 +177,13 @@ struct ResidentScene {
     bool tree_stale = false;            // a device refit left the BVH2 and 4-wide arrays behind: hipr_set_trace_variant refuses them until the next upload / geometry update
 
     bool ready = false;
+    // The last writer was a device refit that reported needs_rebuild: the scene is not ready, but its pools and triangles are whole -- the one state besides `ready`
+    // that rebuild_trees() accepts. Every writer clears it on its way in, so a scene a failed writer left behind is never taken for it.
+    bool awaits_rebuild = false;
+    void begin_write() { ready = false; awaits_rebuild = false; }
+    // install_rebuilt_trees() replaced the BVH2 and the 8-wide tree and left the 4-wide array of the OLD tree behind: the next geometry update brings the new tree's,
+    // whose size and stack need it takes instead of comparing them with the uploaded ones.
+    bool wide4_awaits_geometry = false;
     // The search of the uploaded scene, fixed when it is uploaded (hipr_set_trace_variant / HIPR_TRACE_VARIANT name a request for the NEXT upload).
     int chosen_variant = HIPR_TRACE_BVH2;
     void choose_variant(int requested) {
@@ -194,6 +202,13 @@ struct ResidentScene {
     int refit_transforms(const HiprInstanceTransform* moved, uint32_t moved_count, const HiprLight* new_lights, uint32_t light_count, hipStream_t stream, HiprRefitResult* out);
     int update_materials(const HiprMaterialUpdate* changed, uint32_t changed_count, const HiprInstanceMaterial* assignments, uint32_t assignment_count, hipStream_t stream);
     int lights_keep_their_types(const char* who, const HiprLight* new_lights, uint32_t count) const;
+    // What hipr_rebuild_scene_trees hands over once nothing can refuse any more: device arrays of the build's and the collapse's scratch, and the host's copy of the slots.
+    struct RebuiltTrees {
+        const HiprTriangle* flat; const uint8_t* flat_class; const uint32_t* order;      // the triangles in flatten order, and the new order over them
+        const HiprBvhNode* nodes; uint32_t node_count, deepest;
+        const HiprSlot8* slots; const HiprSlot8* host_slots; HiprWide8BuildResult wide8;
+    };
+    int install_rebuilt_trees(const RebuiltTrees& built, hipStream_t stream);
 
 private:
     int upload_pools(const HiprSceneDesc* s, bool all_pools, hipStream_t stream);
@@ -285,6 +300,20 @@ struct CollapseScratch {
 };
 struct CollapseScratchGuard { CollapseScratch& scratch; ~CollapseScratchGuard() { scratch.release_if_large(); } };
 
+// What hipr_rebuild_scene_trees needs beside the two builds' scratch (scene_rebuild.h), by the same rule: 9 B per triangle and a word per instance and BVH2 node. The
+// flat triangle array itself is BuildScratch::triangles, where hipr_build_bvh2 keeps its input.
+struct RebuildScratch {
+    DeviceBuffer flat_class, claim, instance_counts, first, level_nodes, status;
+    double flatten_ms = 0.0, bvh2_ms = 0.0, collapse_ms = 0.0, install_ms = 0.0, readback_ms = 0.0;      // of the last rebuild
+    void release_if_large() {
+        DeviceBuffer* all[] = {&flat_class, &claim, &instance_counts, &first, &level_nodes, &status};
+        size_t total = 0;
+        for (const DeviceBuffer* b : all) total += b->bytes;
+        if (total > BuildScratch::KEEP_BYTES) for (DeviceBuffer* b : all) b->release();
+    }
+};
+struct RebuildScratchGuard { RebuildScratch& scratch; ~RebuildScratchGuard() { scratch.release_if_large(); } };
+
 } // namespace
 
 struct HiprContext {
@@ -375,6 +404,7 @@ struct HiprContext {
     DeviceBuffer debug_a, debug_b, debug_c;
     BuildScratch build;                 // hipr_build_bvh2; nothing of the resident scene
     CollapseScratch collapse;           // hipr_build_wide8; likewise
+    RebuildScratch rebuild;             // hipr_rebuild_scene_trees, which also runs over the two above
 
     hipEvent_t next_event() {
         if (events_used == event_pool.size()) {
@@ -1324,7 +1354,8 @@ int ResidentScene::prepare_refit(const HiprSceneDesc* s, bool new_topology, hipS
 }
 
 int ResidentScene::upload(const HiprSceneDesc* s, const Preflight& checked, int requested_variant, bool cull_backfaces, hipStream_t stream) {
-    ready = false;
+    begin_write();
+    wide4_awaits_geometry = false;
     if (int r = upload_pools(s, true, stream)) return r;
     const HiprEnvironment* env = s->environment;
     args.nodes = nodes.as<float4>();
@@ -1359,8 +1390,14 @@ int ResidentScene::upload(const HiprSceneDesc* s, const Preflight& checked, int 
 
 // The pools it brings again have the uploaded sizes (hipr_update_scene_geometry has compared them): no buffer moves, the pointers and counts in `args` stay.
 int ResidentScene::update_geometry(const HiprSceneDesc* s, const Preflight& checked, int requested_variant, bool cull_backfaces, hipStream_t stream) {
-    ready = false;
+    begin_write();
     if (int r = upload_pools(s, false, stream)) return r;
+    if (wide4_awaits_geometry) {      // the 4-wide array of the rebuilt tree: the buffer may have moved and its size has changed
+        args.wide_nodes = s->wide_nodes && s->wide_node_count ? wide_nodes.as<uint4>() : nullptr;
+        args.wide_node_count = s->wide_nodes ? s->wide_node_count : 0u;
+        wide_stack_entries = checked.wide_stack_need;
+        wide4_awaits_geometry = false;
+    }
     if (int r = derive_from_triangles(s, checked, false, requested_variant, cull_backfaces, stream)) return r;      // also ends the state a device refit left
     ready = true;
     return HIPR_OK;
@@ -1377,7 +1414,7 @@ int ResidentScene::lights_keep_their_types(const char* who, const HiprLight* new
 
 // The device work of hipr_refit_scene_transforms, which has checked the arguments against uploaded_instances and uploaded_light_types.
 int ResidentScene::refit_transforms(const HiprInstanceTransform* moved, uint32_t moved_count, const HiprLight* new_lights, uint32_t light_count, hipStream_t st, HiprRefitResult* out) {
-    ready = false;
+    begin_write();
     *out = {};
     if (new_lights && light_count) {
         if (int r = lights.upload(new_lights, size_t(light_count) * sizeof(HiprLight), st)) return r;
@@ -1423,12 +1460,13 @@ int ResidentScene::refit_transforms(const HiprInstanceTransform* moved, uint32_t
     out->uploaded_half_area = uploaded_half_area;
     for (int a = 0; a < 3; ++a) { out->grid_min[a] = wide8.grid_min[a]; out->grid_cell[a] = wide8.grid_cell[a]; }
     ready = !out->needs_rebuild;
+    awaits_rebuild = !ready;
     return HIPR_OK;
 }
 
 // The device work of hipr_update_scene_materials, which has checked every index against uploaded_materials, uploaded_instances and uploaded_textures.
 int ResidentScene::update_materials(const HiprMaterialUpdate* changed, uint32_t changed_count, const HiprInstanceMaterial* assignments, uint32_t assignment_count, hipStream_t st) {
-    ready = false;
+    begin_write();
     // the host copies as they will be once the device holds them (after the last synchronise); the copies below read from them
     std::vector<HiprMaterial> new_materials = uploaded_materials;
     std::vector<HiprInstance> new_instances = uploaded_instances;
@@ -1474,6 +1512,39 @@ int ResidentScene::update_materials(const HiprMaterialUpdate* changed, uint32_t 
     derive_switches_from_pools();
     all_triangles_opaque = reduction[0] != 0;
     any_coated_triangle = reduction[1] != 0;
+    ready = true;
+    return HIPR_OK;
+}
+
+// The last step of hipr_rebuild_scene_trees, which has refused everything it refuses: the new resident arrays, and what an upload derives from them. The pools, the
+// instances and the lights stay; all_triangles_opaque, any_coated_triangle and the other switches cannot change under a permutation of the triangles and stay. The
+// 4-wide array is not rebuilt: tree_stale stays set until the next upload or geometry update, as after the refit.
+int ResidentScene::install_rebuilt_trees(const RebuiltTrees& built, hipStream_t st) {
+    begin_write();
+    const uint32_t triangle_count = args.triangle_count;
+    hipLaunchKernelGGL(k_rebuild_gather, dim3((triangle_count + REBUILD_BLOCK - 1) / REBUILD_BLOCK), dim3(REBUILD_BLOCK), 0, st, built.flat, built.flat_class, built.order,
+                       triangles.as<HiprTriangle>(), triangle_class.as<uint8_t>(), triangle_count);
+    HIP_TRY(hipGetLastError());
+    if (int r = nodes.resize(size_t(built.node_count) * sizeof(HiprBvhNode))) return r;
+    if (int r = wide8_slots.resize(size_t(built.wide8.slot_count) * sizeof(HiprSlot8))) return r;
+    HIP_TRY(hipMemcpyAsync(nodes.ptr, built.nodes, size_t(built.node_count) * sizeof(HiprBvhNode), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(wide8_slots.ptr, built.slots, size_t(built.wide8.slot_count) * sizeof(HiprSlot8), hipMemcpyDeviceToDevice, st));
+    args.nodes = nodes.as<float4>();
+    args.node_count = built.node_count;
+    wide8.slots = wide8_slots.as<uint4>();
+    wide8.slot_count = built.wide8.slot_count;
+    for (int a = 0; a < 3; ++a) { wide8.grid_min[a] = built.wide8.grid_min[a]; wide8.grid_cell[a] = built.wide8.grid_cell[a]; }
+    wide8_height = built.wide8.height;
+    const uint32_t bvh_max_depth = built.deepest + 1u;      // BvhBuildResult::max_depth
+    stack_size = bvh_max_depth <= 16 ? 16 : (bvh_max_depth <= 32 ? 32 : 64);
+    queue_triangle_records(st);
+    HIP_TRY(hipGetLastError());
+    HiprSceneDesc lists = {};      // what prepare_refit reads of a description
+    lists.wide8_slots = built.host_slots; lists.wide8_slot_count = built.wide8.slot_count;
+    lists.triangle_count = triangle_count; lists.instance_count = uint32_t(uploaded_instances.size());
+    if (int r = prepare_refit(&lists, true, st)) return r;      // the slot lists by kind and level with their host copies, and uploaded_half_area by the kernels that take it at upload
+    tree_stale = true;
+    wide4_awaits_geometry = true;
     ready = true;
     return HIPR_OK;
 }
@@ -1622,10 +1693,13 @@ int hipr_update_scene_geometry(HiprContext* c, const HiprSceneDesc* s) {
     if (s->material_count != r.uploaded_materials.size() || s->texture_count != r.uploaded_texture_count || s->vertex_count != r.uploaded_vertex_count ||
         s->index_count != r.uploaded_index_count || s->texel_bytes != r.uploaded_texel_bytes)
         return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: material, texture, vertex, index and texel pool sizes must equal the uploaded scene's (those pools are not re-uploaded)");
-    if (s->node_count != r.args.node_count || s->triangle_count != r.args.triangle_count || (s->wide_nodes ? s->wide_node_count : 0u) != r.args.wide_node_count ||
+    const bool wide4_follows = r.wide4_awaits_geometry;      // after hipr_rebuild_scene_trees the 4-wide tree is a new one: it is taken, not compared
+    if (s->node_count != r.args.node_count || s->triangle_count != r.args.triangle_count || (!wide4_follows && (s->wide_nodes ? s->wide_node_count : 0u) != r.args.wide_node_count) ||
         s->light_count != r.args.light_count || s->instance_count != r.uploaded_instances.size())
         return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: node, triangle, instance and light counts must equal the uploaded scene's (a refit keeps the topology)");
-    if (checked.wide_stack_need != r.wide_stack_entries) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: the wide BVH's topology changed");
+    if (!wide4_follows && checked.wide_stack_need != r.wide_stack_entries) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: the wide BVH's topology changed");
+    if (wide4_follows && (checked.wide_stack_need > 32u + uint32_t(TRACE_SPILL_ENTRIES) || s->bvh_max_depth > 64))
+        return fail(HIPR_ERROR_UNSUPPORTED, "hipr_update_scene_geometry: the rebuilt scene's trees need more stack than the traversal kernels provide");
     if (r.wide8.slot_count && (s->wide8_slot_count != r.wide8.slot_count || checked.wide8_height != r.wide8_height))
         return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_update_scene_geometry: the 8-wide tree's topology changed");
     if (int st = r.lights_keep_their_types("hipr_update_scene_geometry", s->lights, s->light_count)) return st;
@@ -1691,39 +1765,31 @@ int hipr_update_scene_materials(HiprContext* c, const HiprMaterialUpdate* materi
     return c->scene.update_materials(materials, material_count, assignments, assignment_count, c->stream);
 }
 
-// The BVH2 of host/BvhBuilder.cpp built by the kernels of bvh2_build.h. Nothing of the resident scene is read or written; the outputs are written only once the
-// whole build has succeeded.
-int hipr_build_bvh2(HiprContext* c, const HiprTriangle* triangles, uint32_t count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_node_count,
-                    uint32_t* out_order, uint32_t* out_deepest) {
-    if (int st = check_context(c)) return st;
-    const auto t_validate = std::chrono::steady_clock::now();
-    if (!triangles || !count || !out_nodes || !out_node_count || !out_order || !out_deepest) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_bvh2: null argument or no triangles");
-    if (count > BUILD_MAX_TRIANGLES) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_build_bvh2: %u triangles, a leaf reference holds %u", count, BUILD_MAX_TRIANGLES);
-    if (node_capacity < std::max(std::max(count, 1u) - 1u, 1u)) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_bvh2: room for %u nodes, %u triangles can need %u", node_capacity, count, std::max(count - 1u, 1u));
-    for (uint32_t i = 0; i < count; ++i)
-        for (int k = 0; k < 3; ++k)
-            if (!std::isfinite(triangles[i].v0[k]) || !std::isfinite(triangles[i].v1[k]) || !std::isfinite(triangles[i].v2[k]))
-                return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_bvh2: triangle %u has a corner that is not finite", i);
-    const uint32_t depth_limit = std::max(max_depth, 8u);
+// What the device work of a BVH2 build leaves beside the context's BuildScratch (out_nodes, order, place, status): the nodes, and the nodes created per level.
+struct Bvh2Built { uint32_t node_count = 1; std::vector<uint32_t> level_nodes; };
+// The device-to-device core hipr_build_bvh2 and hipr_rebuild_scene_trees share: scratch, kernels and the words read per level, on the context's stream, ending
+// synchronised. `host_triangles` are uploaded into the scratch first (`uploaded` is the time after that); otherwise the build runs over `device_triangles` where they
+// lie. `who` names the entry point in the messages. The caller holds the BuildScratchGuard and has checked count and corners.
+static int build_bvh2_on_the_device(HiprContext* c, const char* who, const HiprTriangle* host_triangles, const HiprTriangle* device_triangles, uint32_t count, uint32_t depth_limit, Bvh2Built& built,
+                                    std::chrono::steady_clock::time_point& uploaded) {
     const uint32_t max_levels = std::min(depth_limit, count) + 2u;      // a range's depth grows by one per level and never passes the limit
     const size_t n = count, max_open = n / 4 + 2, max_long = n / BUILD_SHORT_RANGE + 2, blocks = (n + BUILD_BLOCK - 1) / BUILD_BLOCK;
     const size_t status_words = STATUS_LEVELS + 2 * size_t(max_levels + 2);
     BuildScratch& b = c->build;
-    const BuildScratchGuard guard{b};
     hipStream_t stream = c->stream;
-    c->break_chain(stream);
-    const auto t0 = std::chrono::steady_clock::now();
     if (b.boxes.resize(n * sizeof(BuildBox)) | b.centroids.resize(n * 12) | b.order.resize(n * 4) | b.seg.resize(n * 4) | b.order_tmp.resize(n * 4) | b.seg_tmp.resize(n * 4) |
         b.ranges[0].resize(max_open * sizeof(BuildRange)) | b.ranges[1].resize(max_open * sizeof(BuildRange)) | b.acc.resize(max_long * ACC_WORDS * 4) | b.setup.resize(max_long * sizeof(BuildSetup)) |
         b.split.resize(max_long * sizeof(BuildSplit)) | b.scan_local.resize(n * 4) | b.block_sums.resize(blocks * 4) | b.nodes.resize(n * sizeof(HiprBvhNode)) | b.sizes.resize(n * 4) |
         b.place.resize(n * 4) | b.out_nodes.resize(n * sizeof(HiprBvhNode)) | b.status.resize(status_words * 4))
         return HIPR_ERROR_OUT_OF_MEMORY;
-    if (int st = b.triangles.upload(triangles, n * sizeof(HiprTriangle), stream)) return st;
-    HIP_TRY(hipStreamSynchronize(stream));
-    const auto t1 = std::chrono::steady_clock::now();
+    if (host_triangles) {
+        if (int st = b.triangles.upload(host_triangles, n * sizeof(HiprTriangle), stream)) return st;
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    uploaded = std::chrono::steady_clock::now();
 
     BuildState S = {};
-    S.triangles = b.triangles.as<HiprTriangle>(); S.count = count; S.depth_limit = depth_limit;
+    S.triangles = host_triangles ? b.triangles.as<HiprTriangle>() : device_triangles; S.count = count; S.depth_limit = depth_limit;
     S.boxes = b.boxes.as<BuildBox>(); S.centroids = b.centroids.as<float>();
     S.order = b.order.as<uint32_t>(); S.seg = b.seg.as<uint32_t>(); S.order_tmp = b.order_tmp.as<uint32_t>(); S.seg_tmp = b.seg_tmp.as<uint32_t>();
     S.acc = b.acc.as<uint32_t>(); S.setup = b.setup.as<BuildSetup>(); S.split = b.split.as<BuildSplit>();
@@ -1740,7 +1806,8 @@ int hipr_build_bvh2(HiprContext* c, const HiprTriangle* triangles, uint32_t coun
     HIP_TRY(hipMemsetAsync(S.place, 0, 4, stream));
     const dim3 block(BUILD_BLOCK), per_position{uint32_t(blocks)};
     hipLaunchKernelGGL(k_build_prepare, per_position, block, 0, stream, S);
-    std::vector<uint32_t> level_nodes;      // the open ranges = new nodes of every level
+    std::vector<uint32_t>& level_nodes = built.level_nodes;      // the open ranges = new nodes of every level
+    level_nodes.clear();
     uint32_t node_count = 1;
     if (count <= BUILD_LEAF_MAX) hipLaunchKernelGGL(k_build_single_leaf, dim3(1), block, 0, stream, S);
     else {
@@ -1749,7 +1816,7 @@ int hipr_build_bvh2(HiprContext* c, const HiprTriangle* triangles, uint32_t coun
         uint32_t open = 1, long_ranges = root.long_index == BUILD_NONE ? 0u : 1u, node_base = 0;
         for (uint32_t level = 0; open; ++level) {
             if (level >= max_levels || node_base + open > count - 1u || open > max_open - 2 || long_ranges > max_long - 2)
-                return fail(HIPR_ERROR_HIP, "hipr_build_bvh2: the build left its bounds at level %u (%u open ranges, %u nodes)", level, open, node_base);
+                return fail(HIPR_ERROR_HIP, "%s: the build left its bounds at level %u (%u open ranges, %u nodes)", who, level, open, node_base);
             const BuildLevel L = {b.ranges[level & 1u].as<BuildRange>(), b.ranges[(level + 1u) & 1u].as<BuildRange>(), open, node_base, level};
             const dim3 per_range((open + BUILD_BLOCK - 1) / BUILD_BLOCK);
             if (long_ranges) {
@@ -1770,8 +1837,8 @@ int hipr_build_bvh2(HiprContext* c, const HiprTriangle* triangles, uint32_t coun
             HIP_TRY(hipStreamSynchronize(stream));
             if (status[STATUS_DECLINE] != 0xFFFFFFFFu) {
                 b.levels = level + 1;
-                return fail(HIPR_ERROR_UNSUPPORTED, "hipr_build_bvh2: the range [%u, %u) of %u triangles at level %u takes the median path (the depth budget, or coincident centroids) and is longer than the %u a lane sorts; build on the host",
-                            status[STATUS_DECLINE + 1], status[STATUS_DECLINE], status[STATUS_DECLINE] - status[STATUS_DECLINE + 1], level, BUILD_MEDIAN_LANE_LIMIT);
+                return fail(HIPR_ERROR_UNSUPPORTED, "%s: the range [%u, %u) of %u triangles at level %u takes the median path (the depth budget, or coincident centroids) and is longer than the %u a lane sorts; build on the host",
+                            who, status[STATUS_DECLINE + 1], status[STATUS_DECLINE], status[STATUS_DECLINE] - status[STATUS_DECLINE + 1], level, BUILD_MEDIAN_LANE_LIMIT);
             }
             level_nodes.push_back(open);
             node_base += open;
@@ -1786,11 +1853,41 @@ int hipr_build_bvh2(HiprContext* c, const HiprTriangle* triangles, uint32_t coun
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
+    built.node_count = node_count;
+    b.levels = uint32_t(level_nodes.size());
+    return HIPR_OK;
+}
+
+// The BVH2 of host/BvhBuilder.cpp built by the kernels of bvh2_build.h. Nothing of the resident scene is read or written; the outputs are written only once the
+// whole build has succeeded.
+int hipr_build_bvh2(HiprContext* c, const HiprTriangle* triangles, uint32_t count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_node_count,
+                    uint32_t* out_order, uint32_t* out_deepest) {
+    if (int st = check_context(c)) return st;
+    const auto t_validate = std::chrono::steady_clock::now();
+    if (!triangles || !count || !out_nodes || !out_node_count || !out_order || !out_deepest) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_bvh2: null argument or no triangles");
+    if (count > BUILD_MAX_TRIANGLES) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_build_bvh2: %u triangles, a leaf reference holds %u", count, BUILD_MAX_TRIANGLES);
+    if (node_capacity < std::max(std::max(count, 1u) - 1u, 1u)) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_bvh2: room for %u nodes, %u triangles can need %u", node_capacity, count, std::max(count - 1u, 1u));
+    for (uint32_t i = 0; i < count; ++i)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(triangles[i].v0[k]) || !std::isfinite(triangles[i].v1[k]) || !std::isfinite(triangles[i].v2[k]))
+                return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_bvh2: triangle %u has a corner that is not finite", i);
+    const uint32_t depth_limit = std::max(max_depth, 8u);
+    const size_t n = count;
+    BuildScratch& b = c->build;
+    const BuildScratchGuard guard{b};
+    hipStream_t stream = c->stream;
+    c->break_chain(stream);
+    const auto t0 = std::chrono::steady_clock::now();
+    Bvh2Built built;
+    std::chrono::steady_clock::time_point t1;
+    if (int st = build_bvh2_on_the_device(c, "hipr_build_bvh2", triangles, nullptr, count, depth_limit, built, t1)) return st;
+    const uint32_t node_count = built.node_count;
+    uint32_t status[STATUS_LEVELS] = {};
     const auto t2 = std::chrono::steady_clock::now();
     if (node_count > node_capacity) return fail(HIPR_ERROR_HIP, "hipr_build_bvh2: %u nodes built, room for %u", node_count, node_capacity);
-    HIP_TRY(hipMemcpyAsync(status.data(), S.status, STATUS_LEVELS * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(out_nodes, S.out_nodes, size_t(node_count) * sizeof(HiprBvhNode), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(out_order, S.order, n * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(status, b.status.ptr, STATUS_LEVELS * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(out_nodes, b.out_nodes.ptr, size_t(node_count) * sizeof(HiprBvhNode), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(out_order, b.order.ptr, n * 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     *out_node_count = node_count;
     *out_deepest = status[STATUS_DEEPEST];
@@ -1799,7 +1896,6 @@ int hipr_build_bvh2(HiprContext* c, const HiprTriangle* triangles, uint32_t coun
     b.upload_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
     b.kernel_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
     b.readback_ms = std::chrono::duration<double, std::milli>(t3 - t2).count();
-    b.levels = uint32_t(level_nodes.size());
     if (std::getenv("HIPR_BVH_TIMING"))
         fprintf(stderr, "[hipr] hipr_build_bvh2: %u triangles, %u nodes, %u levels: argument checks %.3f ms, allocation + upload %.3f ms, kernels %.3f ms, read-back %.3f ms (transfers %.0f %% of %.3f ms)\n", count, node_count, b.levels,
                 b.validate_ms, b.upload_ms, b.kernel_ms, b.readback_ms, 100.0 * (b.upload_ms + b.readback_ms) / (b.validate_ms + b.upload_ms + b.kernel_ms + b.readback_ms),
@@ -1810,6 +1906,104 @@ int hipr_build_bvh2(HiprContext* c, const HiprTriangle* triangles, uint32_t coun
 int hipr_debug_build_times(HiprContext* c, double* out4_ms) {
     if (!c || !out4_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_build_times: null argument");
     out4_ms[0] = c->build.validate_ms; out4_ms[1] = c->build.upload_ms; out4_ms[2] = c->build.kernel_ms; out4_ms[3] = c->build.readback_ms;
+    return HIPR_OK;
+}
+
+// The device-to-device core hipr_build_wide8 and hipr_rebuild_scene_trees share: the passes of wide8_build.h over a BVH2, its triangles, their order and the level lists
+// the device already holds (W8State's input members, the scratch of collapse_scratch_for cleared), on the context's stream, ending synchronised with the slots in
+// CollapseScratch::slots. `level_first`: level l is level_nodes[level_first[l] .. level_first[l + 1]). `who` names the entry point in the messages. The caller holds
+// the CollapseScratchGuard.
+static int collapse_on_the_device(HiprContext* c, const char* who, W8State& S, const std::vector<uint32_t>& level_first, uint32_t slot_capacity, HiprWide8BuildResult& result) {
+    CollapseScratch& b = c->collapse;
+    hipStream_t stream = c->stream;
+    const uint32_t triangle_count = S.triangle_count, node_count = S.node_count, reachable = S.reachable, bvh_levels = uint32_t(level_first.size()) - 1u;
+    const size_t T = triangle_count, N = node_count, scan_blocks = (T + W8_BLOCK - 1) / W8_BLOCK;
+    const dim3 block(W8_BLOCK), per_triangle{uint32_t(scan_blocks)}, per_reference((2u * reachable + W8_BLOCK - 1) / W8_BLOCK);
+    auto blocks_for = [](uint32_t threads) { return dim3((threads + W8_BLOCK - 1) / W8_BLOCK); };
+    // 1, 2: the bounds and the record numbers; the host reads both together
+    hipLaunchKernelGGL(k_w8_bounds, per_triangle, block, 0, stream, S.triangles, triangle_count, b.partial.as<RefitBound>(), S.status);
+    hipLaunchKernelGGL(k_refit_bounds_final, dim3(1), block, 0, stream, b.partial.as<RefitBound>(), uint32_t(scan_blocks), b.bounds.as<RefitBound>());
+    hipLaunchKernelGGL(k_w8_count_leaf, per_reference, block, 0, stream, S);
+    hipLaunchKernelGGL(k_w8_scan_local, per_triangle, block, 0, stream, S);
+    hipLaunchKernelGGL(k_build_scan_sums, dim3(1), block, 0, stream, S.block_sums, uint32_t(scan_blocks + 1));
+    RefitBound bounds[6];
+    uint32_t record_total = 0, not_finite = 0;
+    HIP_TRY(hipMemcpyAsync(bounds, b.bounds.ptr, sizeof(bounds), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&record_total, S.block_sums + scan_blocks, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&not_finite, S.status + W8_STATUS_NOT_FINITE, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (not_finite) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: a triangle corner or a child box is not finite", who);
+    if (record_total == 0 || record_total > triangle_count) return fail(HIPR_ERROR_HIP, "%s: %u records of %u triangles", who, record_total, triangle_count);
+    result = {};
+    {
+        const float lo[3] = {bounds[0].v, bounds[1].v, bounds[2].v}, hi[3] = {bounds[3].v, bounds[4].v, bounds[5].v};
+        refit_grid(lo, hi, result.grid_min, result.grid_cell);
+        for (int a = 0; a < 3; ++a) { S.grid_min[a] = result.grid_min[a]; S.grid_cell[a] = result.grid_cell[a]; }
+    }
+    // 3, 4: the tree over the records and its dynamic program
+    const size_t R = record_total, inner = N + R, wide_capacity = R;
+    if (b.box.resize((inner + R) * sizeof(RefitBox)) | b.left.resize(inner * 4) | b.right.resize(inner * 4) | b.cost.resize(inner * 28) | b.split.resize(inner * 7) | b.roots_used.resize(inner * 7) |
+        b.records.resize(R * sizeof(HiprLeaf8)) | b.record_slot.resize(R * 4) | b.wide_tree.resize(wide_capacity * 4) | b.wide_child.resize(wide_capacity * 32) | b.wide_all.resize(wide_capacity * sizeof(RefitBox)) |
+        b.wide_size.resize(wide_capacity * 4) | b.wide_base.resize(wide_capacity * 4) | b.wide_slot.resize(wide_capacity * 4))
+        return HIPR_ERROR_OUT_OF_MEMORY;
+    S.record_total = record_total; S.leaf_base = uint32_t(inner); S.wide_capacity = uint32_t(wide_capacity);
+    S.box = b.box.as<RefitBox>(); S.left = b.left.as<int32_t>(); S.right = b.right.as<int32_t>(); S.cost = b.cost.as<float>(); S.split = b.split.as<uint8_t>(); S.roots_used = b.roots_used.as<uint8_t>();
+    S.records = b.records.as<HiprLeaf8>(); S.record_slot = b.record_slot.as<uint32_t>();
+    S.wide_tree = b.wide_tree.as<uint32_t>(); S.wide_child = b.wide_child.as<int32_t>(); S.wide_all = b.wide_all.as<RefitBox>();
+    S.wide_size = b.wide_size.as<uint32_t>(); S.wide_base = b.wide_base.as<uint32_t>(); S.wide_slot = b.wide_slot.as<uint32_t>();
+    hipLaunchKernelGGL(k_w8_leaf, per_reference, block, 0, stream, S);
+    if (!S.single_leaf)
+        for (uint32_t l = bvh_levels; l-- > 0;) {
+            const uint32_t first = level_first[l], count = level_first[l + 1] - first;
+            hipLaunchKernelGGL(k_w8_optimise, blocks_for(count), block, 0, stream, S, first, count);
+        }
+    // 5: the wide nodes, level by level
+    std::vector<uint32_t> wide_first, wide_count;
+    uint32_t status[W8_STATUS_WORDS] = {};
+    for (uint32_t level = 0, first = 0, count = 1; count; ++level) {
+        if (level >= W8_MAX_WIDE_LEVELS || size_t(first) + count > wide_capacity) return fail(HIPR_ERROR_HIP, "%s: the collapse left its bounds at wide level %u (%u nodes from %u, room for %zu)", who, level, count, first, wide_capacity);
+        hipLaunchKernelGGL(k_w8_prepare, blocks_for(count), block, 0, stream, S, first, count, level);
+        HIP_TRY(hipMemcpyAsync(status, S.status, (W8_STATUS_LEVELS + level + 2) * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (status[W8_STATUS_OVERFLOW]) return fail(HIPR_ERROR_HIP, "%s: more wide nodes than a tree over %u records holds", who, record_total);
+        wide_first.push_back(first); wide_count.push_back(count);
+        first += count;
+        count = status[W8_STATUS_LEVELS + level + 1];
+    }
+    const uint32_t wide_total = wide_first.back() + wide_count.back(), wide_levels = uint32_t(wide_first.size());
+    // 6: the sizes; the slots needed are known before one is written
+    for (uint32_t l = wide_levels; l-- > 0;) hipLaunchKernelGGL(k_w8_size, blocks_for(wide_count[l]), block, 0, stream, S, wide_first[l], wide_count[l]);
+    uint32_t size_below_root = 0;
+    HIP_TRY(hipMemcpyAsync(&size_below_root, S.wide_size, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const uint64_t slot_count = 1ull + size_below_root;
+    if (slot_count != uint64_t(wide_total) + record_total) return fail(HIPR_ERROR_HIP, "%s: %llu slots below the root, %u nodes and %u records", who, (unsigned long long)slot_count, wide_total, record_total);
+    if (slot_count > W8_MAX_SLOTS) return fail(HIPR_ERROR_UNSUPPORTED, "%s: the tree needs %llu slots, a node addresses %u", who, (unsigned long long)slot_count, W8_MAX_SLOTS);
+    if (slot_count > slot_capacity) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: the tree needs %llu slots, room for %u", who, (unsigned long long)slot_count, slot_capacity);
+    if (b.slots.resize(size_t(slot_count) * sizeof(HiprSlot8))) return HIPR_ERROR_OUT_OF_MEMORY;
+    S.slots = b.slots.as<HiprSlot8>();
+    // 7, 8: the places, then the slots
+    const uint32_t root_place[2] = {0u, 1u};
+    HIP_TRY(hipMemcpyAsync(S.wide_slot, &root_place[0], 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(S.wide_base, &root_place[1], 4, hipMemcpyHostToDevice, stream));
+    for (uint32_t l = 0; l < wide_levels; ++l) hipLaunchKernelGGL(k_w8_place, blocks_for(wide_count[l]), block, 0, stream, S, wide_first[l], wide_count[l]);
+    hipLaunchKernelGGL(k_w8_emit_nodes, blocks_for(wide_total), block, 0, stream, S, wide_total);
+    hipLaunchKernelGGL(k_w8_emit_leaves, blocks_for(record_total), block, 0, stream, S);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    result.slot_count = uint32_t(slot_count);
+    result.height = wide_levels;
+    result.node_count = wide_total; result.leaf_count = record_total; result.paired_leaves = status[W8_STATUS_PAIRED];
+    return HIPR_OK;
+}
+// The scratch every collapse starts from, sized and cleared (queued on `stream`).
+static int collapse_scratch_for(CollapseScratch& b, size_t T, hipStream_t stream) {
+    const size_t scan_blocks = (T + W8_BLOCK - 1) / W8_BLOCK;
+    if (b.counts.resize(T * 4) | b.block_sums.resize((scan_blocks + 1) * 4) | b.partial.resize(scan_blocks * 6 * sizeof(RefitBound)) | b.bounds.resize(6 * sizeof(RefitBound)) | b.status.resize(W8_STATUS_WORDS * 4))
+        return HIPR_ERROR_OUT_OF_MEMORY;
+    HIP_TRY(hipMemsetAsync(b.counts.ptr, 0, T * 4, stream));
+    HIP_TRY(hipMemsetAsync(b.block_sums.ptr, 0, (scan_blocks + 1) * 4, stream));
+    HIP_TRY(hipMemsetAsync(b.status.ptr, 0, W8_STATUS_WORDS * 4, stream));
     return HIPR_OK;
 }
 
@@ -1849,85 +2043,13 @@ int hipr_build_wide8(HiprContext* c, const HiprBvhNode* nodes, uint32_t node_cou
     S.triangles = b.triangles.as<HiprTriangle>(); S.order = order ? b.order.as<uint32_t>() : nullptr; S.triangle_count = triangle_count;
     S.level_nodes = b.level_nodes.as<uint32_t>(); S.reachable = reachable; S.single_leaf = input.single_leaf ? 1u : 0u;
     S.counts = b.counts.as<uint32_t>(); S.block_sums = b.block_sums.as<uint32_t>(); S.status = b.status.as<uint32_t>();
-    const dim3 block(W8_BLOCK), per_triangle{uint32_t(scan_blocks)}, per_reference((2u * reachable + W8_BLOCK - 1) / W8_BLOCK);
-    auto blocks_for = [](uint32_t threads) { return dim3((threads + W8_BLOCK - 1) / W8_BLOCK); };
-    // 1, 2: the bounds and the record numbers; the host reads both together
-    hipLaunchKernelGGL(k_w8_bounds, per_triangle, block, 0, stream, S.triangles, triangle_count, b.partial.as<RefitBound>(), S.status);
-    hipLaunchKernelGGL(k_refit_bounds_final, dim3(1), block, 0, stream, b.partial.as<RefitBound>(), uint32_t(scan_blocks), b.bounds.as<RefitBound>());
-    hipLaunchKernelGGL(k_w8_count_leaf, per_reference, block, 0, stream, S);
-    hipLaunchKernelGGL(k_w8_scan_local, per_triangle, block, 0, stream, S);
-    hipLaunchKernelGGL(k_build_scan_sums, dim3(1), block, 0, stream, S.block_sums, uint32_t(scan_blocks + 1));
-    RefitBound bounds[6];
-    uint32_t record_total = 0, not_finite = 0;
-    HIP_TRY(hipMemcpyAsync(bounds, b.bounds.ptr, sizeof(bounds), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(&record_total, S.block_sums + scan_blocks, 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(&not_finite, S.status + W8_STATUS_NOT_FINITE, 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (not_finite) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_wide8: a triangle corner or a child box is not finite");
-    if (record_total == 0 || record_total > triangle_count) return fail(HIPR_ERROR_HIP, "hipr_build_wide8: %u records of %u triangles", record_total, triangle_count);
     HiprWide8BuildResult result = {};
-    {
-        const float lo[3] = {bounds[0].v, bounds[1].v, bounds[2].v}, hi[3] = {bounds[3].v, bounds[4].v, bounds[5].v};
-        refit_grid(lo, hi, result.grid_min, result.grid_cell);
-        for (int a = 0; a < 3; ++a) { S.grid_min[a] = result.grid_min[a]; S.grid_cell[a] = result.grid_cell[a]; }
-    }
-    // 3, 4: the tree over the records and its dynamic program
-    const size_t R = record_total, inner = N + R, wide_capacity = R;
-    if (b.box.resize((inner + R) * sizeof(RefitBox)) | b.left.resize(inner * 4) | b.right.resize(inner * 4) | b.cost.resize(inner * 28) | b.split.resize(inner * 7) | b.roots_used.resize(inner * 7) |
-        b.records.resize(R * sizeof(HiprLeaf8)) | b.record_slot.resize(R * 4) | b.wide_tree.resize(wide_capacity * 4) | b.wide_child.resize(wide_capacity * 32) | b.wide_all.resize(wide_capacity * sizeof(RefitBox)) |
-        b.wide_size.resize(wide_capacity * 4) | b.wide_base.resize(wide_capacity * 4) | b.wide_slot.resize(wide_capacity * 4))
-        return HIPR_ERROR_OUT_OF_MEMORY;
-    S.record_total = record_total; S.leaf_base = uint32_t(inner); S.wide_capacity = uint32_t(wide_capacity);
-    S.box = b.box.as<RefitBox>(); S.left = b.left.as<int32_t>(); S.right = b.right.as<int32_t>(); S.cost = b.cost.as<float>(); S.split = b.split.as<uint8_t>(); S.roots_used = b.roots_used.as<uint8_t>();
-    S.records = b.records.as<HiprLeaf8>(); S.record_slot = b.record_slot.as<uint32_t>();
-    S.wide_tree = b.wide_tree.as<uint32_t>(); S.wide_child = b.wide_child.as<int32_t>(); S.wide_all = b.wide_all.as<RefitBox>();
-    S.wide_size = b.wide_size.as<uint32_t>(); S.wide_base = b.wide_base.as<uint32_t>(); S.wide_slot = b.wide_slot.as<uint32_t>();
-    hipLaunchKernelGGL(k_w8_leaf, per_reference, block, 0, stream, S);
-    if (!input.single_leaf)
-        for (uint32_t l = bvh_levels; l-- > 0;) {
-            const uint32_t first = input.level_first[l], count = input.level_first[l + 1] - first;
-            hipLaunchKernelGGL(k_w8_optimise, blocks_for(count), block, 0, stream, S, first, count);
-        }
-    // 5: the wide nodes, level by level
-    std::vector<uint32_t> wide_first, wide_count;
-    uint32_t status[W8_STATUS_WORDS] = {};
-    for (uint32_t level = 0, first = 0, count = 1; count; ++level) {
-        if (level >= W8_MAX_WIDE_LEVELS || size_t(first) + count > wide_capacity) return fail(HIPR_ERROR_HIP, "hipr_build_wide8: the collapse left its bounds at wide level %u (%u nodes from %u, room for %zu)", level, count, first, wide_capacity);
-        hipLaunchKernelGGL(k_w8_prepare, blocks_for(count), block, 0, stream, S, first, count, level);
-        HIP_TRY(hipMemcpyAsync(status, S.status, (W8_STATUS_LEVELS + level + 2) * 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (status[W8_STATUS_OVERFLOW]) return fail(HIPR_ERROR_HIP, "hipr_build_wide8: more wide nodes than a tree over %u records holds", record_total);
-        wide_first.push_back(first); wide_count.push_back(count);
-        first += count;
-        count = status[W8_STATUS_LEVELS + level + 1];
-    }
-    const uint32_t wide_total = wide_first.back() + wide_count.back(), wide_levels = uint32_t(wide_first.size());
-    // 6: the sizes; the slots needed are known before one is written
-    for (uint32_t l = wide_levels; l-- > 0;) hipLaunchKernelGGL(k_w8_size, blocks_for(wide_count[l]), block, 0, stream, S, wide_first[l], wide_count[l]);
-    uint32_t size_below_root = 0;
-    HIP_TRY(hipMemcpyAsync(&size_below_root, S.wide_size, 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    const uint64_t slot_count = 1ull + size_below_root;
-    if (slot_count != uint64_t(wide_total) + record_total) return fail(HIPR_ERROR_HIP, "hipr_build_wide8: %llu slots below the root, %u nodes and %u records", (unsigned long long)slot_count, wide_total, record_total);
-    if (slot_count > W8_MAX_SLOTS) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_build_wide8: the tree needs %llu slots, a node addresses %u", (unsigned long long)slot_count, W8_MAX_SLOTS);
-    if (slot_count > slot_capacity) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_build_wide8: the tree needs %llu slots, room for %u", (unsigned long long)slot_count, slot_capacity);
-    if (b.slots.resize(size_t(slot_count) * sizeof(HiprSlot8))) return HIPR_ERROR_OUT_OF_MEMORY;
-    S.slots = b.slots.as<HiprSlot8>();
-    // 7, 8: the places, then the slots
-    const uint32_t root_place[2] = {0u, 1u};
-    HIP_TRY(hipMemcpyAsync(S.wide_slot, &root_place[0], 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(S.wide_base, &root_place[1], 4, hipMemcpyHostToDevice, stream));
-    for (uint32_t l = 0; l < wide_levels; ++l) hipLaunchKernelGGL(k_w8_place, blocks_for(wide_count[l]), block, 0, stream, S, wide_first[l], wide_count[l]);
-    hipLaunchKernelGGL(k_w8_emit_nodes, blocks_for(wide_total), block, 0, stream, S, wide_total);
-    hipLaunchKernelGGL(k_w8_emit_leaves, blocks_for(record_total), block, 0, stream, S);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
+    if (int st = collapse_on_the_device(c, "hipr_build_wide8", S, input.level_first, slot_capacity, result)) return st;
+    const uint32_t record_total = result.leaf_count,wide_total = result.node_count, wide_levels = result.height;
+    const uint64_t slot_count = result.slot_count;
     const auto t2 = std::chrono::steady_clock::now();
     HIP_TRY(hipMemcpyAsync(out_slots, S.slots, size_t(slot_count) * sizeof(HiprSlot8), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    result.slot_count = uint32_t(slot_count);
-    result.height = wide_levels;
-    result.node_count = wide_total; result.leaf_count = record_total; result.paired_leaves = status[W8_STATUS_PAIRED];
     *out = result;
     const auto t3 = std::chrono::steady_clock::now();
     b.validate_ms = std::chrono::duration<double, std::milli>(t0 - t_validate).count();
@@ -1946,6 +2068,123 @@ int hipr_debug_collapse_times(HiprContext* c, double* out4_ms) {
     return HIPR_OK;
 }
 
+// The trees of the resident scene rebuilt on the device, in place, from the triangles it holds (scene_rebuild.h): flatten order, the BVH2 build, the hand-over, the
+// collapse -- all in scratch, where every refusal still leaves the scene as the call found it -- and then ResidentScene::install_rebuilt_trees.
+int hipr_rebuild_scene_trees(HiprContext* c, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_order, HiprSlot8* out_slots, uint32_t slot_capacity,
+                             HiprSceneRebuildResult* out) {
+    if (int st = check_context(c)) return st;
+    ResidentScene& r = c->scene;
+    if (!r.ready && !r.awaits_rebuild) return fail(HIPR_ERROR_NOT_READY, "hipr_rebuild_scene_trees: no scene uploaded, or one a failed call left behind");
+    const uint32_t count = r.args.triangle_count, instance_count = uint32_t(r.uploaded_instances.size());
+    // the conditions hipr_refit_scene_transforms refuses on: the arrays another search walks are the ones this call leaves stale, and the exhaustive search's items are the host's
+    if (r.wide8.slot_count == 0 || !c->use_wide8() || r.args.trace_item_count != 0 || count > 0x55555555u || count == 0)
+        return fail(HIPR_ERROR_UNSUPPORTED, "hipr_rebuild_scene_trees: the resident scene is not traced through the 8-wide tree; rebuild on the host and call hipr_upload_scene");
+    if (count > BUILD_MAX_TRIANGLES) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_rebuild_scene_trees: %u triangles, a leaf reference holds %u", count, BUILD_MAX_TRIANGLES);
+    const uint32_t nodes_needed = std::max(std::max(count, 1u) - 1u, 1u), slots_needed = uint32_t(std::min<uint64_t>(2ull * count, W8_MAX_SLOTS));
+    if (!out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_rebuild_scene_trees: null result");
+    if (out_nodes && node_capacity < nodes_needed) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_rebuild_scene_trees: room for %u nodes, %u triangles can need %u", node_capacity, count, nodes_needed);
+    if (out_slots && slot_capacity < slots_needed) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_rebuild_scene_trees: room for %u slots, %u triangles can need %u", slot_capacity, count, slots_needed);
+    if (int finish_status = finish_all(c)) return finish_status;      // no pending pass may go on over the new trees
+    const uint32_t depth_limit = std::max(max_depth, 8u);
+    BuildScratch& b = c->build;
+    CollapseScratch& w = c->collapse;
+    RebuildScratch& x = c->rebuild;
+    const BuildScratchGuard build_guard{b};
+    const CollapseScratchGuard collapse_guard{w};
+    const RebuildScratchGuard rebuild_guard{x};
+    hipStream_t stream = c->stream;
+    c->break_chain(stream);
+    const auto t0 = std::chrono::steady_clock::now();
+
+    // the flatten order
+    const size_t n = count;
+    if (b.triangles.resize(n * sizeof(HiprTriangle)) | x.flat_class.resize(n) | x.claim.resize(n * 4) | x.instance_counts.resize(size_t(instance_count) * 4) | x.first.resize((size_t(instance_count) + 1) * 4) |
+        x.status.resize(REBUILD_STATUS_WORDS * 4))
+        return HIPR_ERROR_OUT_OF_MEMORY;
+    HIP_TRY(hipMemsetAsync(x.claim.ptr, 0, n * 4, stream));
+    HIP_TRY(hipMemsetAsync(x.instance_counts.ptr, 0, size_t(instance_count) * 4, stream));
+    HIP_TRY(hipMemsetAsync(x.status.ptr, 0, REBUILD_STATUS_WORDS * 4, stream));
+    const RebuildArrays a = {r.triangles.as<HiprTriangle>(), r.triangle_class.as<uint8_t>(), count, instance_count, x.instance_counts.as<uint32_t>(), x.first.as<uint32_t>(),
+                             b.triangles.as<HiprTriangle>(), x.flat_class.as<uint8_t>(), x.claim.as<uint32_t>(), x.status.as<uint32_t>()};
+    const dim3 block(REBUILD_BLOCK), per_triangle((count + REBUILD_BLOCK - 1) / REBUILD_BLOCK);
+    hipLaunchKernelGGL(k_rebuild_count, per_triangle, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> first(size_t(instance_count) + 1, 0u);
+    uint32_t claim_status = 0;
+    HIP_TRY(hipMemcpyAsync(first.data() + 1, x.instance_counts.ptr, size_t(instance_count) * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < instance_count; ++i) { total += first[i + 1]; first[i + 1] = uint32_t(total); }
+    if (total != count) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_rebuild_scene_trees: %llu of %u resident triangles belong to one of the %u instances", (unsigned long long)total, count, instance_count);
+    HIP_TRY(hipMemcpyAsync(x.first.ptr, first.data(), first.size() * 4, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_rebuild_scatter, per_triangle, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&claim_status, x.status.as<uint32_t>() + REBUILD_STATUS_CLAIM, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (claim_status) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_rebuild_scene_trees: two resident triangles claim one flatten position (instance, primitive); rebuild on the host");
+    const auto t1 = std::chrono::steady_clock::now();
+
+    // the BVH2 over the flat array
+    Bvh2Built built;
+    std::chrono::steady_clock::time_point unused;
+    if (int st = build_bvh2_on_the_device(c, "hipr_rebuild_scene_trees", nullptr, b.triangles.as<HiprTriangle>(), count, depth_limit, built, unused)) return st;
+    uint32_t build_status[STATUS_LEVELS] = {};
+    HIP_TRY(hipMemcpyAsync(build_status, b.status.ptr, STATUS_LEVELS * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const uint32_t node_count = built.node_count, deepest = build_status[STATUS_DEEPEST];
+    const uint32_t bvh_levels = std::max<uint32_t>(uint32_t(built.level_nodes.size()), 1u);
+    if (bvh_levels > W8_MAX_LEVELS || deepest + 1u > 64u)
+        return fail(HIPR_ERROR_UNSUPPORTED, "hipr_rebuild_scene_trees: the new BVH2 has %u levels of nodes and its deepest leaf at %u, the kernels walk 64", bvh_levels, deepest);
+    const auto t2 = std::chrono::steady_clock::now();
+
+    // the hand-over and the collapse
+    if (x.level_nodes.resize(size_t(node_count) * 4)) return HIPR_ERROR_OUT_OF_MEMORY;
+    if (int st = collapse_scratch_for(w, n, stream)) return st;
+    hipLaunchKernelGGL(k_rebuild_levels, dim3((node_count + REBUILD_BLOCK - 1) / REBUILD_BLOCK), block, 0, stream, b.place.as<uint32_t>(), x.level_nodes.as<uint32_t>(), node_count);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> level_first(size_t(bvh_levels) + 1, 0u);
+    if (built.level_nodes.empty()) level_first[1] = 1u;      // at most three triangles: the root references one leaf twice
+    else for (uint32_t l = 0; l < bvh_levels; ++l) level_first[l + 1] = level_first[l] + built.level_nodes[l];
+    W8State S = {};
+    S.nodes = b.out_nodes.as<HiprBvhNode>(); S.node_count = node_count;
+    S.triangles = b.triangles.as<HiprTriangle>(); S.order = b.order.as<uint32_t>(); S.triangle_count = count;
+    S.level_nodes = x.level_nodes.as<uint32_t>(); S.reachable = node_count; S.single_leaf = built.level_nodes.empty() ? 1u : 0u;
+    S.counts = w.counts.as<uint32_t>(); S.block_sums = w.block_sums.as<uint32_t>(); S.status = w.status.as<uint32_t>();
+    HiprWide8BuildResult wide8 = {};
+    if (int st = collapse_on_the_device(c, "hipr_rebuild_scene_trees", S, level_first, 0xFFFFFFFFu, wide8)) return st == HIPR_ERROR_INVALID_ARGUMENT ? HIPR_ERROR_UNSUPPORTED : st;
+    if (wide8.height > 33u) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_rebuild_scene_trees: the new 8-wide tree is %u levels high, the kernels' stacks hold 33; rebuild on the host", wide8.height);
+    if ((out_nodes && node_count > node_capacity) || (out_slots && wide8.slot_count > slot_capacity)) return fail(HIPR_ERROR_HIP, "hipr_rebuild_scene_trees: %u nodes and %u slots built, more than the bounds checked", node_count, wide8.slot_count);
+    std::vector<HiprSlot8> host_slots(wide8.slot_count);      // the refit's lists are made from the host's copy, as at upload
+    HIP_TRY(hipMemcpyAsync(host_slots.data(), S.slots, host_slots.size() * sizeof(HiprSlot8), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const auto t3 = std::chrono::steady_clock::now();
+
+    // nothing refuses from here on: the new resident arrays
+    const ResidentScene::RebuiltTrees trees = {b.triangles.as<HiprTriangle>(), x.flat_class.as<uint8_t>(), b.order.as<uint32_t>(), b.out_nodes.as<HiprBvhNode>(), node_count, deepest,
+                                               S.slots, host_slots.data(), wide8};
+    if (int st = r.install_rebuilt_trees(trees, stream)) return st;
+    const auto t4 = std::chrono::steady_clock::now();
+    if (out_nodes) HIP_TRY(hipMemcpyAsync(out_nodes, b.out_nodes.ptr, size_t(node_count) * sizeof(HiprBvhNode), hipMemcpyDeviceToHost, stream));
+    if (out_order) HIP_TRY(hipMemcpyAsync(out_order, b.order.ptr, n * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (out_slots) std::memcpy(out_slots, host_slots.data(), host_slots.size() * sizeof(HiprSlot8));
+    out->node_count = node_count; out->deepest = deepest; out->wide8 = wide8; out->half_area = r.uploaded_half_area;
+    const auto t5 = std::chrono::steady_clock::now();
+    auto ms = [](std::chrono::steady_clock::time_point from, std::chrono::steady_clock::time_point to) { return std::chrono::duration<double, std::milli>(to - from).count(); };
+    x.flatten_ms = ms(t0, t1); x.bvh2_ms = ms(t1, t2); x.collapse_ms = ms(t2, t3); x.install_ms = ms(t3, t4); x.readback_ms = ms(t4, t5);
+    if (std::getenv("HIPR_BVH_TIMING"))
+        fprintf(stderr, "[hipr] hipr_rebuild_scene_trees: %u triangles, %u nodes, %u slots: flatten order %.3f ms, BVH2 %.3f ms, collapse + slots to the host %.3f ms, new resident arrays %.3f ms, read-back %.3f ms\n", count, node_count,
+                wide8.slot_count, x.flatten_ms, x.bvh2_ms, x.collapse_ms, x.install_ms, x.readback_ms);
+    return HIPR_OK;
+}
+
+int hipr_debug_rebuild_times(HiprContext* c, double* out5_ms) {
+    if (!c || !out5_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_rebuild_times: null argument");
+    const RebuildScratch& x = c->rebuild;
+    out5_ms[0] = x.flatten_ms; out5_ms[1] = x.bvh2_ms; out5_ms[2] = x.collapse_ms; out5_ms[3] = x.install_ms; out5_ms[4] = x.readback_ms;
+    return HIPR_OK;
+}
+
 int hipr_debug_read_scene_buffer(HiprContext* c, int which, void* out, uint64_t capacity_bytes) {
     if (int st = check_context(c)) return st;
     if (!out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: null output");
@@ -1959,6 +2198,7 @@ int hipr_debug_read_scene_buffer(HiprContext* c, int which, void* out, uint64_t 
     else if (which == HIPR_SCENE_BUFFER_TRIANGLE_CLASS) { from = c->scene.triangle_class.ptr; bytes = uint64_t(c->scene.args.triangle_count); }
     else if (which == HIPR_SCENE_BUFFER_MATERIALS) { from = c->scene.materials.ptr; bytes = uint64_t(c->scene.uploaded_materials.size()) * sizeof(HiprMaterial); }
     else if (which == HIPR_SCENE_BUFFER_INSTANCES) { from = c->scene.instances.ptr; bytes = uint64_t(c->scene.uploaded_instances.size()) * sizeof(HiprInstance); }
+    else if (which == HIPR_SCENE_BUFFER_NODES) { from = c->scene.nodes.ptr; bytes = uint64_t(c->scene.args.node_count) * sizeof(HiprBvhNode); }
     else return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: unknown buffer %d", which);
     if (capacity_bytes < bytes) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: %llu bytes needed, %llu given", (unsigned long long)bytes, (unsigned long long)capacity_bytes);
     if (int finish_status = finish_all(c)) return finish_status;

@@ -30,6 +30,11 @@ def load_host_library() -> C.CDLL:
     lib.hiprh_scene_model_pose.argtypes = [vp, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_uint), C.POINTER(C.c_float), C.c_uint]
     lib.hiprh_scene_update_materials.argtypes = [vp, C.POINTER(capi.HiprMaterialUpdate), C.c_uint, C.POINTER(capi.HiprInstanceMaterial), C.c_uint]
     lib.hiprh_scene_rebuild.argtypes = [vp]
+    lib.hiprh_scene_stage_model.argtypes = [vp, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float]
+    lib.hiprh_scene_adopt_trees.argtypes = [vp, vp, C.c_uint, vp, C.c_uint, vp, C.POINTER(capi.HiprWide8BuildResult)]
+    lib.hiprh_scene_order.argtypes = [vp, C.POINTER(C.c_uint)]
+    lib.hiprh_scene_order.restype = C.POINTER(C.c_uint)
+    lib.hiprh_scene_rebuild_counts.argtypes = [vp, C.POINTER(C.c_uint)]
     lib.hiprh_scene_materials.argtypes = [vp, C.POINTER(C.c_uint)]
     lib.hiprh_scene_materials.restype = C.POINTER(capi.HiprMaterial)
     lib.hiprh_scene_instances.argtypes = [vp, C.POINTER(C.c_uint)]
@@ -199,6 +204,46 @@ class Scene:
         """A fresh build (triangle flags, BVH2, 4-wide and 8-wide trees) over the instances and materials as they stand."""
         if self.lib.hiprh_scene_rebuild(self.handle) != 0:
             raise capi.HiprError("hiprh_scene_rebuild failed")
+
+    def stage_model(self, model_index: int, translation, rotation=(0.0, 0.0, 0.0, 1.0), scale: float = 1.0) -> bool:
+        """SceneBuilder::stage_model_transforms: the pose is recorded in the instances only; `desc` must not be read until adopt_trees, move_model or rebuild has caught
+        up. False when the pose turns an instance inside out."""
+        status = self.lib.hiprh_scene_stage_model(self.handle, model_index, (C.c_float * 3)(*translation), (C.c_float * 4)(*rotation), scale)
+        if status < 0:
+            raise capi.HiprError("hiprh_scene_stage_model failed")
+        return status == 1
+
+    def adopt_trees(self, nodes: np.ndarray, order: np.ndarray, deepest: int, slots: np.ndarray, wide8) -> bool:
+        """SceneBuilder::adopt_rebuilt_trees: the trees Context.rebuild_scene_trees made -- `nodes` (n, 16) uint32, `order`, `deepest`, `slots` (s, 16) uint32, `wide8` a
+        capi.HiprWide8BuildResult or the dict build_wide8 returns -- taken over in place of a rebuild. False, with nothing touched, when they do not fit the scene."""
+        nodes = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 16)
+        order = np.ascontiguousarray(order, np.uint32)
+        slots = np.ascontiguousarray(slots, np.uint32).reshape(-1, 16)
+        if isinstance(wide8, dict):
+            wide8 = capi.HiprWide8BuildResult(wide8["slot_count"], wide8["height"], (C.c_float * 3)(*[float(v) for v in wide8["grid_min"]]), (C.c_float * 3)(*[float(v) for v in wide8["grid_cell"]]),
+                                              wide8["node_count"], wide8["leaf_count"], wide8["paired_leaves"])
+        if len(order) != self.desc_triangle_count() or wide8.slot_count != len(slots):
+            order_pointer = None      # lengths that do not fit are the library's to refuse: it reads none of the arrays then
+        else:
+            order_pointer = C.c_void_p(order.ctypes.data)
+        status = self.lib.hiprh_scene_adopt_trees(self.handle, C.c_void_p(nodes.ctypes.data), len(nodes), order_pointer, int(deepest), C.c_void_p(slots.ctypes.data), C.byref(wide8))
+        if status < 0:
+            raise capi.HiprError("hiprh_scene_adopt_trees failed")
+        return status == 1
+
+    def desc_triangle_count(self) -> int:
+        return len(self.order())
+
+    def order(self) -> np.ndarray:
+        """The builder's current order: order()[k] is the position, in the order the builder flattens in, of the triangle desc.triangles[k]."""
+        count = C.c_uint()
+        pointer = self.lib.hiprh_scene_order(self.handle, C.byref(count))
+        return np.ctypeslib.as_array(pointer, shape=(count.value,)).astype(np.uint32) if count.value else np.zeros(0, np.uint32)
+
+    def rebuild_counts(self) -> dict:
+        out = (C.c_uint * 2)()
+        self.lib.hiprh_scene_rebuild_counts(self.handle, out)
+        return dict(adopted=int(out[0]), refused=int(out[1]))
 
     def materials(self) -> list:
         """Copies of the scene's materials (capi.HiprMaterial), slot 0 the invalid material."""

@@ -213,6 +213,7 @@ struct Renderer::Implementation {
     Renderer::SceneUpdateCounts scene_updates = {0, 0, 0, 0};
     Renderer::SceneBuildCounts retired_builds = {0, 0};      // of the scene builders that are gone
     Renderer::SceneCollapseCounts retired_collapses = {0, 0};
+    Renderer::SceneRebuildCounts scene_rebuilds = {0, 0};
 
     bool is_valid() const { return device_ID >= 0; }
 
@@ -358,10 +359,45 @@ struct Renderer::Implementation {
             else if (result.needs_rebuild || result.child_half_area > 1.5 * result.uploaded_half_area) rebuild = true;
             else ++scene_updates.device_refits;
         }
-        if (rebuild) {
+        if (rebuild && !rebuild_on_the_device()) {
             scene->rebuild();
             for (CameraState& c : per_camera_state) c.scene_uploaded = false;
         }
+        return true;
+    }
+
+    // HIPR_DEVICE_REBUILD=1: a move that asks for a rebuild is answered where the triangles already are (hipr_rebuild_scene_trees; csrc/scene_rebuild.h) instead of a
+    // flatten, a build and an upload of every pool. The first camera with an uploaded scene rebuilds with outputs and the scene builder adopts them
+    // (SceneBuilder::adopt_rebuilt_trees: its description is then what rebuild() leaves); every other uploaded camera rebuilds without outputs -- the same kernels
+    // over the same arrays give the same bytes -- and one whose call fails takes the upload. false: a decline before the adoption, or the variable unset; the caller
+    // takes the host path whole. Off by default until profiles/device_rebuild_vs_host.txt says otherwise.
+    bool rebuild_on_the_device() {
+        const char* wanted = std::getenv("HIPR_DEVICE_REBUILD");
+        if (!wanted || std::atoi(wanted) == 0) return false;
+        CameraState* first = nullptr;
+        for (CameraState& c : per_camera_state)
+            if (c.context && c.scene_uploaded) { first = &c; break; }
+        if (!first) return false;
+        const uint32_t n = scene->desc_triangle_count();
+        const uint32_t node_capacity = std::max(std::max(n, 1u) - 1u, 1u), slot_capacity = uint32_t(std::min<uint64_t>(2ull * n, 0xFFFFFFull));
+        // the pages of this room are touched only where the device's arrays are copied to
+        struct Room { void* p; ~Room() { std::free(p); } };
+        Room nodes = {std::malloc(size_t(node_capacity) * sizeof(HiprBvhNode))}, order = {std::malloc(size_t(std::max(n, 1u)) * 4)}, slots = {std::malloc(size_t(std::max(slot_capacity, 1u)) * sizeof(HiprSlot8))};
+        HiprSceneRebuildResult built = {};
+        const bool rebuilt = nodes.p && order.p && slots.p &&
+                             hipr_group_rebuild_scene_trees(first->context, scene->bvh_max_depth_limit(), static_cast<HiprBvhNode*>(nodes.p), node_capacity, static_cast<uint32_t*>(order.p),
+                                                            static_cast<HiprSlot8*>(slots.p), slot_capacity, &built) == HIPR_OK;
+        if (!rebuilt || !scene->adopt_rebuilt_trees(static_cast<const HiprBvhNode*>(nodes.p), built.node_count, static_cast<const uint32_t*>(order.p), built.deepest,
+                                                    static_cast<const HiprSlot8*>(slots.p), built.wide8)) {
+            ++scene_rebuilds.declined_rebuilds;
+            return false;
+        }
+        for (CameraState& c : per_camera_state) {
+            if (&c == first || !c.context || !c.scene_uploaded) continue;
+            HiprSceneRebuildResult same = {};
+            if (hipr_group_rebuild_scene_trees(c.context, scene->bvh_max_depth_limit(), nullptr, 0, nullptr, nullptr, 0, &same) != HIPR_OK) c.scene_uploaded = false;
+        }
+        ++scene_rebuilds.device_rebuilds;
         return true;
     }
 
@@ -710,6 +746,7 @@ void Renderer::set_AI_denoiser_flags(AIDenoiserFlags flags) { m_impl->AI_denoise
 void Renderer::handle_updates() { m_impl->handle_updates(); }
 
 Renderer::SceneUpdateCounts Renderer::scene_update_counts() const { return m_impl->scene_updates; }
+Renderer::SceneRebuildCounts Renderer::scene_rebuild_counts() const { return m_impl->scene_rebuilds; }
 Renderer::SceneCollapseCounts Renderer::scene_collapse_counts() const {
     SceneCollapseCounts counts = m_impl->retired_collapses;
     if (m_impl->scene) { counts.device_collapses += m_impl->scene->collapse_counts().device_collapses; counts.declined_collapses += m_impl->scene->collapse_counts().declined_collapses; }

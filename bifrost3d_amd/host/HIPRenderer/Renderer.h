@@ -106,6 +106,11 @@ public:
     // The same for the 8-wide collapse (hipr_build_wide8; HIPR_DEVICE_COLLAPSE=0 keeps it on the host under HIPR_DEVICE_BUILD=1).
     struct SceneCollapseCounts { unsigned int device_collapses, declined_collapses; };
     SceneCollapseCounts scene_collapse_counts() const;
+    // Moves that asked for a rebuild -- the refit stretched the tree past the 1.5 rule, or a pair parted -- whose trees the devices rebuilt in place from the triangles
+    // they hold (HIPR_DEVICE_REBUILD=1, hipr_rebuild_scene_trees) and the scene builder adopted, and moves where a device or the builder declined, so that the host
+    // rebuilt and every camera took the upload.
+    struct SceneRebuildCounts { unsigned int device_rebuilds, declined_rebuilds; };
+    SceneRebuildCounts scene_rebuild_counts() const;
 
 private:
     Renderer(const std::vector<int>& device_IDs, const std::filesystem::path& data_directory);

@@ -204,12 +204,18 @@ void SceneBuilder::finalize(uint32_t bvh_max_depth) {
     const auto t_flat = std::chrono::steady_clock::now();
     Bvh2SourceReport report;      // fall_back: a scene builder's build carries on with the host's stage
     Wide8SourceReport wide8_report;
-    m_bvh = build_bvh(world, bvh_max_depth, m_bvh2_source, &report, m_wide8_source, &wide8_report);
+    build_trees_over(world, m_bvh2_source, report, m_wide8_source, wide8_report);
     if (report.used) ++m_build_counts.device_builds; else if (report.asked) ++m_build_counts.declined_builds;
     if (wide8_report.used) ++m_collapse_counts.device_collapses; else if (wide8_report.asked) ++m_collapse_counts.declined_collapses;
     if (std::getenv("HIPR_BVH_TIMING"))
         fprintf(stderr, "[hipr] finalize: %zu triangles: flatten %.3f s, build_bvh %.3f s (BVH2 source: %s, %.3f s)\n", world.size(), std::chrono::duration<double>(t_flat - t_start).count(),
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t_flat).count(), report.used ? "used" : (report.asked ? "declined" : "none"), report.seconds);
+}
+
+// The trees over the triangles in flatten order, the triangles in the trees' order and the description: what finalize() does after its flatten, and what
+// adopt_rebuilt_trees() does with sources that hand back the trees it was given.
+void SceneBuilder::build_trees_over(const std::vector<HiprTriangle>& world, const Bvh2Source& bvh2_source, Bvh2SourceReport& report, const Wide8Source& wide8_source, Wide8SourceReport& wide8_report) {
+    m_bvh = build_bvh(world, m_bvh_max_depth_limit, bvh2_source, &report, wide8_source, &wide8_report);
     m_built_bvh_area = bvh_child_area(m_bvh);
     m_triangles.resize(world.size());
     for (size_t k = 0; k < world.size(); ++k) m_triangles[k] = world[m_bvh.order[k]];
@@ -294,6 +300,18 @@ bool SceneBuilder::apply_staged_transforms(double rebuild_threshold) {
         finalize(m_bvh_max_depth_limit);
         return false;
     }
+    move_triangles(moved);
+    const double area = refit_bvh(m_bvh, m_triangles);
+    for (int a = 0; a < 3; ++a) { m_desc.wide8_grid_min[a] = m_bvh.wide8.grid_min[a]; m_desc.wide8_grid_cell[a] = m_bvh.wide8.grid_cell[a]; }     // the refit moves the grid with the scene
+    if (area < 0.0 || (m_built_bvh_area > 0.0 && area > rebuild_threshold * m_built_bvh_area)) {      // area < 0: a leaf record of the 8-wide tree could not be refitted
+        finalize(m_bvh_max_depth_limit);      // the instances already carry the new transforms
+        return false;
+    }
+    return true;
+}
+
+// The world-space corners of the triangles of the instances flagged in `moved`, recomputed in place from the instances' matrices, and the scene's bounds.
+void SceneBuilder::move_triangles(const std::vector<bool>& moved) {
     m_bounds = AABB::invalid();
     for (HiprTriangle& t : m_triangles) {
         if (moved[t.instance_index]) {
@@ -311,12 +329,78 @@ bool SceneBuilder::apply_staged_transforms(double rebuild_threshold) {
         m_bounds.grow_to_contain(Vector3f(t.v1[0], t.v1[1], t.v1[2]));
         m_bounds.grow_to_contain(Vector3f(t.v2[0], t.v2[1], t.v2[2]));
     }
-    const double area = refit_bvh(m_bvh, m_triangles);
-    for (int a = 0; a < 3; ++a) { m_desc.wide8_grid_min[a] = m_bvh.wide8.grid_min[a]; m_desc.wide8_grid_cell[a] = m_bvh.wide8.grid_cell[a]; }     // the refit moves the grid with the scene
-    if (area < 0.0 || (m_built_bvh_area > 0.0 && area > rebuild_threshold * m_built_bvh_area)) {      // area < 0: a leaf record of the 8-wide tree could not be refitted
-        finalize(m_bvh_max_depth_limit);      // the instances already carry the new transforms
-        return false;
+}
+
+namespace {
+// Sources that hand build_bvh the trees a device rebuild made (hipr_rebuild_scene_trees), so that the 4-wide collapse, the depth and the description go on from
+// them exactly as after the host's own stages.
+struct AdoptedTrees { const HiprBvhNode* nodes; uint32_t node_count; const uint32_t* order; uint32_t deepest; const HiprSlot8* slots; HiprWide8BuildResult wide8; };
+int adopted_bvh2(void* context, const HiprTriangle*, uint32_t count, uint32_t, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_node_count, uint32_t* out_order, uint32_t* out_deepest) {
+    const AdoptedTrees& t = *static_cast<const AdoptedTrees*>(context);
+    if (t.node_count > node_capacity) return HIPR_ERROR_INVALID_ARGUMENT;
+    std::copy(t.nodes, t.nodes + t.node_count, out_nodes);
+    std::copy(t.order, t.order + count, out_order);
+    *out_node_count = t.node_count; *out_deepest = t.deepest;
+    return HIPR_OK;
+}
+int adopted_wide8(void* context, const HiprBvhNode*, uint32_t, const HiprTriangle*, const uint32_t*, uint32_t, HiprSlot8* out_slots, uint32_t slot_capacity, HiprWide8BuildResult* out) {
+    const AdoptedTrees& t = *static_cast<const AdoptedTrees*>(context);
+    if (t.wide8.slot_count > slot_capacity) return HIPR_ERROR_INVALID_ARGUMENT;
+    std::copy(t.slots, t.slots + t.wide8.slot_count, out_slots);
+    *out = t.wide8;
+    return HIPR_OK;
+}
+}
+
+bool SceneBuilder::adopt_rebuilt_trees(const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, uint32_t deepest, const HiprSlot8* slots, const HiprWide8BuildResult& wide8) {
+    const uint32_t n = uint32_t(m_triangles.size());
+    auto refuse = [&] { ++m_rebuild_counts.refused; return false; };
+    // counts that do not fit; an instance turned inside out is drawn from other index triples, which changes the set of triangles
+    if (!nodes || !order || !slots || n == 0 || m_bvh.order.size() != n || m_staged_flips) return refuse();
+    if (node_count == 0 || node_count > std::max(n, 2u) - 1u || wide8.slot_count == 0 || wide8.slot_count > std::min<uint64_t>(2ull * n, 0xFFFFFFull)) return refuse();
+    std::vector<bool> seen(n, false);
+    for (uint32_t k = 0; k < n; ++k) {      // a permutation
+        if (order[k] >= n || seen[order[k]]) return refuse();
+        seen[order[k]] = true;
     }
+    for (uint32_t i = 0; i < node_count; ++i)
+        for (int c = 0; c < 2; ++c) {
+            const int32_t ref = nodes[i].child[c];
+            if (ref >= 0 ? uint32_t(ref) >= node_count || uint32_t(ref) <= i : uint64_t(uint32_t(~ref) >> 3) + (uint32_t(~ref) & 7u) + 1u > n) return refuse();
+        }
+    {   // the 8-wide tree from the root: every child slot in range, every record's triangles in range
+        std::vector<uint32_t> walk = {0u};
+        for (size_t i = 0; i < walk.size(); ++i) {
+            const HiprNode8& node = slots[walk[i]].node;
+            const uint32_t base = node.base_valid & 0xFFFFFFu, valid = node.base_valid >> 24;
+            uint32_t rank = 0;
+            for (int p = 0; p < 8; ++p) {
+                if (!(valid >> p & 1u)) continue;
+                const uint32_t child = base + rank++;
+                if (child >= wide8.slot_count || child <= walk[i] || walk.size() > wide8.slot_count) return refuse();
+                if (node.inner_mask >> p & 1u) walk.push_back(child);
+                else if (slots[child].leaf.triangle[0] >= n || (slots[child].leaf.triangle[1] != HIPR_LEAF8_NONE && slots[child].leaf.triangle[1] >= n)) return refuse();
+            }
+        }
+    }
+    // everything staged reaches the builder's own triangles, without a refit of trees that are about to be replaced and without a flatten
+    const std::vector<bool> moved = m_staged_moved.size() == m_instances.size() ? m_staged_moved : std::vector<bool>(m_instances.size(), false);
+    m_staged = false;
+    m_staged_moved.assign(m_instances.size(), false);
+    move_triangles(moved);
+    std::vector<HiprTriangle> world(n);      // the flatten order, through the old order
+    for (uint32_t k = 0; k < n; ++k) world[m_bvh.order[k]] = m_triangles[k];
+    m_bounds = AABB::invalid();      // grown in the order finalize() grows them in
+    for (const HiprTriangle& t : world) {
+        m_bounds.grow_to_contain(Vector3f(t.v0[0], t.v0[1], t.v0[2]));
+        m_bounds.grow_to_contain(Vector3f(t.v1[0], t.v1[1], t.v1[2]));
+        m_bounds.grow_to_contain(Vector3f(t.v2[0], t.v2[1], t.v2[2]));
+    }
+    AdoptedTrees adopted = {nodes, node_count, order, deepest, slots, wide8};
+    Bvh2SourceReport report;
+    Wide8SourceReport wide8_report;
+    build_trees_over(world, Bvh2Source{adopted_bvh2, &adopted}, report, Wide8Source{adopted_wide8, &adopted}, wide8_report);      // a host configured away from the default trees builds its own, as rebuild() would
+    ++m_rebuild_counts.adopted;
     return true;
 }
 

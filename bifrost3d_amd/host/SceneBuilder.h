@@ -99,6 +99,18 @@ public:
     void set_wide8_source(const Wide8Source& source) { m_wide8_source = source; }
     struct CollapseCounts { unsigned device_collapses = 0, declined_collapses = 0; };
     CollapseCounts collapse_counts() const { return m_collapse_counts; }
+    // The trees a device rebuild of the resident scene made (hipr_rebuild_scene_trees: the same trees, built from the triangles the device holds) taken over in place of
+    // a rebuild(): everything staged is applied to the builder's own triangles WITHOUT a refit and without a flatten, they are brought into flatten order through the
+    // old order and into the new one through `order` (order[k] = the flatten position of the triangle at place k: BvhBuildResult::order), the BVH2 (`nodes`,
+    // `deepest`) and the 8-wide tree (`slots`, `wide8`) are installed, the 4-wide tree is collapsed on the host from the adopted BVH2, and desc() is, in every
+    // array and scalar, what rebuild() leaves. Returns false, with nothing touched, for counts that do not fit, an `order` that is no permutation, a child or
+    // leaf reference out of range, or a staged transform that turns an instance inside out. rebuild_counts(): calls that adopted, calls that refused.
+    bool adopt_rebuilt_trees(const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, uint32_t deepest, const HiprSlot8* slots, const HiprWide8BuildResult& wide8);
+    struct RebuildCounts { unsigned adopted = 0, refused = 0; };
+    RebuildCounts rebuild_counts() const { return m_rebuild_counts; }
+    uint32_t desc_triangle_count() const { return uint32_t(m_triangles.size()); }      // desc().triangle_count, also while transforms are staged
+    uint32_t bvh_max_depth_limit() const { return m_bvh_max_depth_limit; }             // what finalize() was given: the depth every rebuild builds to
+    const std::vector<uint32_t>& order() const { return m_bvh.order; }      // order()[k] = the flatten position of the triangle desc().triangles[k]
     // Material-only update after finalize(): `changed` rewrites material slots, `assignments` gives instances another material. The builder's own description is
     // kept in step WITHOUT a rebuild -- a material moves no corner and the tree builders read no flag, so the trees and the triangle order are the ones a rebuild
     // would make: the flags of the touched instances' triangles are recomputed (csrc/material_rules.h) and the leaf records of the 8-wide tree follow them. What
@@ -124,6 +136,9 @@ private:
     // them with the second and third corner exchanged, so that the world-space corners wind the way the reference's transformed geometric normal points
     // (rtTransformNormal through the inverse transpose, ORS/MonteCarlo.cu:147) and every consumer of the triple order sees the same triangle.
     uint32_t index_offset_for(uint32_t mesh, const float* object_to_world);
+    void build_trees_over(const std::vector<HiprTriangle>& world, const Bvh2Source& bvh2_source, Bvh2SourceReport& report, const Wide8Source& wide8_source, Wide8SourceReport& wide8_report);
+    void move_triangles(const std::vector<bool>& moved);
+    RebuildCounts m_rebuild_counts;
     bool record_model_transforms(const std::vector<std::pair<uint32_t, Transform>>& model_transforms, std::vector<HiprInstanceTransform>* moved_instances);
     bool m_staged = false, m_staged_flips = false;      // transforms recorded in m_instances that m_triangles / m_bvh do not carry yet
     std::vector<bool> m_staged_moved;

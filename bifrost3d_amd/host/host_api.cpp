@@ -355,6 +355,39 @@ int hiprh_scene_rebuild(void* scene) {
     catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_rebuild: %s\n", e.what()); return -1; }
 }
 
+// SceneBuilder::stage_model_transforms for one model: the pose is recorded in the instances, the triangles and the trees stay (hiprh_scene_desc must not be asked
+// until hiprh_scene_adopt_trees, hiprh_scene_move_model or hiprh_scene_rebuild has caught up). Returns 1, 0 when the pose turns an instance inside out, -1 on error.
+int hiprh_scene_stage_model(void* scene, unsigned model_index, const float* translation3, const float* rotation4, float scale) {
+    if (!scene || !translation3 || !rotation4) return -1;
+    const Transform t(Vector3f(translation3[0], translation3[1], translation3[2]), Bifrost::Math::Quaternionf(rotation4[0], rotation4[1], rotation4[2], rotation4[3]), scale);
+    try {
+        std::vector<HiprInstanceTransform> moved;
+        return static_cast<SceneBuilder*>(scene)->stage_model_transforms({{model_index, t}}, moved) ? 1 : 0;
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_stage_model: %s\n", e.what()); return -1; }
+}
+
+// SceneBuilder::adopt_rebuilt_trees: the trees hipr_rebuild_scene_trees made of the resident scene taken over in place of a rebuild. Returns 1 when adopted, 0 when
+// refused (nothing touched), -1 on error.
+int hiprh_scene_adopt_trees(void* scene, const HiprBvhNode* nodes, unsigned node_count, const unsigned* order, unsigned deepest, const HiprSlot8* slots, const HiprWide8BuildResult* wide8) {
+    if (!scene || !wide8) return -1;
+    try { return static_cast<SceneBuilder*>(scene)->adopt_rebuilt_trees(nodes, node_count, order, deepest, slots, *wide8) ? 1 : 0; }
+    catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_adopt_trees: %s\n", e.what()); return -1; }
+}
+// The builder's current order (BvhBuildResult::order): triangle_count words, valid until the scene changes or is destroyed.
+const unsigned* hiprh_scene_order(void* scene, unsigned* out_count) {
+    if (!scene || !out_count) return nullptr;
+    const std::vector<uint32_t>& order = static_cast<SceneBuilder*>(scene)->order();
+    *out_count = unsigned(order.size());
+    return order.data();
+}
+// out[0] = calls of hiprh_scene_adopt_trees that adopted, out[1] = calls that refused.
+int hiprh_scene_rebuild_counts(void* scene, unsigned* out2) {
+    if (!scene || !out2) return -1;
+    const SceneBuilder* sb = static_cast<SceneBuilder*>(scene);
+    out2[0] = sb->rebuild_counts().adopted; out2[1] = sb->rebuild_counts().refused;
+    return 0;
+}
+
 static int build_bvh2_on_context(void* context, const HiprTriangle* triangles, uint32_t count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_node_count,
                                  uint32_t* out_order, uint32_t* out_deepest);
 static int build_wide8_on_context(void* context, const HiprBvhNode* nodes, uint32_t node_count, const HiprTriangle* triangles, const uint32_t* order, uint32_t triangle_count, HiprSlot8* out_slots,

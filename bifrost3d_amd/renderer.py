@@ -75,12 +75,14 @@ class Context:
 
     def upload_scene(self, scene):
         self._scene = scene   # keep the host arrays alive until uploaded (copy happens inside)
+        self._rebuilt_counts = None
         self._check(self.lib.hipr_upload_scene(self.handle, C.byref(scene.desc)), "hipr_upload_scene")
         state = scene.state
         self._check(self.lib.hipr_set_scene_state(self.handle, C.byref(state)), "hipr_set_scene_state")
 
     def update_scene_geometry(self, scene):
         self._scene = scene
+        self._rebuilt_counts = None
         self._check(self.lib.hipr_update_scene_geometry(self.handle, C.byref(scene.desc)), "hipr_update_scene_geometry")
 
     def refit_scene_transforms(self, moved=(), lights=None) -> dict:
@@ -146,6 +148,37 @@ class Context:
         return status, slots[:r.slot_count], dict(slot_count=r.slot_count, height=r.height, grid_min=np.array(r.grid_min[:], np.float32), grid_cell=np.array(r.grid_cell[:], np.float32),
                                                   node_count=r.node_count, leaf_count=r.leaf_count, paired_leaves=r.paired_leaves)
 
+    def rebuild_scene_trees(self, max_depth: int = 62, read_back: bool = True, group=None) -> dict:
+        """hipr_rebuild_scene_trees: the trees of the resident scene rebuilt on the device from the triangles it holds (after a refit_scene_transforms that moved a model
+        far, or reported needs_rebuild). Returns a dict of status, node_count, deepest, wide8 (as build_wide8's result), half_area and -- `read_back` -- nodes
+        ((node_count, 16) uint32), order ((triangles,) uint32, Scene.adopt_trees takes them) and slots ((slot_count, 16)). On a status other than HIPR_OK the dict holds
+        the status and the arrays whole as the call left them. `group`: a HiprGroup handle, for hipr_group_rebuild_scene_trees."""
+        n = self._scene.desc.triangle_count
+        nodes = np.zeros((max(n - 1, 1), 16), np.uint32) if read_back else None
+        order = np.zeros(n, np.uint32) if read_back else None
+        slots = np.zeros((max(min(2 * n, 0xFFFFFF), 1), 16), np.uint32) if read_back else None
+        result = capi.HiprSceneRebuildResult()
+        pointer = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        call, handle = (self.lib.hipr_group_rebuild_scene_trees, group) if group is not None else (self.lib.hipr_rebuild_scene_trees, self.handle)
+        status = call(handle, max_depth, pointer(nodes), len(nodes) if read_back else 0, pointer(order), pointer(slots), len(slots) if read_back else 0, C.byref(result))
+        if status != capi.HIPR_OK:
+            return dict(status=status, nodes=nodes, order=order, slots=slots)
+        w = result.wide8
+        if group is None:
+            self._rebuilt_counts = (result.node_count, w.slot_count)
+        out = dict(status=status, node_count=result.node_count, deepest=result.deepest, half_area=float(result.half_area),
+                   wide8=dict(slot_count=w.slot_count, height=w.height, grid_min=np.array(w.grid_min[:], np.float32), grid_cell=np.array(w.grid_cell[:], np.float32), node_count=w.node_count,
+                              leaf_count=w.leaf_count, paired_leaves=w.paired_leaves), raw=result)
+        if read_back:
+            out.update(nodes=nodes[:result.node_count], order=order, slots=slots[:w.slot_count])
+        return out
+
+    def rebuild_times(self) -> dict:
+        """Milliseconds of the last rebuild_scene_trees: flatten order, BVH2, collapse (with the slots copied to the host), the new resident arrays, the outputs' read-back."""
+        out = (C.c_double * 5)()
+        self._check(self.lib.hipr_debug_rebuild_times(self.handle, out), "hipr_debug_rebuild_times")
+        return dict(flatten=out[0], bvh2=out[1], collapse=out[2], install=out[3], readback=out[4])
+
     def collapse_times(self) -> dict:
         """Milliseconds of the last build_wide8: the walk over the indices, allocation + upload, kernels, read-back."""
         out = (C.c_double * 4)()
@@ -154,9 +187,10 @@ class Context:
 
     def read_scene_buffer(self, which: int) -> np.ndarray:
         """The scene array the device holds (hipr_debug_read_scene_buffer): capi.SCENE_BUFFER_TRIANGLES -> (triangles, 12) uint32 words, SCENE_BUFFER_WIDE8_SLOTS -> (slots, 16),
-        _TRACE_TRIANGLES -> (triangles, 12), _SHADE_TRIANGLES -> (triangles, 32), _TRIANGLE_CLASS -> (triangles,) uint8, _MATERIALS -> (materials, 16), _INSTANCES -> (instances, 20)."""
+        _TRACE_TRIANGLES -> (triangles, 12), _SHADE_TRIANGLES -> (triangles, 32), _TRIANGLE_CLASS -> (triangles,) uint8, _MATERIALS -> (materials, 16), _INSTANCES -> (instances, 20), SCENE_BUFFER_NODES -> (BVH2 nodes, 16)."""
         desc = self._scene.desc
-        shape, dtype = {capi.SCENE_BUFFER_TRIANGLES: ((desc.triangle_count, 12), np.uint32), capi.SCENE_BUFFER_WIDE8_SLOTS: ((desc.wide8_slot_count, 16), np.uint32),
+        node_count, slot_count = getattr(self, "_rebuilt_counts", None) or (desc.node_count, desc.wide8_slot_count)      # a device rebuild changes both
+        shape, dtype = {capi.SCENE_BUFFER_TRIANGLES: ((desc.triangle_count, 12), np.uint32), capi.SCENE_BUFFER_WIDE8_SLOTS: ((slot_count, 16), np.uint32), capi.SCENE_BUFFER_NODES: ((node_count, 16), np.uint32),
                         capi.SCENE_BUFFER_TRACE_TRIANGLES: ((desc.triangle_count, 12), np.uint32), capi.SCENE_BUFFER_SHADE_TRIANGLES: ((desc.triangle_count, 32), np.uint32),
                         capi.SCENE_BUFFER_TRIANGLE_CLASS: ((desc.triangle_count,), np.uint8), capi.SCENE_BUFFER_MATERIALS: ((desc.material_count, 16), np.uint32),
                         capi.SCENE_BUFFER_INSTANCES: ((desc.instance_count, 20), np.uint32)}.get(which, ((0,), np.uint8))

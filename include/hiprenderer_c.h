@@ -414,6 +414,34 @@ typedef struct HiprWide8BuildResult {
 } HiprWide8BuildResult;
 int hipr_build_wide8(HiprContext* context, const HiprBvhNode* nodes, uint32_t node_count, const HiprTriangle* triangles, const uint32_t* order /* may be NULL */,
                      uint32_t triangle_count, HiprSlot8* out_slots, uint32_t slot_capacity, HiprWide8BuildResult* out);
+/* The trees of the RESIDENT scene rebuilt on the device, in place, from the triangles it holds (the reference asks OptiX for a "Trbvh" build, which runs on the GPU
+ * over the geometry the device holds, OR/Renderer.cpp:161-182,471-476; a moved node marks the acceleration dirty and the next launch rebuilds it on the device,
+ * OR/Renderer.cpp:472,1010-1041): what a model that was dragged far asks for -- hipr_refit_scene_transforms reports child_half_area past 1.5 x uploaded_half_area, or
+ * needs_rebuild -- without a flatten on the host and without an upload. No pool has changed, and after the refit the device holds the host's world-space triangles
+ * byte for byte; kernels put them into the order the scene builder flattens in (instances in order, primitives in order), build the BVH2 (csrc/bvh2_build.h),
+ * collapse it (csrc/wide8_build.h) and install the result (csrc/scene_rebuild.h). Afterwards the device holds, byte for byte, what SceneBuilder::rebuild() followed
+ * by hipr_upload_scene on a fresh context puts into the triangles, the BVH2 nodes, the 8-wide slots and everything derived from them; the 4-wide array is not
+ * rebuilt, so the state hipr_refit_scene_transforms describes (hipr_set_trace_variant refuses the other searches) lasts until the next upload or geometry update; that
+ * hipr_update_scene_geometry brings the NEW tree's 4-wide array, whose size and stack need it takes instead of comparing them with the uploaded ones.
+ * Outputs are host pointers and may be NULL (not read back): `out_nodes` the BVH2, `out_order` triangle_count words -- out_order[k] is the position, in the
+ * builder's flatten order, of the triangle that stands at place k afterwards (BvhBuildResult::order) -- `out_slots` the 8-wide tree. max_depth below 8 is taken as 8.
+ * The call accepts a scene that is ready, and one whose last writer was a hipr_refit_scene_transforms that returned needs_rebuild (not ready, but whole).
+ * Checked before the device is touched:
+ *   HIPR_ERROR_NOT_READY          no scene, or a scene a failed call left behind;
+ *   HIPR_ERROR_UNSUPPORTED        the conditions hipr_refit_scene_transforms refuses on: no 8-wide tree, another search, the exhaustive search's items;
+ *   HIPR_ERROR_INVALID_ARGUMENT   a null `out`; a non-null `out_nodes` with room for fewer than max(count, 1) - 1 (or 1) nodes; a non-null `out_slots` with room
+ *                                 for fewer than min(2 x triangle_count, 0xFFFFFF) slots -- what always suffices.
+ * Found on the device, before anything resident is replaced, all HIPR_ERROR_UNSUPPORTED with the reason in hipr_last_error(): a decline of the BVH2 build (a
+ * median range longer than a lane sorts, as hipr_build_bvh2); a new 8-wide tree higher than the kernels' stacks (33); more than 0xFFFFFF slots; two resident
+ * triangles that claim one flatten position. Every refusal leaves the resident scene exactly as the call found it -- not ready included -- and the outputs
+ * untouched. A HIP failure once the new arrays are being installed leaves no scene, as with the other writers. */
+typedef struct HiprSceneRebuildResult {
+    uint32_t node_count, deepest;        /* the BVH2, as hipr_build_bvh2 reports them */
+    HiprWide8BuildResult wide8;          /* as hipr_build_wide8 reports it */
+    double half_area;                    /* child_half_area of the new tree = the scene's new uploaded_half_area */
+} HiprSceneRebuildResult;
+int hipr_rebuild_scene_trees(HiprContext* context, uint32_t max_depth, HiprBvhNode* out_nodes /* may be NULL */, uint32_t node_capacity, uint32_t* out_order /* may be NULL */,
+                             HiprSlot8* out_slots /* may be NULL */, uint32_t slot_capacity, HiprSceneRebuildResult* out);
 int hipr_set_scene_state(HiprContext* context, const HiprSceneState* state);
 
 /* Entry points, numbered like OR/Types.h:33-44. set_backend() of the host renderer maps Backend values onto them
@@ -499,6 +527,8 @@ int hipr_group_build_bvh2(HiprGroup* group, const HiprTriangle* triangles, uint3
                           uint32_t* out_node_count, uint32_t* out_order, uint32_t* out_deepest);   /* builds on member 0 */
 int hipr_group_build_wide8(HiprGroup* group, const HiprBvhNode* nodes, uint32_t node_count, const HiprTriangle* triangles, const uint32_t* order, uint32_t triangle_count,
                            HiprSlot8* out_slots, uint32_t slot_capacity, HiprWide8BuildResult* out);   /* collapses on member 0 */
+int hipr_group_rebuild_scene_trees(HiprGroup* group, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_order, HiprSlot8* out_slots,
+                                   uint32_t slot_capacity, HiprSceneRebuildResult* out);   /* every member rebuilds; member 0's arrays are handed out; their results must agree */
 int hipr_group_update_scene_materials(HiprGroup* group, const HiprMaterialUpdate* materials, uint32_t material_count,
                                       const HiprInstanceMaterial* assignments, uint32_t assignment_count);   /* every member checks before any member writes */
 int hipr_group_set_scene_state(HiprGroup* group, const HiprSceneState* state);
@@ -640,13 +670,16 @@ int hipr_debug_trace_shadow(HiprContext* context, const float* rays, uint32_t n,
  * trace records (48 bytes per triangle), the shading records (128 bytes per triangle), the class bytes of the listing pass (one per triangle),
  * HiprMaterial[material_count], HiprInstance[instance_count]. */
 enum { HIPR_SCENE_BUFFER_TRIANGLES = 0, HIPR_SCENE_BUFFER_WIDE8_SLOTS = 1, HIPR_SCENE_BUFFER_TRACE_TRIANGLES = 2, HIPR_SCENE_BUFFER_SHADE_TRIANGLES = 3,
-       HIPR_SCENE_BUFFER_TRIANGLE_CLASS = 4, HIPR_SCENE_BUFFER_MATERIALS = 5, HIPR_SCENE_BUFFER_INSTANCES = 6 };
+       HIPR_SCENE_BUFFER_TRIANGLE_CLASS = 4, HIPR_SCENE_BUFFER_MATERIALS = 5, HIPR_SCENE_BUFFER_INSTANCES = 6, HIPR_SCENE_BUFFER_NODES = 7 /* the BVH2 */ };
 int hipr_debug_read_scene_buffer(HiprContext* context, int which, void* out, uint64_t capacity_bytes);
 /* Milliseconds of the context's last successful hipr_build_bvh2, which add up to the call: the argument checks (the pass over all corners for one that is not
  * finite), scratch allocation + upload, kernels, read-back (tools/device_build_probe.py). */
 int hipr_debug_build_times(HiprContext* context, double* out4_ms);
 /* The same for the context's last successful hipr_build_wide8: the walk over the indices, allocation + upload, kernels (with the few words read per level), read-back. */
 int hipr_debug_collapse_times(HiprContext* context, double* out4_ms);
+/* The same for the context's last successful hipr_rebuild_scene_trees: the flatten order, the BVH2 build, the hand-over and the collapse with its slots copied to the
+ * host, the new resident arrays with what is derived from them, the read-back of the outputs (tools/device_rebuild_probe.py). */
+int hipr_debug_rebuild_times(HiprContext* context, double* out5_ms);
 
 #ifdef __cplusplus
 }
