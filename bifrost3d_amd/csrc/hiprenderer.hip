@@ -804,6 +804,11 @@ int enqueue_bounce(HiprContext* c, Wavefront& w, const HiprCameraState& camera, 
             fprintf(stderr, "[hipr]     wave iterations: %.0f node (%.1f lanes working) + %.0f triangle (%.1f lanes working); %.1f lanes busy on average; %llu refills\n", ni,
                     double(dc.node_lanes - p.node_lanes) / ni, ti, ti > 0 ? double(dc.triangle_lanes - p.triangle_lanes) / ti : 0.0,
                     double(dc.busy_lanes - p.busy_lanes) / (ni + ti), dc.refills - p.refills);
+            const double rc = double(dc.record_iterations_closest - p.record_iterations_closest), rs = double(dc.record_iterations_shadow - p.record_iterations_shadow),
+                         rm = double(dc.record_iterations_mixed - p.record_iterations_mixed);
+            if (rc + rs + rm > 0)      // fused launches over the 8-wide tree: a record iteration with one kind of ray branches over the other kind's code
+                fprintf(stderr, "[hipr]     triangle iterations by the rays on the records: %.0f closest-hit only (%.1f %%) + %.0f shadow only (%.1f %%) + %.0f both (%.1f %%)\n", rc,
+                        100.0 * rc / (rc + rs + rm), rs, 100.0 * rs / (rc + rs + rm), rm, 100.0 * rm / (rc + rs + rm));
             const double pushes = double(dc.pushes - p.pushes);
             if (pushes > 0)
                 fprintf(stderr, "[hipr]     stack pushes: %.0f, of which %.3f %% onto entry 16 or deeper and %.3f %% onto entry 24 or deeper\n", pushes,
@@ -2787,6 +2792,56 @@ int hipr_debug_trace_shadow(HiprContext* c, const float* rays, uint32_t n, float
     for (uint32_t i = 0; i < n; ++i) out_transmittance[i] = result[4 * i];
     c->total = {};
     c->total.shadow_rays = n;
+    return HIPR_OK;
+}
+
+// Both of the above in ONE fused launch, as a bounce of a pass makes it for the scenes of the persistent kernels: the closest-hit rays first, the shadow rays behind
+// them in one index space. Same ray layouts as the two entries above; either queue may be empty.
+int hipr_debug_trace_fused(HiprContext* c, const float* closest_rays, const uint32_t* skip, uint32_t n_closest, const float* shadow_rays, uint32_t n_shadow, float* out_hits,
+                           float* out_transmittance) {
+    if (int s = check_context(c)) return s;
+    if (!c->scene.ready) return fail(HIPR_ERROR_NOT_READY, "no scene uploaded");
+    if ((n_closest && (!closest_rays || !out_hits)) || (n_shadow && (!shadow_rays || !out_transmittance))) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null argument");
+    if (n_closest > 0x7FFFFFFFu || n_shadow > 0x7FFFFFFFu) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_trace_fused: more than 2^31 rays of a kind");
+    if (!c->use_persistent()) return fail(HIPR_ERROR_UNSUPPORTED, "a fused trace launch needs a persistent kernel");
+    if (n_closest + n_shadow == 0) return HIPR_OK;
+    if (int s = drain(c)) return s;      // as in hipr_debug_trace_closest
+    const size_t nc = std::max(n_closest, 1u), ns = std::max(n_shadow, 1u);      // an empty queue still has its buffers
+    std::vector<float> o(nc * 4, 0.0f), d(nc * 4, 0.0f), so(ns * 4, 0.0f), sd(ns * 4, 0.0f), rad(ns * 4, 0.0f), ones(ns * 4, 1.0f);
+    std::vector<uint32_t> meta(nc * 2, 0u);
+    if (n_closest) debug_prepare_rays(closest_rays, n_closest, o, d);
+    for (uint32_t i = 0; i < n_closest; ++i) { meta[2 * i] = i; meta[2 * i + 1] = skip ? skip[i] : HIPR_NO_TRIANGLE; }
+    for (uint32_t i = 0; i < n_shadow; ++i) {
+        std::memcpy(&so[4 * i], shadow_rays + 8 * size_t(i), 12);
+        so[4 * i + 3] = shadow_rays[8 * size_t(i) + 7];       // tmax
+        std::memcpy(&sd[4 * i], shadow_rays + 8 * size_t(i) + 4, 12);
+        std::memcpy(&sd[4 * i + 3], &i, 4);                   // slot
+    }
+    const uint32_t counts[2] = {n_closest, n_shadow};
+    DeviceBuffer bo, bd, bm, bh, bso, bsd, br, bacc, bc;
+    int r = bo.upload(o.data(), o.size() * 4, c->stream) | bd.upload(d.data(), d.size() * 4, c->stream) | bm.upload(meta.data(), meta.size() * 4, c->stream) | bh.resize(nc * 16) |
+            bso.upload(so.data(), so.size() * 4, c->stream) | bsd.upload(sd.data(), sd.size() * 4, c->stream) | br.upload(ones.data(), ones.size() * 4, c->stream) |
+            bacc.upload(rad.data(), rad.size() * 4, c->stream) | bc.upload(counts, 8, c->stream);
+    if (r) return HIPR_ERROR_OUT_OF_MEMORY;
+    HIP_TRY(hipMemsetAsync(c->counters.ptr, 0, sizeof(DeviceCounters), c->stream));
+    PathState in = {bo.as<float4>(), bd.as<float4>(), nullptr, bm.as<uint2>()};
+    Wavefront w;
+    w.stream = c->stream;
+    w.hits = std::move(bh);
+    w.shadow[0] = std::move(bso); w.shadow[1] = std::move(bsd); w.shadow[2] = std::move(br);
+    std::swap(c->radiance, bacc);      // the launch writes the context's radiance buffer: this call's, for its duration
+    trace_rays<TRACE_FUSED>(c, w, {in, bc.as<uint32_t>(), bc.as<uint32_t>() + 1, n_closest + n_shadow});
+    std::swap(c->radiance, bacc);
+    if (int finish_status = finish_all(c)) return finish_status;
+    if (n_closest) HIP_TRY(hipMemcpy(out_hits, w.hits.ptr, size_t(n_closest) * 16, hipMemcpyDeviceToHost));
+    if (n_shadow) {
+        std::vector<float> result(size_t(n_shadow) * 4);
+        HIP_TRY(hipMemcpy(result.data(), bacc.ptr, result.size() * 4, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n_shadow; ++i) out_transmittance[i] = result[4 * i];
+    }
+    c->total = {};
+    c->total.closest_rays = n_closest;
+    c->total.shadow_rays = n_shadow;
     return HIPR_OK;
 }
 

@@ -106,6 +106,8 @@ struct DeviceCounters {
     // diagnostics of the persistent kernels (instrumented builds): wave iterations by kind and the lanes that did work in them
     unsigned long long node_iterations, node_lanes, triangle_iterations, triangle_lanes, busy_lanes, refills;
     unsigned long long pushes, pushes_past_16, pushes_past_24;   // stack pushes of the persistent kernels, and those that landed on entry 16 / 24 or deeper
+    // record iterations of the fused 8-wide launches by the rays on the records: closest-hit rays only, shadow rays only (each branches over the other kind's code), both
+    unsigned long long record_iterations_closest, record_iterations_shadow, record_iterations_mixed;
 };
 
 // Blocks that share an XCD (blockIdx % 8) get a contiguous range of chunks so that spatially

@@ -62,6 +62,14 @@ constexpr int WIDE8_STACK_SHALLOW = 12;      // 12 KB per block of two waves: tw
 #endif
 HD constexpr int wide8_waves_per_simd(int stack_entries) { return stack_entries <= 8 ? HIPR_WIDE8_WAVES_LOW : (stack_entries <= 12 ? HIPR_WIDE8_WAVES : (stack_entries <= 16 ? 5 : 4)); }
 
+// The weights (1 - ru - rv, ru, rv) of a record's corners as the (u, v) of its scene triangle `which` (0: A, 1: B), through the record's selectors.
+__device__ __forceinline__ void record_barycentrics(uint32_t flags, int which, float ru, float rv, float& u, float& v) {
+    const float rw = 1.0f - ru - rv;
+    const uint32_t su = (flags >> (which == 0 ? 8 : 12)) & 3u, sv = (flags >> (which == 0 ? 10 : 14)) & 3u;
+    u = su == 0u ? rw : (su == 1u ? ru : rv);
+    v = sv == 0u ? rw : (sv == 1u ? ru : rv);
+}
+
 // COVERAGE_R8: ... and every coverage texture is single-channel 8-bit, linear (kernels.h material_coverage_r8).
 // COVERAGE: the scene holds triangles that are not statically opaque (coverage textures, cut-outs, partial coverage): a shadow ray that hits one samples its material's
 // coverage. Scenes without any (the common case; decided at upload) run the instantiation without that code: it is a fifth of the kernel's instructions and, though never
@@ -101,6 +109,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
     uint32_t nodes = 0, tris = 0, shadow_nodes = 0, shadow_tris = 0;
     uint32_t diag_node_iterations = 0, diag_node_lanes = 0, diag_triangle_iterations = 0, diag_triangle_lanes = 0, diag_busy_lanes = 0, diag_refills = 0;   // lane 0 only
     uint32_t diag_pushes = 0, diag_pushes_deep = 0;
+    uint32_t diag_records_closest = 0, diag_records_shadow = 0, diag_records_mixed = 0;      // lane 0 only: record iterations of a fused launch by the rays on the records
 
     for (;;) {
         // ---- retire finished lanes (converged: every lane of the wave is here) --------------------------------------
@@ -204,11 +213,15 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
             const bool node_mode = active & !item_is_leaf;
             const unsigned long long lmask = wave_ballot(leaf_mode), nmask = wave_ballot(node_mode);
             bool advance = false;       // this lane finished its item in this iteration and takes the next one
+            const unsigned long long shadows = INSTRUMENT && MODE == TRACE_FUSED ? wave_ballot(leaf_mode && is_shadow) : 0ull;
             if (INSTRUMENT && lane == 0) {
                 const bool leaves = __popcll(lmask) * HIPR_WIDE8_LEAF_VOTE_DEN > __popcll(nmask) * HIPR_WIDE8_LEAF_VOTE_NUM;
                 diag_triangle_iterations += leaves; diag_triangle_lanes += leaves ? __popcll(lmask) : 0;
                 diag_node_iterations += !leaves; diag_node_lanes += leaves ? 0 : __popcll(nmask);
                 diag_busy_lanes += __popcll(lmask | nmask);
+                if (MODE == TRACE_FUSED && leaves) {      // which kinds of ray the record lanes hold: with one kind, the other kind's code is branched over
+                    diag_records_closest += shadows == 0ull; diag_records_shadow += shadows == lmask; diag_records_mixed += shadows != 0ull && shadows != lmask;
+                }
             }
             if (__popcll(lmask) * HIPR_WIDE8_LEAF_VOTE_DEN > __popcll(nmask) * HIPR_WIDE8_LEAF_VOTE_NUM) {
                 if (leaf_mode) {
@@ -239,15 +252,18 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
                             TriangleTest test;
                             const f3 first = which == 0 ? e1 : e2, second = which == 0 ? e2 : e3;
                             const bool hit = triangle_inside(a, first, second, o, d, test);
-                            float t = 0.0f, ru = 0.0f, rv = 0.0f;
-                            if (wave_any(hit)) triangle_hit_values(test, second, t, ru, rv);     // the lanes in this branch agree to skip the division
-                            const float rw = 1.0f - ru - rv;
-                            const uint32_t su = (flags >> (which == 0 ? 8 : 12)) & 3u, sv = (flags >> (which == 0 ? 10 : 14)) & 3u;
-                            const float u = su == 0u ? rw : (su == 1u ? ru : rv), v = sv == 0u ? rw : (sv == 1u ? ru : rv);
+                            // triangle_hit_values in two steps: t for every lane; u and v only where a branch below reads them -- the closest-hit lanes, and the
+                            // shadow lanes that sample a coverage. A wave whose record lanes all hold shadow rays (the normal case in a fused launch: its shards
+                            // are ranges of one kind of ray) then branches over the closest-hit selection as waves without shadow rays branch over the
+                            // transmittance code, and in a scene of opaque triangles it never forms u or v.
+                            float t = 0.0f, by_det = 0.0f;
+                            if (wave_any(hit)) { by_det = 1.0f / test.det; t = dot_fma(second, test.q) * by_det; }     // the lanes in this branch agree to skip the division
                             if constexpr (MODE != TRACE_CLOSEST) {
                                 if (is_shadow && hit && t > tmin && t < tmax) {
                                     float coverage = 1.0f;
                                     if (COVERAGE && !(flags >> which & 1u)) {
+                                        float u, v;
+                                        record_barycentrics(flags, which, test.un * by_det, test.vn * by_det, u, v);
                                         // The triangle's texture coordinates and material index from its SHADING record (k_build_shade_triangles: the same floats the
                                         // vertex arrays hold, zero without texture coordinates): three loads side by side where triangle -> instance -> indices -> texture
                                         // coordinates were four one after the other (round 4: a wave waits on this chain for every lane that meets a cut-out;
@@ -267,10 +283,14 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
                                 }
                             }
                             if constexpr (MODE != TRACE_SHADOW) {
-                                const float facing = which == 0 ? test.det : __uint_as_float(__float_as_uint(test.det) ^ ((flags & 16u) << 27));
-                                const bool refused = facing < (which == 0 ? refuse_a_below : refuse_b_below);
-                                const bool closer = !is_shadow & hit & !refused & (id != pay_k) & (t > tmin) & ((t < tmax) | ((t == tmax) & (id < __float_as_uint(pay_z))));
-                                tmax = closer ? t : tmax; pay_x = closer ? u : pay_x; pay_y = closer ? v : pay_y; pay_z = closer ? __uint_as_float(id) : pay_z;
+                                if (!is_shadow && hit) {      // a branch, not terms of `closer`: no closest-hit lane inside this triangle, no instruction issued
+                                    float u, v;
+                                    record_barycentrics(flags, which, test.un * by_det, test.vn * by_det, u, v);
+                                    const float facing = which == 0 ? test.det : __uint_as_float(__float_as_uint(test.det) ^ ((flags & 16u) << 27));
+                                    const bool refused = facing < (which == 0 ? refuse_a_below : refuse_b_below);
+                                    const bool closer = !refused & (id != pay_k) & (t > tmin) & ((t < tmax) | ((t == tmax) & (id < __float_as_uint(pay_z))));
+                                    tmax = closer ? t : tmax; pay_x = closer ? u : pay_x; pay_y = closer ? v : pay_y; pay_z = closer ? __uint_as_float(id) : pay_z;
+                                }
                             }
                         }
                     }
@@ -364,6 +384,10 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
         wave_add(&counters->triangle_iterations, diag_triangle_iterations); wave_add(&counters->triangle_lanes, diag_triangle_lanes);
         wave_add(&counters->busy_lanes, diag_busy_lanes); wave_add(&counters->refills, diag_refills);
         wave_add(&counters->pushes, diag_pushes); wave_add(&counters->pushes_past_16, diag_pushes_deep);
+        if (MODE == TRACE_FUSED) {
+            wave_add(&counters->record_iterations_closest, diag_records_closest); wave_add(&counters->record_iterations_shadow, diag_records_shadow);
+            wave_add(&counters->record_iterations_mixed, diag_records_mixed);
+        }
         if (MODE != TRACE_SHADOW) { wave_add(&counters->closest_nodes, nodes); wave_add(&counters->closest_triangles, tris); }
         if (MODE != TRACE_CLOSEST) { wave_add(&counters->shadow_nodes, shadow_nodes); wave_add(&counters->shadow_triangles, shadow_tris); }
     }

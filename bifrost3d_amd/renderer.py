@@ -376,3 +376,18 @@ class Context:
         fp = C.POINTER(C.c_float)
         self._check(self.lib.hipr_debug_trace_shadow(self.handle, rays.ctypes.data_as(fp), len(rays), out.ctypes.data_as(fp)), "hipr_debug_trace_shadow")
         return out
+
+    def debug_trace_fused(self, closest_rays, skip, shadow_rays):
+        """One fused launch over both queues, as a bounce makes it: -> (hits (n_closest, 4), transmittance (n_shadow,)). Either set of rays may be empty."""
+        closest_rays = np.ascontiguousarray(closest_rays, np.float32).reshape(-1, 8)
+        shadow_rays = np.ascontiguousarray(shadow_rays, np.float32).reshape(-1, 8)
+        hits = np.zeros((len(closest_rays), 4), np.float32)
+        out = np.zeros(len(shadow_rays), np.float32)
+        fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, np.uint32)
+            assert len(skip) == len(closest_rays)
+        sk = skip.ctypes.data_as(up) if skip is not None else None
+        self._check(self.lib.hipr_debug_trace_fused(self.handle, closest_rays.ctypes.data_as(fp), sk, len(closest_rays), shadow_rays.ctypes.data_as(fp), len(shadow_rays),
+                                                    hits.ctypes.data_as(fp), out.ctypes.data_as(fp)), "hipr_debug_trace_fused")
+        return hits, out

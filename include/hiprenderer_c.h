@@ -666,6 +666,10 @@ int hipr_debug_sample_offsets(HiprContext* context, float* out_256x4);
 int hipr_debug_trace_closest(HiprContext* context, const float* rays, const uint32_t* skip, uint32_t n, float* out_hits);
 /* K4: shadow transmittance for n rays (float4 origin_tmin + float4 direction_tmax) -> one float per ray. */
 int hipr_debug_trace_shadow(HiprContext* context, const float* rays, uint32_t n, float* out_transmittance);
+/* K2 + K4 in ONE fused launch, as a bounce makes it for scenes of the persistent kernels (HIPR_ERROR_UNSUPPORTED for the others): n_closest closest-hit rays and
+ * n_shadow shadow rays in the layouts of the two entries above; either count may be 0, and its pointers are then not read. */
+int hipr_debug_trace_fused(HiprContext* context, const float* closest_rays, const uint32_t* skip, uint32_t n_closest, const float* shadow_rays, uint32_t n_shadow,
+                           float* out_hits, float* out_transmittance);
 /* The uploaded (or device-refitted, or material-updated) scene arrays as the device holds them: HiprTriangle[triangle_count], HiprSlot8[wide8_slot_count], the
  * trace records (48 bytes per triangle), the shading records (128 bytes per triangle), the class bytes of the listing pass (one per triangle),
  * HiprMaterial[material_count], HiprInstance[instance_count]. */
