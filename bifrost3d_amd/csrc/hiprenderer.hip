@@ -112,7 +112,7 @@ struct Wavefront {
     Stream own_stream;                  // first member: destroyed after the events and buffers below
     hipStream_t stream = nullptr;       // borrowed: wavefront 0 runs on the context stream, the others on their own
     Event shade_done[2], counts_copied[2], finished;   // by bounce parity: two bounces are in flight
-    DeviceBuffer path[2][4], hits, shadow[3], queue_counts, order, order_coat, nee_flags, sort_keys[2], sort_order, sort_temp;     // sort_*: ray_sort.hip (HIPR_COHERENCE_SORT=1)   // queue_counts: COUNT_LINES 64 B lines (see there); order: k_classify_hits' listing of a bounce's rays
+    DeviceBuffer path[2][4], hits, shadow[3], queue_counts, order, nee_flags, sort_keys[2], sort_order, sort_temp;     // sort_*: ray_sort.hip (HIPR_COHERENCE_SORT=1)   // queue_counts: COUNT_LINES 64 B lines (see there); order: k_classify_hits' listing of a bounce's rays
     PinnedWords host_counts;            // pinned: {continuing paths, shadow rays} per bounce parity, [4] staging word
     uint32_t first_slot = 0, n_slots = 0;      // first_slot: the wavefront's phase in the round-robin deal of 64-slot groups (partition_path_slots)
 
@@ -123,10 +123,9 @@ struct Wavefront {
 };
 constexpr int MAX_WAVEFRONTS = 4;
 constexpr int COUNT_PAIR_STRIDE = 16;   // uint32 words between the counters of a wavefront (one 64 B line each)
-// A wavefront's counters: lines 0-2 the queue-size pairs {paths, shadow rays}, bounce k reads pair k % 3 and fills pair (k + 1) % 3; lines 3-4
-// k_classify_hits' 8-byte counter of bounce parity 0 and 1. Nothing in the stream zeroes them between bounces: the shade kernel of bounce k zeroes
-// pair (k + 2) % 3 -- read last by bounce k - 1, whose sizes the host has read back before it queues bounce k -- and the listing counter of parity (k + 1) & 1.
-constexpr int COUNT_PAIRS = 3, COUNT_LINES = 5;
+// A wavefront's counters: lines 0-2 the queue-size pairs {paths, shadow rays}, bounce k reads pair k % 3 and fills pair (k + 1) % 3. Nothing in the stream zeroes
+// them between bounces: the shade kernel of bounce k zeroes pair (k + 2) % 3 -- read last by bounce k - 1, whose sizes the host has read back before it queues bounce k.
+constexpr int COUNT_PAIRS = 3, COUNT_LINES = 3;
 constexpr int HOST_COUNT_WORDS = 8 + COUNT_LINES * COUNT_PAIR_STRIDE;   // pinned: 2 x {paths, shadow rays} read back, [4..8) spare, then the image of the counters at the start of a pass
 
 // What the argument checks of a description derive on their way (preflight_scene).
@@ -235,7 +234,7 @@ struct Knobs {
     bool shade_classes = false;         // HIPR_SHADE_CLASSES=1: coated surface hits listed apart (built and measured in round 4: no gain, profiles/r04_ab_shade_classes.txt)
     int blocks_per_cu_override = 0;     // HIPR_BLOCKS_PER_CU: persistent trace blocks per CU instead of what the occupancy query says
     int shade_blocks_per_cu = 0;        // persistent shade blocks per CU = waves per SIMD; 0: 3 (what the kernel is compiled for), 2 for all-Diffuse scenes (HIPR_SHADE_BLOCKS_PER_CU)
-    uint32_t shade_ordered_from = 1u << 18;   // bounces with fewer paths than this are shaded in queue order (HIPR_SHADE_ORDERED_FROM)
+    uint32_t shade_ordered_from = 1u << 18;   // bounces with fewer paths than this are shaded in queue order (HIPR_SHADE_ORDERED_FROM); a listed bounce is dealt to the XCDs by chunks of 4096: under 8 chunks whole XCDs idle (shade_schedule.h)
     int refill_below = 40;              // persistent kernels refill a wave once fewer lanes than this are busy (HIPR_REFILL_BELOW)
     bool shade_split = false;           // HIPR_SHADE_SPLIT=1: the shade kernel as two, next event estimation and the rest (shade_kernel.h; measured)
     bool shade_ordered = true;          // k_classify_hits before k_shade (HIPR_SHADE_ORDERED=0: shade in queue order)
@@ -644,25 +643,24 @@ void trace_rays(HiprContext* c, const Wavefront& w, const TraceWork& work) {
     else launch_trace<MODE, false>(c, w, work);
 }
 
+// The listing pass of a bounce (kernels.h k_classify_hits): `order` chunk by chunk [plain surface hits | coated surface hits | everything else]. `grid` 0: one block
+// per chunk up to eight per CU.
+void classify_hits(HiprContext* c, hipStream_t stream, const float4* hits, const uint32_t* count, uint32_t upper_bound, uint32_t* order, bool classes, uint32_t grid) {
+    if (!grid) grid = grid_for(upper_bound, 256u * CLASSIFY_ROUNDS, uint32_t(c->cu_count) * 8u);
+    if (classes) hipLaunchKernelGGL(k_classify_hits<true>, dim3(grid), dim3(256), 0, stream, hits, count, order, c->scene.triangle_class.as<unsigned char>());
+    else hipLaunchKernelGGL(k_classify_hits<false>, dim3(grid), dim3(256), 0, stream, hits, count, order, (const unsigned char*)nullptr);
+}
+
 void launch_shade(HiprContext* c, const Wavefront& w, const HiprCameraState& camera, int cur, uint32_t alive, const uint32_t* in_count, uint32_t* out_counts, uint32_t* zero_pair, bool camera_rays) {
     // The rays of the bounce listed by kind (kernels.h k_classify_hits): the shade kernel's batches then hold surface hits only, or none.
     const uint32_t* order = nullptr;
-    const unsigned long long* listed = nullptr;
     // Pays where a good share of a bounce's rays did not hit a surface (the atrium's open roof: shade 23.3 -> 21.4 ms per step) and costs a pass over the hits
     // where nearly all did (the closed Cornell box: +7 %): on for the scenes of the persistent kernels, which are the large ones.
     // A bounce of a few thousand paths runs one wave per SIMD at most: the order they are taken in changes nothing, the listing pass would cost a launch.
-    uint32_t* taken_words = w.queue_counts.as<uint32_t>() + COUNT_PAIR_STRIDE * COUNT_PAIRS;
     // Camera rays need no listing: a wave of them is one pixel's samples (or an 8 x 8 tile's pixels) -- they hit a surface, or miss, together (HIPR_SHADE_ORDERED_CAMERA=1 lists them anyway).
     if (c->knobs.shade_ordered && c->use_persistent() && c->entry == HIPR_ENTRY_PATH_TRACING && alive >= c->knobs.shade_ordered_from && (!camera_rays || c->knobs.shade_ordered_camera)) {
-        unsigned long long* taken = reinterpret_cast<unsigned long long*>(taken_words + COUNT_PAIR_STRIDE * cur);
-        if (c->knobs.shade_classes && c->scene.any_coated_triangle)
-            hipLaunchKernelGGL(k_classify_hits<true>, dim3(grid_for(alive, 256u * CLASSIFY_ROUNDS, uint32_t(c->cu_count) * 8u)), dim3(256), 0, w.stream, w.hits.as<float4>(), in_count, w.order.as<uint32_t>(), taken,
-                               c->scene.triangle_class.as<unsigned char>(), w.order_coat.as<uint32_t>());
-        else
-            hipLaunchKernelGGL(k_classify_hits<false>, dim3(grid_for(alive, 256u * CLASSIFY_ROUNDS, uint32_t(c->cu_count) * 8u)), dim3(256), 0, w.stream, w.hits.as<float4>(), in_count, w.order.as<uint32_t>(), taken,
-                               (const unsigned char*)nullptr, w.order_coat.as<uint32_t>());
+        classify_hits(c, w.stream, w.hits.as<float4>(), in_count, alive, w.order.as<uint32_t>(), c->knobs.shade_classes && c->scene.any_coated_triangle, 0u);
         order = w.order.as<uint32_t>();
-        listed = taken;
     }
     // persistent blocks: three per CU stay resident (3 waves per SIMD), each walks the queue with a grid stride, one batch ahead on its inputs
     // measured: the Default / Transmissive kernels gain from a third wave per SIMD (atrium 29.4 -> 25.9 ms of shading per step), the lighter all-Diffuse
@@ -671,9 +669,8 @@ void launch_shade(HiprContext* c, const Wavefront& w, const HiprCameraState& cam
     const uint32_t blocks_per_cu = c->knobs.shade_blocks_per_cu > 0 ? uint32_t(c->knobs.shade_blocks_per_cu) : (split ? uint32_t(HIPR_SHADE_SPLIT_WAVES) : (c->scene.shading_models == 2 ? 2u : uint32_t(c->shade_unit().waves_per_simd)));
     PathState shaded = w.path_state(cur);
     if (camera_rays) shaded.thr_bounces = nullptr;      // k_generate's queue: throughput 1, no bounce yet -- not stored
-    ShadeLaunch a = {grid_for(alive, SHADE_BLOCK, uint32_t(c->cu_count) * blocks_per_cu), w.stream, c->scene.args, camera, c->frame, c->entry, shaded, w.hits.as<float4>(), order, w.order_coat.as<uint32_t>(), listed, w.path_state(1 - cur),
-                     w.shadow_queue(), c->radiance.as<float4>(), in_count, reinterpret_cast<unsigned long long*>(out_counts), reinterpret_cast<unsigned long long*>(zero_pair),
-                     reinterpret_cast<unsigned long long*>(taken_words + COUNT_PAIR_STRIDE * (1 - cur)), split ? w.nee_flags.as<unsigned char>() : nullptr,
+    ShadeLaunch a = {grid_for(alive, SHADE_BLOCK, uint32_t(c->cu_count) * blocks_per_cu), w.stream, c->scene.args, camera, c->frame, c->entry, shaded, w.hits.as<float4>(), order, w.path_state(1 - cur),
+                     w.shadow_queue(), c->radiance.as<float4>(), in_count, reinterpret_cast<unsigned long long*>(out_counts), reinterpret_cast<unsigned long long*>(zero_pair), split ? w.nee_flags.as<unsigned char>() : nullptr,
                      c->counters.as<DeviceCounters>(), c->scene.has_textures || !c->knobs.lean_shade, c->scene.has_environment || !c->knobs.lean_shade};
     c->shade_unit().shade(c->scene.shading_models, a);
 }
@@ -701,7 +698,7 @@ int partition_path_slots(HiprContext* c) {
         const size_t bytes = size_t(std::max(w.n_slots, 64u)) * 16;
         if (g >= c->wavefront_count && !second_slot) {   // queues of wavefronts this pass size does not use go back to the allocator
             for (auto& buffers : w.path) for (DeviceBuffer& b : buffers) b.release();
-            w.hits.release(); w.order.release(); w.order_coat.release(); w.nee_flags.release();
+            w.hits.release(); w.order.release(); w.nee_flags.release();
             w.sort_keys[0].release(); w.sort_keys[1].release(); w.sort_order.release(); w.sort_temp.release();
             for (DeviceBuffer& b : w.shadow) b.release();
             continue;
@@ -709,7 +706,6 @@ int partition_path_slots(HiprContext* c) {
         for (int i = 0; i < 2; ++i) for (int j = 0; j < 4; ++j) r |= w.path[i][j].resize(j == 3 ? bytes / 2 : bytes);      // [3]: the 8-byte meta records
         r |= w.hits.resize(bytes);
         r |= w.order.resize(bytes / 4);
-        r |= w.order_coat.resize(bytes / 4);
         if (c->knobs.shade_split) r |= w.nee_flags.resize(bytes / 16);
 #if HIPR_RAY_SORT
         if (c->knobs.coherence_sort) {      // both queues of a fused launch: 2 x n_slots entries
@@ -2792,6 +2788,31 @@ int hipr_debug_trace_shadow(HiprContext* c, const float* rays, uint32_t n, float
     for (uint32_t i = 0; i < n; ++i) out_transmittance[i] = result[4 * i];
     c->total = {};
     c->total.shadow_rays = n;
+    return HIPR_OK;
+}
+
+// The listing pass (kernels.h k_classify_hits) on given hits, through the launch path of a pass (classify_hits).
+int hipr_debug_classify_hits(HiprContext* c, const float* hits_n4, uint32_t n, int coat_classes, uint32_t grid, uint32_t* out_order) {
+    if (int s = check_context(c)) return s;
+    if (!hits_n4 || !out_order) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null argument");
+    if (grid > 65536u) return fail(HIPR_ERROR_INVALID_ARGUMENT, "grid");
+    if (n == 0) return HIPR_OK;
+    if (coat_classes) {      // the kernel reads one class byte per surface hit: every id must name a triangle of the resident scene
+        if (!c->scene.ready || !c->scene.triangle_class.ptr) return fail(HIPR_ERROR_NOT_READY, "no scene uploaded");
+        for (uint32_t i = 0; i < n; ++i) {
+            uint32_t id;
+            std::memcpy(&id, hits_n4 + 4 * size_t(i) + 3, 4);
+            if (id != HIPR_HIT_MISS && !(id & HIPR_HIT_LIGHT) && id >= c->scene.args.triangle_count) return fail(HIPR_ERROR_INVALID_ARGUMENT, "a hit names a triangle the scene does not hold");
+        }
+    }
+    if (int s = drain(c)) return s;
+    DeviceBuffer bh, bc, bo;
+    if (bh.upload(hits_n4, size_t(n) * 16, c->stream) | bc.upload(&n, 4, c->stream) | bo.resize(size_t(n) * 4)) return HIPR_ERROR_OUT_OF_MEMORY;
+    HIP_TRY(hipMemsetAsync(bo.ptr, 0xFF, size_t(n) * 4, c->stream));      // a place the pass leaves out shows as 0xFFFFFFFF
+    classify_hits(c, c->stream, bh.as<float4>(), bc.as<uint32_t>(), n, bo.as<uint32_t>(), coat_classes != 0, grid);
+    HIP_TRY(hipGetLastError());
+    if (int finish_status = finish_all(c)) return finish_status;
+    HIP_TRY(hipMemcpy(out_order, bo.ptr, size_t(n) * 4, hipMemcpyDeviceToHost));
     return HIPR_OK;
 }
 

@@ -18,6 +18,7 @@
 
 #include "device_shading.h"
 #include "fast_divide.h"
+#include "shade_schedule.h"
 
 namespace hipr {
 
@@ -1095,64 +1096,49 @@ __global__ __launch_bounds__(256) void k_build_shade_triangles(DeviceScene sc, f
 // ---------------------------------------------------------------------------------------------
 // K5c: the order in which the shade kernel takes the rays of a bounce. A wave of k_shade runs the surface code -- attributes, material, three RIS light
 // candidates, BSDF sample: thousands of instructions -- as long as ONE of its 64 rays hit a triangle, and 42 % of the atrium's traced rays did not
-// (they escaped, hit a light, or sit in a dead slot): measured 28 of 64 lanes live per instruction. This pass lists the indices of the rays that hit a
-// triangle from the front of `order` and all others from its back (one 64-bit atomic per block of 256 rays reserves both ranges; inside a block the rays
-// keep their order), so that all but one or two of the shade kernel's batches are of one kind. Which rays are shaded, and what each yields, is unchanged.
+// (they escaped, hit a light, or sit in a dead slot): measured 28 of 64 lanes live per instruction. This pass lists the rays CHUNK by chunk of 4096 queue
+// entries: places [chunk, chunk + 4096) of `order` hold the chunk's own entries as [plain surface hits | coated surface hits | everything else], each class in
+// queue order, so that all but one or two waves of the 16 shade batches of a chunk are of one kind. The last chunk is partial: its m entries fill its first m
+// places. Which rays are shaded, and what each yields, is unchanged.
+// The listing is local on purpose. The kinds are interleaved entry by entry in the queue and a 128 B line holds 8 or 16 records, so the hit batches and the
+// other batches of a stretch of the queue want the same lines. Rounds 3 to 6 listed the hits from the front of `order` and the others from its back over the
+// WHOLE queue (two global atomics per chunk): k_shade then swept the queue twice, gigabytes apart, and fetched nearly every line of it twice. With the chunk's
+// places together, the shade kernel's schedule (shade_schedule.h) takes both kinds of a chunk through one L2 within a round or two
+// (profiles/ab_shade_chunk_listing.txt). No atomics, no counters to zero, and the listing is the same from run to run.
 // ---------------------------------------------------------------------------------------------
-constexpr uint32_t CLASSIFY_ROUNDS = 16;      // rounds of 256 rays a block lists per reservation: 4096 rays per atomic (one 64-bit atomic on one address costs ~8 ns device-wide)
+constexpr uint32_t CLASSIFY_ROUNDS = 16;      // rounds of 256 rays a block lists per chunk: 4096 rays
+static_assert(SHADE_CHUNK_BATCHES * uint32_t(SHADE_BLOCK) == 256u * CLASSIFY_ROUNDS, "shade_schedule.h deals the shade batches of this pass's chunks");
 // Round 4: the surface hits are listed in two classes. The shade kernel's instruction stream forks on the material where a COAT is present -- a second
 // specular layer: make_default prepares it, every BSDF evaluation (three light candidates and the sample) adds its lobe -- and a wave that holds one
 // coated hit among its 64 walks that code for all of them (atrium: 4 of 25 materials are coated, i.e. nearly every wave of 64 mixed hits). `triangle_class`
-// holds one byte per scene triangle (bit 0: its material has a coat; written at upload), the coated hits go to a list of their own (`order_coat`, counted in
-// taken[1]) and the shade kernel takes the entries as [plain surface hits | coated surface hits | everything else]: order[j] for j < plain,
-// order_coat[j - plain] for the next `coated`, order[j] again behind them (the others were listed from the back of `order`: they end at n - 1).
-// MEASURED (profiles/r04_ab_shade_classes.txt): frames bit-identical (tests/test_gpu_coverage.py), atrium shade 17.1 -> 17.3 ms per step: only 4.6 % of the
-// atrium's surface hits are coated (the four coated materials cover little area), so 95 % of the waves did skip the coat code -- and the byte gather per
-// hit in this pass cost more than that code did. Off by default (HIPR_SHADE_CLASSES=1 turns it on); the listing is then round 3's two kinds.
+// holds one byte per scene triangle (bit 0: its material has a coat; written at upload); the coated hits of a chunk stand between its plain hits and its others.
+// MEASURED (profiles/r04_ab_shade_classes.txt, with the queue-wide listing of that round): frames bit-identical (tests/test_gpu_coverage.py), atrium shade
+// 17.1 -> 17.3 ms per step: only 4.6 % of the atrium's surface hits are coated (the four coated materials cover little area), so 95 % of the waves did skip
+// the coat code -- and the byte gather per hit in this pass cost more than that code did. Off by default (HIPR_SHADE_CLASSES=1 turns it on); the listing is
+// then round 3's two kinds.
 template <bool CLASSES>
 __global__ __launch_bounds__(256) void k_classify_hits(const float4* __restrict__ hits, const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ order,
-                                                       unsigned long long* taken /* [0] low word: plain surface hits listed, high word: others listed; [1]: coated surface hits listed */,
-                                                       const unsigned char* __restrict__ triangle_class, uint32_t* __restrict__ order_coat) {
-    __shared__ uint32_t s_surface[4], s_other[4], s_coat[4];
+                                                       const unsigned char* __restrict__ triangle_class) {
     static_assert(CLASSIFY_ROUNDS * 4u == 64u, "the prefix of the (round, wave) table is one wave-wide scan");
     __shared__ uint32_t s_table[3][CLASSIFY_ROUNDS * 4];      // per class: a wave's rays of each round, then their exclusive prefix in (round, wave) order
-    __shared__ unsigned long long s_base;
-    __shared__ uint32_t s_coat_base;
+    __shared__ uint32_t s_total[3];                           // per class: the chunk's rays
     const uint32_t n = *count_ptr;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const unsigned long long lt = (1ull << lane) - 1ull;
     for (uint32_t chunk = blockIdx.x * (256u * CLASSIFY_ROUNDS); chunk < n; chunk += gridDim.x * (256u * CLASSIFY_ROUNDS)) {
-        // pass 1: what the chunk holds, one bit per round and thread
-        uint32_t surface_bits = 0u, valid_bits = 0u, coat_bits = 0u;
+        // what the chunk holds, one bit per round and thread; every wave leaves its count of each class for each round in a table
+        uint32_t surface_bits = 0u, other_bits = 0u, coat_bits = 0u;
+        unsigned long long surface_masks[CLASSIFY_ROUNDS], other_masks[CLASSIFY_ROUNDS], coat_masks[CLASSES ? CLASSIFY_ROUNDS : 1];
 #pragma unroll
         for (uint32_t r = 0; r < CLASSIFY_ROUNDS; ++r) {
             const uint32_t i = chunk + r * 256u + threadIdx.x;
             const uint32_t id = i < n ? __float_as_uint(hits[i].w) : HIPR_HIT_MISS;
-            const bool surface = i < n && id != HIPR_HIT_MISS && !(id & HIPR_HIT_LIGHT);
-            const bool coated = CLASSES && surface && (triangle_class[id] & 1u);
-            surface_bits |= (surface && !coated) ? (1u << r) : 0u;
+            const bool hit = i < n && id != HIPR_HIT_MISS && !(id & HIPR_HIT_LIGHT);
+            const bool coated = CLASSES && hit && (triangle_class[id] & 1u);
+            const bool surface = hit && !coated, other = i < n && !hit;
+            surface_bits |= surface ? (1u << r) : 0u;
             coat_bits |= coated ? (1u << r) : 0u;
-            valid_bits |= i < n ? (1u << r) : 0u;
-        }
-        uint32_t surfaces = uint32_t(__popc(surface_bits)), coats = uint32_t(__popc(coat_bits)), others = uint32_t(__popc(valid_bits & ~(surface_bits | coat_bits)));
-        for (int off = 32; off > 0; off >>= 1) { surfaces += __shfl_xor(surfaces, off); others += __shfl_xor(others, off); coats += __shfl_xor(coats, off); }
-        if (lane == 0) { s_surface[wave] = surfaces; s_other[wave] = others; s_coat[wave] = coats; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            s_base = atomicAdd(taken, (unsigned long long)(s_surface[0] + s_surface[1] + s_surface[2] + s_surface[3]) |
-                                      (unsigned long long)(s_other[0] + s_other[1] + s_other[2] + s_other[3]) << 32);
-            const uint32_t block_coats = CLASSES ? s_coat[0] + s_coat[1] + s_coat[2] + s_coat[3] : 0u;
-            s_coat_base = block_coats ? uint32_t(atomicAdd(taken + 1, (unsigned long long)block_coats)) : 0u;
-        }
-        __syncthreads();
-        // pass 2: places inside the block's ranges, rays in (round, thread) order. Every wave leaves its count of each class for each round in a table, the first wave
-        // turns the table into exclusive prefixes in (round, wave) order -- one barrier on either side of that instead of the two per ROUND of a running sum (round 4:
-        // the pass was the latency of its 34 barriers per chunk, profiles/r04_ab_knobs.txt) -- then every thread places its rays.
-        const uint32_t front = uint32_t(s_base), back = uint32_t(s_base >> 32), coat_front = s_coat_base;
-        unsigned long long surface_masks[CLASSIFY_ROUNDS], other_masks[CLASSIFY_ROUNDS], coat_masks[CLASSES ? CLASSIFY_ROUNDS : 1];
-#pragma unroll
-        for (uint32_t r = 0; r < CLASSIFY_ROUNDS; ++r) {
-            const bool surface = (surface_bits >> r) & 1u, coated = (coat_bits >> r) & 1u, other = ((valid_bits & ~(surface_bits | coat_bits)) >> r) & 1u;
+            other_bits |= other ? (1u << r) : 0u;
             surface_masks[r] = wave_ballot(surface); other_masks[r] = wave_ballot(other);
             if (CLASSES) coat_masks[r] = wave_ballot(coated);
             if (lane == 0) {
@@ -1161,6 +1147,8 @@ __global__ __launch_bounds__(256) void k_classify_hits(const float4* __restrict_
             }
         }
         __syncthreads();
+        // the first wave turns the table into exclusive prefixes in (round, wave) order -- one barrier on either side of that instead of the two per ROUND of a
+        // running sum (round 4: the pass was the latency of its 34 barriers per chunk, profiles/r04_ab_knobs.txt) -- then every thread places its rays.
         if (wave == 0) {        // 16 rounds x 4 waves = 64 entries: one wave-wide exclusive scan per class
 #pragma unroll
             for (int c = 0; c < (CLASSES ? 3 : 2); ++c) {
@@ -1168,16 +1156,18 @@ __global__ __launch_bounds__(256) void k_classify_hits(const float4* __restrict_
                 uint32_t inclusive = mine;
                 for (int off = 1; off < 64; off <<= 1) { const uint32_t up = __shfl_up(inclusive, off); inclusive += lane >= uint32_t(off) ? up : 0u; }
                 s_table[c][lane] = inclusive - mine;
+                if (lane == 63u) s_total[c] = inclusive;
             }
         }
         __syncthreads();
+        // places inside the chunk's own stretch of `order`, rays in (round, thread) = queue order: [plain surface hits | coated surface hits | everything else]
+        const uint32_t coat_front = chunk + s_total[0], other_front = coat_front + (CLASSES ? s_total[2] : 0u);
 #pragma unroll
         for (uint32_t r = 0; r < CLASSIFY_ROUNDS; ++r) {
-            const bool surface = (surface_bits >> r) & 1u, coated = (coat_bits >> r) & 1u, other = ((valid_bits & ~(surface_bits | coat_bits)) >> r) & 1u;
             const uint32_t i = chunk + r * 256u + threadIdx.x;
-            if (surface) order[front + s_table[0][r * 4u + wave] + uint32_t(__popcll(surface_masks[r] & lt))] = i;
-            if (CLASSES && coated) order_coat[coat_front + s_table[2][r * 4u + wave] + uint32_t(__popcll(coat_masks[r] & lt))] = i;
-            if (other) order[n - 1u - (back + s_table[1][r * 4u + wave] + uint32_t(__popcll(other_masks[r] & lt)))] = i;
+            if ((surface_bits >> r) & 1u) order[chunk + s_table[0][r * 4u + wave] + uint32_t(__popcll(surface_masks[r] & lt))] = i;
+            if (CLASSES && ((coat_bits >> r) & 1u)) order[coat_front + s_table[2][r * 4u + wave] + uint32_t(__popcll(coat_masks[r] & lt))] = i;
+            if ((other_bits >> r) & 1u) order[other_front + s_table[1][r * 4u + wave] + uint32_t(__popcll(other_masks[r] & lt))] = i;
         }
         __syncthreads();        // the table is written again by the next chunk
     }

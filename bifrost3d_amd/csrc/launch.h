@@ -14,16 +14,13 @@ struct ShadeLaunch {
     int entry;                 // HIPR_ENTRY_*
     PathState in;
     const float4* hits;
-    const uint32_t* order;     // k_classify_hits: the queue entries in the order the kernel takes them (surface hits first); nullptr = queue order
-    const uint32_t* order_coat;               // the coated surface hits, listed apart
-    const unsigned long long* listed;         // k_classify_hits' counters of this bounce: [0] low word = plain surface hits, [1] = coated surface hits
+    const uint32_t* order;     // k_classify_hits: the queue entries in the order the kernel takes them (chunk by chunk, surface hits first); nullptr = queue order
     PathState out;
     ShadowQueue shadows;
     float4* radiance;
     const uint32_t* in_count;
     unsigned long long* out_counts;   // {paths that continue, shadow rays queued}: one 8-byte word so that a block reserves both with one atomic
-    unsigned long long* zero_a;       // two 8-byte counters the kernel zeroes for the kernels of the next bounce (nullptr: none)
-    unsigned long long* zero_b;
+    unsigned long long* zero_a;       // the 8-byte counter pair the kernel zeroes for the kernels of the next bounce (nullptr: none)
     unsigned char* nee_flags;         // one byte per queue entry: non-null runs the kernel as its two halves (shade_kernel.h SHADE_PART_*)
     DeviceCounters* counters;
     bool textures;                    // the scene holds textures or an environment map (false: k_shade<..., TEXTURES = 0>)

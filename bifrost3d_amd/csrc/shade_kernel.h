@@ -5,6 +5,7 @@
 #pragma once
 
 #include "kernels.h"
+#include "shade_schedule.h"
 
 namespace hipr {
 
@@ -291,13 +292,25 @@ HD void shade_path(const DeviceScene& sc, const HiprCameraState& cam, int entry,
         if (PART == SHADE_PART_NEE) return;
     }
     const bool light_sample_kept = PART == SHADE_PART_BSDF ? nee_kept_a_sample : pdf_is_valid(kept.pdf);
+    // The last bounce: the path ends here whatever the BSDF sample would be (bounces + 1 > max_bounce_count below), so it is not drawn. Per lane, behind a branch:
+    // a wave of last-bounce hits skips the sampling code (rejected hits keep their bounce count, so a queue mixes counts by a few entries). The two dozen
+    // instructions behind the sample still run, on a sample without a PDF: out.continues comes out false as it always did. (Leaving the function here instead costs
+    // k_shade<Default> 28 B more scratch at its 168 VGPRs; this form needs none: profiles/ab_shade_chunk_listing.txt.)
+    // The empty asm statement keeps the sample behind a branch of its own (s_cbranch_execz): without it the compiler folds the condition into the sample's inner
+    // branches and selects, and a wave of last-bounce hits still walks most of the code. That is the behaviour of one compiler (ROCm 7.2.0), not of the language:
+    // the result is the same either way, the saving is to be looked for again after a compiler update (profiles/ab_shade_chunk_listing.txt, resource lines).
+    const bool last_bounce = !AOV && bounces >= cam.max_bounce_count;
 
     // --- BSDF sampling (MonteCarlo.cu:204-232) ---------------------------------------------------
+    Sample bs = sample_none();
+    if (!last_bounce) {
+        asm volatile("");
 #if HIPR_SHADE_TERMS
-    const Sample bs = shading_sample<MODELS>(shading, terms, wo, mk3(bsdf_u.x, bsdf_u.y, bsdf_u.z));
+        bs = shading_sample<MODELS>(shading, terms, wo, mk3(bsdf_u.x, bsdf_u.y, bsdf_u.z));
 #else
-    const Sample bs = shading_sample<MODELS>(shading, wo, mk3(bsdf_u.x, bsdf_u.y, bsdf_u.z));
+        bs = shading_sample<MODELS>(shading, wo, mk3(bsdf_u.x, bsdf_u.y, bsdf_u.z));
 #endif
+    }
     const bool is_reflection = bs.dir.z >= 0;
     f3 direction = to_world(tbn, bs.dir);
     float new_pdf = bs.pdf;
@@ -318,7 +331,8 @@ HD void shade_path(const DeviceScene& sc, const HiprCameraState& cam, int entry,
     }
 }
 
-// Persistent blocks (the launch sizes the grid to what is resident) walk the queue with a grid stride and run one iteration
+// Persistent blocks (the launch sizes the grid to what is resident) walk the queue one batch per round (shade_place: a listed queue chunk by chunk on one XCD,
+// shade_schedule.h; the queue's own order with the grid stride) and run one iteration
 // AHEAD on their inputs: while a batch of 256 paths is shaded, the path state and hit of the next batch are in flight; its
 // triangle, shading record and material are requested once the hit id has arrived, behind the compaction barriers. The four
 // dependent gathers of a hit (path state -> hit -> triangle / record -> material) are thereby off the critical path.
@@ -341,13 +355,18 @@ HD ShadeInputs shade_fetch_inputs(const PathState& in, const float4* hits, uint3
     }
     return r;
 }
-// The queue entry that place j of the shading order holds (k_classify_hits; the queue's own order without it).
-// The queue entry the kernel takes j-th: queue order, or k_classify_hits' listing [plain surface hits | coated surface hits | everything else].
-struct ShadeOrder { const uint32_t* order; const uint32_t* order_coat; uint32_t plain, coated; };
-HD uint32_t shade_entry(const ShadeOrder& o, uint32_t j, uint32_t n) {
+// The queue entry that place j of the shading order holds: k_classify_hits' listing (chunk by chunk [plain surface hits | coated surface hits | everything else]),
+// or the queue's own order without it. Places from n on hold none.
+HD uint32_t shade_entry(const uint32_t* order, uint32_t j, uint32_t n) {
     if (j >= n) return HIPR_DEAD_SLOT;
-    if (!o.order) return j;
-    return (j >= o.plain && j - o.plain < o.coated) ? o.order_coat[j - o.plain] : o.order[j];
+    return order ? order[j] : j;
+}
+// The place thread `thread` of block `block` takes in round `round`; n (no place) in a round that holds no batch for the block. A listed queue is taken chunk by
+// chunk on one XCD (shade_schedule.h), the queue's own order with the plain grid stride as ever.
+HD uint32_t shade_place(bool listed, uint32_t block, uint32_t round, uint32_t grid, uint32_t thread, uint32_t n) {
+    const uint32_t batches = (n + uint32_t(SHADE_BLOCK) - 1u) / uint32_t(SHADE_BLOCK);
+    const uint32_t b = listed ? shade_batch(block, round, grid, batches) : shade_batch_strided(block, round, grid, batches);
+    return b == SHADE_NO_BATCH ? n : b * uint32_t(SHADE_BLOCK) + thread;
 }
 HD bool shade_hits_triangle(const ShadeInputs& in) {
     const uint32_t id = __float_as_uint(in.hit.w);
@@ -394,9 +413,9 @@ constexpr int shade_waves_per_simd(int part) { return part == SHADE_PART_ALL ? H
 // ARITHMETIC (HIPR_ARITHMETIC_*) names the build of the shade unit the instantiation belongs to: shade.hip is compiled twice into one library (fast and exact arithmetic,
 // hipr_set_arithmetic), and two kernels of one name would share one host-side launch stub.
 template <int MODELS, bool AOV, int PART, int TEXTURES, int ARITHMETIC>
-__global__ __launch_bounds__(SHADE_BLOCK, shade_waves_per_simd(PART)) void k_shade(DeviceScene sc, HiprCameraState cam, FrameInfo frame, int entry, PathState in, const float4* hits, const uint32_t* order_list, const uint32_t* order_coat, const unsigned long long* listed, PathState out,
+__global__ __launch_bounds__(SHADE_BLOCK, shade_waves_per_simd(PART)) void k_shade(DeviceScene sc, HiprCameraState cam, FrameInfo frame, int entry, PathState in, const float4* hits, const uint32_t* order, PathState out,
                                                         ShadowQueue shadows, float4* radiance, const uint32_t* count_ptr, unsigned long long* out_counts,
-                                                        unsigned long long* zero_a, unsigned long long* zero_b, unsigned char* nee_flags, DeviceCounters* counters) {
+                                                        unsigned long long* zero_a, unsigned char* nee_flags, DeviceCounters* counters) {
 #if HIPR_SHADE_ONE_BARRIER
     __shared__ unsigned long long s_arrivals[2], s_totals[2];
     __shared__ uint32_t s_base[4];
@@ -413,19 +432,17 @@ __global__ __launch_bounds__(SHADE_BLOCK, shade_waves_per_simd(PART)) void k_sha
     __shared__ HiprLight s_lights[SHADE_LDS_LIGHTS];
 #endif
     const uint32_t n = *count_ptr;
-    ShadeOrder order = {order_list, order_coat, 0u, 0u};
-    if (order_list && listed) { order.plain = uint32_t(listed[0]); order.coated = uint32_t(listed[1]); }      // k_classify_hits has run on this stream
-    // The counters the NEXT bounce's kernels fill start from zero; nothing on the device reads or writes them while this kernel runs (hiprenderer.hip
-    // enqueue_bounce). A fill command in the stream for each costs more than this whole kernel does on a bounce of a few thousand paths.
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (zero_a) *zero_a = 0ull;
-        if (zero_b) { zero_b[0] = 0ull; zero_b[1] = 0ull; }      // the listing pass's two counters of the next bounce
-    }
-    if (blockIdx.x * SHADE_BLOCK >= n) return;
-    const uint32_t stride = gridDim.x * SHADE_BLOCK;
-    uint32_t base = blockIdx.x * SHADE_BLOCK;
-    ShadeInputs cur = shade_fetch_inputs(in, hits, shade_entry(order, base + threadIdx.x, n));
-    uint32_t next_entry = shade_entry(order, base + stride + threadIdx.x, n);      // the entries are looked up two batches ahead, the inputs one
+    // The counter the NEXT bounce's kernels fill starts from zero; nothing on the device reads or writes it while this kernel runs (hiprenderer.hip
+    // enqueue_bounce). A fill command in the stream costs more than this whole kernel does on a bounce of a few thousand paths.
+    if (blockIdx.x == 0 && threadIdx.x == 0 && zero_a) *zero_a = 0ull;
+    // The block's batches, one per round (shade_place). A round may hold none for it -- its places are then past the end, and every lane idles through it like the
+    // lanes past the end of the last batch do.
+    const bool listed = order != nullptr;      // k_classify_hits has run on this stream
+    const uint32_t batches = (n + uint32_t(SHADE_BLOCK) - 1u) / uint32_t(SHADE_BLOCK);
+    const uint32_t rounds = listed ? shade_rounds(blockIdx.x, gridDim.x, batches) : shade_rounds_strided(blockIdx.x, gridDim.x, batches);
+    if (rounds == 0u) return;
+    ShadeInputs cur = shade_fetch_inputs(in, hits, shade_entry(order, shade_place(listed, blockIdx.x, 0u, gridDim.x, threadIdx.x, n), n));
+    uint32_t next_entry = shade_entry(order, shade_place(listed, blockIdx.x, 1u, gridDim.x, threadIdx.x, n), n);      // the entries are looked up two batches ahead, the inputs one
     for (uint32_t w = threadIdx.x; w < SOBOL_TABLE_WORDS; w += SHADE_BLOCK) s_sobol[w] = sc.sobol_tables[w];
 #if HIPR_SHADE_LDS_TABLES
     for (uint32_t w = threadIdx.x; w < 32 * 32; w += SHADE_BLOCK) { s_ggx_rho[w] = sc.tables.ggx_rho[w]; s_alpha[w] = sc.tables.alpha[w]; }
@@ -450,20 +467,21 @@ __global__ __launch_bounds__(SHADE_BLOCK, shade_waves_per_simd(PART)) void k_sha
 #else
     const uint32_t wave = threadIdx.x >> 6;
 #endif
-    for (; base < n; base += stride) {
+    for (uint32_t round = 0; round < rounds; ++round) {
         // inputs of the next batch: issued now, first used after this batch has been shaded
         ShadeInputs next = shade_fetch_inputs(in, hits, next_entry);
-        next_entry = shade_entry(order, base + 2u * stride + threadIdx.x, n);
+        next_entry = shade_entry(order, shade_place(listed, blockIdx.x, round + 2u, gridDim.x, threadIdx.x, n), n);
 
         ShadeOutput so;
         so.continues = so.shadow = so.shaded = false;
 #ifdef HIPR_SHADE_EXTRA_READ      // experiment: 16 (or 32) more bytes read per queue entry, coalesced -- what does a byte of queue traffic cost this kernel?
         {
-            const float4 extra = shadows.radiance[base + threadIdx.x];
-            if (extra.w == 12345.678f) radiance[base + threadIdx.x] = extra;
+            const uint32_t at = min(shade_place(listed, blockIdx.x, round, gridDim.x, threadIdx.x, n), n - 1u);
+            const float4 extra = shadows.radiance[at];
+            if (extra.w == 12345.678f) radiance[at] = extra;
 #if HIPR_SHADE_EXTRA_READ > 1
-            const float4 extra2 = shadows.d_slot[base + threadIdx.x];
-            if (extra2.w == 12345.678f) radiance[base + threadIdx.x] = extra2;
+            const float4 extra2 = shadows.d_slot[at];
+            if (extra2.w == 12345.678f) radiance[at] = extra2;
 #endif
         }
 #endif

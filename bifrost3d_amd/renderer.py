@@ -377,6 +377,14 @@ class Context:
         self._check(self.lib.hipr_debug_trace_shadow(self.handle, rays.ctypes.data_as(fp), len(rays), out.ctypes.data_as(fp)), "hipr_debug_trace_shadow")
         return out
 
+    def debug_classify_hits(self, hits, coat_classes=False, grid=0):
+        """The listing pass of a bounce on the given (n, 4) hits -> order (n,): the queue entry the shade kernel takes at each place (hipr_debug_classify_hits)."""
+        hits = np.ascontiguousarray(hits, np.float32).reshape(-1, 4)
+        order = np.zeros(len(hits), np.uint32)
+        self._check(self.lib.hipr_debug_classify_hits(self.handle, hits.ctypes.data_as(C.POINTER(C.c_float)), len(hits), int(bool(coat_classes)), int(grid),
+                                                      order.ctypes.data_as(C.POINTER(C.c_uint32))), "hipr_debug_classify_hits")
+        return order
+
     def debug_trace_fused(self, closest_rays, skip, shadow_rays):
         """One fused launch over both queues, as a bounce makes it: -> (hits (n_closest, 4), transmittance (n_shadow,)). Either set of rays may be empty."""
         closest_rays = np.ascontiguousarray(closest_rays, np.float32).reshape(-1, 8)

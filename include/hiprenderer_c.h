@@ -670,6 +670,11 @@ int hipr_debug_trace_shadow(HiprContext* context, const float* rays, uint32_t n,
  * n_shadow shadow rays in the layouts of the two entries above; either count may be 0, and its pointers are then not read. */
 int hipr_debug_trace_fused(HiprContext* context, const float* closest_rays, const uint32_t* skip, uint32_t n_closest, const float* shadow_rays, uint32_t n_shadow,
                            float* out_hits, float* out_transmittance);
+/* K5c: the listing pass of a bounce on n given hits (hits_n4: float4 {t, u, v, bits(triangle | 0x80000000 + light | 0xFFFFFFFF miss)} per queue entry). out_order[p]
+ * = the queue entry the shade kernel takes at place p: every chunk of 4096 places holds that chunk's own entries as [plain surface hits | coated surface hits |
+ * everything else], each class in queue order. coat_classes != 0 lists the hits on triangles of a coated material apart (needs an uploaded scene, and every
+ * triangle id below its triangle count); 0 lists them with the plain ones. grid: blocks of the launch, 0 = what a pass takes. Host pointers. */
+int hipr_debug_classify_hits(HiprContext* context, const float* hits_n4, uint32_t n, int coat_classes, uint32_t grid, uint32_t* out_order);
 /* The uploaded (or device-refitted, or material-updated) scene arrays as the device holds them: HiprTriangle[triangle_count], HiprSlot8[wide8_slot_count], the
  * trace records (48 bytes per triangle), the shading records (128 bytes per triangle), the class bytes of the listing pass (one per triangle),
  * HiprMaterial[material_count], HiprInstance[instance_count]. */
