@@ -129,6 +129,17 @@ class HiprSceneRebuildResult(C.Structure):
     _fields_ = [("node_count", c_u32), ("deepest", c_u32), ("wide8", HiprWide8BuildResult), ("half_area", C.c_double)]
 
 
+EDIT_NEW_INSTANCE = 0xFFFFFFFF
+
+
+class HiprInstanceEdit(C.Structure):
+    _fields_ = [("source", c_u32), ("primitive_count", c_u32), ("instance", HiprInstance)]
+
+
+class HiprSceneEditResult(C.Structure):
+    _fields_ = [("triangle_count", c_u32), ("instance_count", c_u32), ("node_count", c_u32), ("deepest", c_u32), ("wide8", HiprWide8BuildResult), ("_pad", c_u32), ("half_area", C.c_double)]
+
+
 class HiprRefitResult(C.Structure):
     _fields_ = [("needs_rebuild", c_i32), ("child_half_area", C.c_double), ("uploaded_half_area", C.c_double), ("grid_min", c_f * 3), ("grid_cell", c_f * 3)]
 
@@ -179,11 +190,12 @@ class HiprKernelTimes(C.Structure):
 
 assert C.sizeof(HiprMaterial) == 64 and C.sizeof(HiprLight) == 48 and C.sizeof(HiprVertexGeometry) == 16
 assert C.sizeof(HiprTexture) == 24 and C.sizeof(HiprCameraState) == 180 and C.sizeof(HiprTriangle) == 48 and C.sizeof(HiprBvhNode) == 64 and C.sizeof(HiprInstance) == 80
+assert C.sizeof(HiprInstanceEdit) == 88 and C.sizeof(HiprSceneEditResult) == 72
 
 # Every symbol include/hiprenderer_c.h declares; tests check the library exports all of them.
 C_ABI_SYMBOLS = (
     "hipr_create", "hipr_destroy", "hipr_last_error", "hipr_device_count", "hipr_set_stream",
-    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_build_bvh2", "hipr_group_build_bvh2", "hipr_debug_build_times", "hipr_build_wide8", "hipr_group_build_wide8", "hipr_debug_collapse_times", "hipr_rebuild_scene_trees", "hipr_group_rebuild_scene_trees", "hipr_debug_rebuild_times", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
+    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_build_bvh2", "hipr_group_build_bvh2", "hipr_debug_build_times", "hipr_build_wide8", "hipr_group_build_wide8", "hipr_debug_collapse_times", "hipr_rebuild_scene_trees", "hipr_group_rebuild_scene_trees", "hipr_edit_scene_instances", "hipr_group_edit_scene_instances", "hipr_debug_rebuild_times", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
     "hipr_set_frame", "hipr_owned_pixel_count",
     "hipr_render_pass", "hipr_set_samples_per_pass", "hipr_trace_pass", "hipr_accumulate_samples", "hipr_read_accumulation", "hipr_scatter_tiles", "hipr_synchronize", "hipr_get_counters",
     "hipr_device_malloc", "hipr_device_free", "hipr_device_memset", "hipr_copy_to_host", "hipr_present_flipped",
@@ -240,6 +252,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.hipr_debug_collapse_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.hipr_rebuild_scene_trees.argtypes = [vp, c_u32, vp, c_u32, vp, vp, c_u32, C.POINTER(HiprSceneRebuildResult)]
     lib.hipr_group_rebuild_scene_trees.argtypes = [vp, c_u32, vp, c_u32, vp, vp, c_u32, C.POINTER(HiprSceneRebuildResult)]
+    lib.hipr_edit_scene_instances.argtypes = [vp, C.POINTER(HiprInstanceEdit), c_u32, c_u32, vp, c_u32, vp, c_u32, vp, c_u32, C.POINTER(HiprSceneEditResult)]
+    lib.hipr_group_edit_scene_instances.argtypes = [vp, C.POINTER(HiprInstanceEdit), c_u32, c_u32, vp, c_u32, vp, c_u32, vp, c_u32, C.POINTER(HiprSceneEditResult)]
     lib.hipr_debug_rebuild_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.hipr_debug_read_scene_buffer.argtypes = [vp, C.c_int, vp, c_u64]
     lib.hipr_set_scene_state.argtypes = [vp, C.POINTER(HiprSceneState)]

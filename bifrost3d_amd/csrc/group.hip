@@ -376,6 +376,26 @@ int hipr_group_rebuild_scene_trees(HiprGroup* g, uint32_t max_depth, HiprBvhNode
     return HIPR_OK;
 }
 
+// hipr_edit_scene_instances on every member, as the rebuild above: the same list over the same arrays gives the same scene.
+int hipr_group_edit_scene_instances(HiprGroup* g, const HiprInstanceEdit* edits, uint32_t edit_count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_order,
+                                    uint32_t order_capacity, HiprSlot8* out_slots, uint32_t slot_capacity, HiprSceneEditResult* out) {
+    if (!g || !out || g->members.empty()) return HIPR_ERROR_INVALID_ARGUMENT;
+    std::vector<HiprSceneEditResult> results(g->members.size());
+    const int status = for_each_member(g, [&](Member& m, uint32_t index) {
+        return index == 0 ? hipr_edit_scene_instances(m.context, edits, edit_count, max_depth, out_nodes, node_capacity, out_order, order_capacity, out_slots, slot_capacity, &results[0])
+                          : hipr_edit_scene_instances(m.context, edits, edit_count, max_depth, nullptr, 0, nullptr, 0, nullptr, 0, &results[index]);
+    });
+    if (status) return status;
+    for (const HiprSceneEditResult& r : results)
+        if (std::memcmp(&r, &results[0], sizeof(r))) {
+            hipr_internal_set_last_error("hipr_group_edit_scene_instances: the members' scenes disagree");
+            fprintf(stderr, "hiprenderer: hipr_group_edit_scene_instances: the members' scenes disagree\n");
+            return HIPR_ERROR_HIP;
+        }
+    *out = results[0];
+    return HIPR_OK;
+}
+
 int hipr_group_update_scene_materials(HiprGroup* g, const HiprMaterialUpdate* materials, uint32_t material_count, const HiprInstanceMaterial* assignments, uint32_t assignment_count) {
     if (!g) return HIPR_ERROR_INVALID_ARGUMENT;
     // Every member checks before any member writes: an edit one member refuses leaves all of them as they were.

@@ -18,6 +18,7 @@
 #include "bvh2_build.h"
 #include "wide8_build.h"
 #include "scene_rebuild.h"
+#include "instance_edit.h"
 #include "launch.h"
 
 #include <hip/hip_runtime.h>
@@ -164,6 +165,7 @@ struct ResidentScene {
     std::vector<HiprTexture> uploaded_textures;        // small; a material edit derives the texture switches from it again
     bool uploaded_environment = false;                 // the upload brought an environment description
     uint32_t uploaded_texture_count = 0, uploaded_vertex_count = 0, uploaded_index_count = 0;
+    uint32_t uploaded_mesh_attributes = 0;             // HIPR_MESH_TEXCOORDS | _TINTS | _EMISSIVE: the optional per-vertex pools the upload brought
     uint64_t uploaded_texel_bytes = 0;
 
     // device refit of the 8-wide tree (wide8_refit.h); filled at upload for scenes that bring the tree
@@ -206,6 +208,12 @@ struct ResidentScene {
         const HiprTriangle* flat; const uint8_t* flat_class; const uint32_t* order;      // the triangles in flatten order, and the new order over them
         const HiprBvhNode* nodes; uint32_t node_count, deepest;
         const HiprSlot8* slots; const HiprSlot8* host_slots; HiprWide8BuildResult wide8;
+        // hipr_edit_scene_instances: another SET of triangles and instances comes in (null: the resident ones stay, as after hipr_rebuild_scene_trees)
+        struct NewSet {
+            uint32_t triangle_count; const HiprInstance* device_instances; const std::vector<HiprInstance>* instances;
+            bool all_triangles_opaque, any_coated_triangle;      // reduced over the new set (k_edit_reduce)
+        };
+        const NewSet* new_set;
     };
     int install_rebuilt_trees(const RebuiltTrees& built, hipStream_t stream);
 
@@ -303,9 +311,10 @@ struct CollapseScratchGuard { CollapseScratch& scratch; ~CollapseScratchGuard() 
 // flat triangle array itself is BuildScratch::triangles, where hipr_build_bvh2 keeps its input.
 struct RebuildScratch {
     DeviceBuffer flat_class, claim, instance_counts, first, level_nodes, status;
+    DeviceBuffer old_to_new, created, created_first, instances;      // hipr_edit_scene_instances (instance_edit.h): a word or a record per instance
     double flatten_ms = 0.0, bvh2_ms = 0.0, collapse_ms = 0.0, install_ms = 0.0, readback_ms = 0.0;      // of the last rebuild
     void release_if_large() {
-        DeviceBuffer* all[] = {&flat_class, &claim, &instance_counts, &first, &level_nodes, &status};
+        DeviceBuffer* all[] = {&flat_class, &claim, &instance_counts, &first, &level_nodes, &status, &old_to_new, &created, &created_first, &instances};
         size_t total = 0;
         for (const DeviceBuffer* b : all) total += b->bytes;
         if (total > BuildScratch::KEEP_BYTES) for (DeviceBuffer* b : all) b->release();
@@ -1193,6 +1202,7 @@ void ResidentScene::derive_from_pools(const HiprSceneDesc* s) {
     uploaded_light_types.resize(s->light_count);
     for (uint32_t l = 0; l < s->light_count; ++l) uploaded_light_types[l] = s->lights[l].flags & HIPR_LIGHT_TYPE_MASK;
     uploaded_texture_count = s->texture_count; uploaded_vertex_count = s->vertex_count; uploaded_index_count = s->index_count; uploaded_texel_bytes = s->texel_bytes;
+    uploaded_mesh_attributes = (s->texcoords ? HIPR_MESH_TEXCOORDS : 0u) | (s->tints ? HIPR_MESH_TINTS : 0u) | (s->emissions ? HIPR_MESH_EMISSIVE : 0u);
     derive_switches_from_pools();
 }
 
@@ -1520,8 +1530,31 @@ int ResidentScene::update_materials(const HiprMaterialUpdate* changed, uint32_t 
 // The last step of hipr_rebuild_scene_trees, which has refused everything it refuses: the new resident arrays, and what an upload derives from them. The pools, the
 // instances and the lights stay; all_triangles_opaque, any_coated_triangle and the other switches cannot change under a permutation of the triangles and stay. The
 // 4-wide array is not rebuilt: tree_stale stays set until the next upload or geometry update, as after the refit.
+// After hipr_edit_scene_instances (`built.new_set`) the set of triangles and the instance list are other ones: every per-triangle and per-instance array takes the new
+// size, the instance array and its host copy become the new list, and the switches that follow the triangles and the instances are the ones reduced over the new set.
+// The pools stay, and with them the switches derived from them.
 int ResidentScene::install_rebuilt_trees(const RebuiltTrees& built, hipStream_t st) {
     begin_write();
+    if (const RebuiltTrees::NewSet* set = built.new_set) {
+        const size_t t = set->triangle_count, i = set->instances->size();
+        int r = 0;
+        r |= triangles.resize(t * sizeof(HiprTriangle));
+        r |= triangle_class.resize(t);
+        r |= shade_triangles.resize(t * SHADE_TRIANGLE_QUADS * sizeof(float4));
+        r |= trace_triangles.resize(t * 3 * sizeof(float4));
+        r |= instances.resize(i * sizeof(HiprInstance));
+        if (r) return r < 0 ? r : HIPR_ERROR_HIP;
+        HIP_TRY(hipMemcpyAsync(instances.ptr, set->device_instances, i * sizeof(HiprInstance), hipMemcpyDeviceToDevice, st));
+        args.triangles = triangles.as<float4>();
+        args.triangle_count = set->triangle_count;
+        args.shade_triangles = shade_triangles.as<float4>();
+        args.trace_triangles = trace_triangles.as<float4>();
+        args.instances = instances.as<HiprInstance>();
+        uploaded_instances = *set->instances;
+        shading_models = shading_model_mask(uploaded_instances.data(), uint32_t(uploaded_instances.size()), uploaded_materials.data());
+        all_triangles_opaque = set->all_triangles_opaque;
+        any_coated_triangle = set->any_coated_triangle;
+    }
     const uint32_t triangle_count = args.triangle_count;
     hipLaunchKernelGGL(k_rebuild_gather, dim3((triangle_count + REBUILD_BLOCK - 1) / REBUILD_BLOCK), dim3(REBUILD_BLOCK), 0, st, built.flat, built.flat_class, built.order,
                        triangles.as<HiprTriangle>(), triangle_class.as<uint8_t>(), triangle_count);
@@ -2071,20 +2104,39 @@ int hipr_debug_collapse_times(HiprContext* c, double* out4_ms) {
 
 // The trees of the resident scene rebuilt on the device, in place, from the triangles it holds (scene_rebuild.h): flatten order, the BVH2 build, the hand-over, the
 // collapse -- all in scratch, where every refusal still leaves the scene as the call found it -- and then ResidentScene::install_rebuilt_trees.
-int hipr_rebuild_scene_trees(HiprContext* c, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_order, HiprSlot8* out_slots, uint32_t slot_capacity,
-                             HiprSceneRebuildResult* out) {
+//
+// hipr_edit_scene_instances is the same call with another instance list going in and another triangle count coming out: `edit`, which its entry point has checked
+// (check_instance_edit), names the new list. The count per OLD instance is taken as without it; the flat array is then the NEW list's -- kept triangles through
+// the old-to-new table, new ones made in place (instance_edit.h) -- and everything from the BVH2 build on runs over the new count.
+struct InstanceEdit {
+    std::vector<HiprInstance> instances;      // the new list: kept entries as the device holds them, new ones as given
+    std::vector<uint32_t> source;             // per entry of the new list: the resident instance kept, BUILD_NONE for a new one
+    std::vector<uint32_t> primitive_count;    // per entry of the new list: a new instance's count (kept ones: filled from the count pass)
+    std::vector<uint32_t> old_to_new;         // per resident instance: its new index, BUILD_NONE when removed
+    uint32_t order_capacity = 0;
+    uint32_t triangle_count = 0;              // out: of the new set
+};
+static int rebuild_trees_on_the_device(HiprContext* c, const char* who, InstanceEdit* edit, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_order,
+                                       HiprSlot8* out_slots, uint32_t slot_capacity, HiprSceneRebuildResult* out) {
     if (int st = check_context(c)) return st;
     ResidentScene& r = c->scene;
-    if (!r.ready && !r.awaits_rebuild) return fail(HIPR_ERROR_NOT_READY, "hipr_rebuild_scene_trees: no scene uploaded, or one a failed call left behind");
+    if (!r.ready && !r.awaits_rebuild) return fail(HIPR_ERROR_NOT_READY, "%s: no scene uploaded, or one a failed call left behind", who);
     const uint32_t count = r.args.triangle_count, instance_count = uint32_t(r.uploaded_instances.size());
     // the conditions hipr_refit_scene_transforms refuses on: the arrays another search walks are the ones this call leaves stale, and the exhaustive search's items are the host's
     if (r.wide8.slot_count == 0 || !c->use_wide8() || r.args.trace_item_count != 0 || count > 0x55555555u || count == 0)
-        return fail(HIPR_ERROR_UNSUPPORTED, "hipr_rebuild_scene_trees: the resident scene is not traced through the 8-wide tree; rebuild on the host and call hipr_upload_scene");
-    if (count > BUILD_MAX_TRIANGLES) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_rebuild_scene_trees: %u triangles, a leaf reference holds %u", count, BUILD_MAX_TRIANGLES);
-    const uint32_t nodes_needed = std::max(std::max(count, 1u) - 1u, 1u), slots_needed = uint32_t(std::min<uint64_t>(2ull * count, W8_MAX_SLOTS));
-    if (!out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_rebuild_scene_trees: null result");
-    if (out_nodes && node_capacity < nodes_needed) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_rebuild_scene_trees: room for %u nodes, %u triangles can need %u", node_capacity, count, nodes_needed);
-    if (out_slots && slot_capacity < slots_needed) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_rebuild_scene_trees: room for %u slots, %u triangles can need %u", slot_capacity, count, slots_needed);
+        return fail(HIPR_ERROR_UNSUPPORTED, "%s: the resident scene is not traced through the 8-wide tree; rebuild on the host and call hipr_upload_scene", who);
+    if (count > BUILD_MAX_TRIANGLES) return fail(HIPR_ERROR_UNSUPPORTED, "%s: %u triangles, a leaf reference holds %u", who, count, BUILD_MAX_TRIANGLES);
+    if (!out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null result", who);
+    // the room the outputs need for `triangles` triangles; an edit knows its count once the kept instances are counted, and is checked there
+    auto outputs_fit = [&](uint32_t triangles) {
+        const uint32_t nodes_needed = std::max(std::max(triangles, 1u) - 1u, 1u), slots_needed = uint32_t(std::min<uint64_t>(2ull * triangles, W8_MAX_SLOTS));
+        if (out_nodes && node_capacity < nodes_needed) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: room for %u nodes, %u triangles can need %u", who, node_capacity, triangles, nodes_needed);
+        if (out_slots && slot_capacity < slots_needed) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: room for %u slots, %u triangles can need %u", who, slot_capacity, triangles, slots_needed);
+        if (edit && out_order && edit->order_capacity < triangles) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: room for %u order words, the new list has %u triangles", who, edit->order_capacity, triangles);
+        return int(HIPR_OK);
+    };
+    if (!edit)
+        if (int st = outputs_fit(count)) return st;
     if (int finish_status = finish_all(c)) return finish_status;      // no pending pass may go on over the new trees
     const uint32_t depth_limit = std::max(max_depth, 8u);
     BuildScratch& b = c->build;
@@ -2097,45 +2149,77 @@ int hipr_rebuild_scene_trees(HiprContext* c, uint32_t max_depth, HiprBvhNode* ou
     c->break_chain(stream);
     const auto t0 = std::chrono::steady_clock::now();
 
-    // the flatten order
-    const size_t n = count;
-    if (b.triangles.resize(n * sizeof(HiprTriangle)) | x.flat_class.resize(n) | x.claim.resize(n * 4) | x.instance_counts.resize(size_t(instance_count) * 4) | x.first.resize((size_t(instance_count) + 1) * 4) |
-        x.status.resize(REBUILD_STATUS_WORDS * 4))
-        return HIPR_ERROR_OUT_OF_MEMORY;
-    HIP_TRY(hipMemsetAsync(x.claim.ptr, 0, n * 4, stream));
+    // the flatten order: the triangles per resident instance ...
+    if (x.instance_counts.resize(size_t(instance_count) * 4) | x.status.resize(REBUILD_STATUS_WORDS * 4)) return HIPR_ERROR_OUT_OF_MEMORY;
     HIP_TRY(hipMemsetAsync(x.instance_counts.ptr, 0, size_t(instance_count) * 4, stream));
     HIP_TRY(hipMemsetAsync(x.status.ptr, 0, REBUILD_STATUS_WORDS * 4, stream));
-    const RebuildArrays a = {r.triangles.as<HiprTriangle>(), r.triangle_class.as<uint8_t>(), count, instance_count, x.instance_counts.as<uint32_t>(), x.first.as<uint32_t>(),
-                             b.triangles.as<HiprTriangle>(), x.flat_class.as<uint8_t>(), x.claim.as<uint32_t>(), x.status.as<uint32_t>()};
+    RebuildArrays a = {r.triangles.as<HiprTriangle>(), r.triangle_class.as<uint8_t>(), count, instance_count, x.instance_counts.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr, x.status.as<uint32_t>()};
     const dim3 block(REBUILD_BLOCK), per_triangle((count + REBUILD_BLOCK - 1) / REBUILD_BLOCK);
-    hipLaunchKernelGGL(k_rebuild_count, per_triangle, block, 0, stream, a);
+    hipLaunchKernelGGL(k_rebuild_count, per_triangle, block, 0, stream, a);      // reads the resident triangles, writes the counts and the flag
     HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> first(size_t(instance_count) + 1, 0u);
-    uint32_t claim_status = 0;
-    HIP_TRY(hipMemcpyAsync(first.data() + 1, x.instance_counts.ptr, size_t(instance_count) * 4, hipMemcpyDeviceToHost, stream));
+    std::vector<uint32_t> counted(size_t(instance_count) + 1, 0u);
+    HIP_TRY(hipMemcpyAsync(counted.data(), x.instance_counts.ptr, size_t(instance_count) * 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     uint64_t total = 0;
-    for (uint32_t i = 0; i < instance_count; ++i) { total += first[i + 1]; first[i + 1] = uint32_t(total); }
-    if (total != count) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_rebuild_scene_trees: %llu of %u resident triangles belong to one of the %u instances", (unsigned long long)total, count, instance_count);
+    for (uint32_t i = 0; i < instance_count; ++i) total += counted[i];
+    if (total != count) return fail(HIPR_ERROR_UNSUPPORTED, "%s: %llu of %u resident triangles belong to one of the %u instances", who, (unsigned long long)total, count, instance_count);
+    // ... and first[] of the list the flat array is made for: the resident instances, or the edit's
+    const uint32_t list_count = edit ? uint32_t(edit->instances.size()) : instance_count;
+    std::vector<uint32_t> first(size_t(list_count) + 1, 0u), created, created_first(1, 0u);
+    total = 0;
+    for (uint32_t i = 0; i < list_count; ++i) {
+        if (edit && edit->source[i] != BUILD_NONE) edit->primitive_count[i] = counted[edit->source[i]];
+        if (edit && edit->source[i] == BUILD_NONE) { created.push_back(i); created_first.push_back(created_first.back() + edit->primitive_count[i]); }      // below 2^32: each count is inside the index pool, checked against the total next
+        total += edit ? edit->primitive_count[i] : counted[i];
+        if (total > BUILD_MAX_TRIANGLES) return fail(HIPR_ERROR_UNSUPPORTED, "%s: the new list has more than %u triangles, what a leaf reference holds", who, BUILD_MAX_TRIANGLES);
+        first[i + 1] = uint32_t(total);
+    }
+    const size_t n = size_t(total);
+    const uint32_t new_count = uint32_t(total);
+    if (edit) {
+        if (new_count == 0) return fail(HIPR_ERROR_UNSUPPORTED, "%s: the new list yields no triangle", who);
+        if (int st = outputs_fit(new_count)) return st;
+    }
+    if (b.triangles.resize(n * sizeof(HiprTriangle)) | x.flat_class.resize(n) | x.claim.resize(n * 4) | x.first.resize((size_t(list_count) + 1) * 4)) return HIPR_ERROR_OUT_OF_MEMORY;
+    HIP_TRY(hipMemsetAsync(x.claim.ptr, 0, n * 4, stream));
     HIP_TRY(hipMemcpyAsync(x.first.ptr, first.data(), first.size() * 4, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_rebuild_scatter, per_triangle, block, 0, stream, a);
+    a.first = x.first.as<uint32_t>(); a.flat = b.triangles.as<HiprTriangle>(); a.flat_class = x.flat_class.as<uint8_t>(); a.claim = x.claim.as<uint32_t>();
+    if (!edit) hipLaunchKernelGGL(k_rebuild_scatter, per_triangle, block, 0, stream, a);
+    else {
+        const uint32_t created_count = uint32_t(created.size()), created_triangles = created_first.back();
+        if (x.old_to_new.upload(edit->old_to_new.data(), edit->old_to_new.size() * 4, stream) | x.created.upload(created.data(), created.size() * 4, stream) |
+            x.created_first.upload(created_first.data(), created_first.size() * 4, stream) | x.instances.upload(edit->instances.data(), edit->instances.size() * sizeof(HiprInstance), stream))
+            return HIPR_ERROR_OUT_OF_MEMORY;
+        const EditArrays e = {a.resident, a.resident_class, count, instance_count, x.old_to_new.as<uint32_t>(), a.first, list_count, new_count, x.created.as<uint32_t>(), x.created_first.as<uint32_t>(),
+                              created_count, created_triangles, x.instances.as<HiprInstance>(), r.materials.as<HiprMaterial>(), r.indices.as<uint32_t>(), r.geometry.as<HiprVertexGeometry>(),
+                              r.uploaded_vertex_count, r.uploaded_mesh_attributes & HIPR_MESH_TEXCOORDS ? reinterpret_cast<const float*>(r.args.texcoords) : nullptr, r.textures.as<HiprTexture>(), uint32_t(r.uploaded_textures.size()), r.texels.as<uint8_t>(),
+                              a.flat, a.flat_class, a.claim, a.status};
+        hipLaunchKernelGGL(k_edit_scatter, per_triangle, block, 0, stream, e);
+        if (created_triangles) hipLaunchKernelGGL(k_edit_new_triangles, dim3((created_triangles + REBUILD_BLOCK - 1) / REBUILD_BLOCK), block, 0, stream, e);
+        hipLaunchKernelGGL(k_edit_reduce, dim3((new_count + REBUILD_BLOCK - 1) / REBUILD_BLOCK), block, 0, stream, e.flat, e.flat_class, e.claim, e.status, new_count);
+    }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&claim_status, x.status.as<uint32_t>() + REBUILD_STATUS_CLAIM, 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (claim_status) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_rebuild_scene_trees: two resident triangles claim one flatten position (instance, primitive); rebuild on the host");
+    uint32_t flatten_status[REBUILD_STATUS_WORDS] = {};
+    HIP_TRY(hipMemcpyAsync(flatten_status, x.status.ptr, sizeof(flatten_status), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));      // the host's lists are read by now as well
+    if (edit && flatten_status[EDIT_STATUS_INDEX]) return fail(HIPR_ERROR_UNSUPPORTED, "%s: an index triple of a new instance points outside the vertex pool", who);
+    if (edit && flatten_status[REBUILD_STATUS_CLAIM]) return fail(HIPR_ERROR_UNSUPPORTED, "%s: a flatten position (instance, primitive) is claimed twice or not at all; rebuild on the host", who);
+    if (flatten_status[REBUILD_STATUS_CLAIM]) return fail(HIPR_ERROR_UNSUPPORTED, "%s: two resident triangles claim one flatten position (instance, primitive); rebuild on the host", who);
     const auto t1 = std::chrono::steady_clock::now();
 
     // the BVH2 over the flat array
     Bvh2Built built;
     std::chrono::steady_clock::time_point unused;
-    if (int st = build_bvh2_on_the_device(c, "hipr_rebuild_scene_trees", nullptr, b.triangles.as<HiprTriangle>(), count, depth_limit, built, unused)) return st;
+    if (int st = build_bvh2_on_the_device(c, who, nullptr, b.triangles.as<HiprTriangle>(), new_count, depth_limit, built, unused)) return st;
     uint32_t build_status[STATUS_LEVELS] = {};
     HIP_TRY(hipMemcpyAsync(build_status, b.status.ptr, STATUS_LEVELS * 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     const uint32_t node_count = built.node_count, deepest = build_status[STATUS_DEEPEST];
     const uint32_t bvh_levels = std::max<uint32_t>(uint32_t(built.level_nodes.size()), 1u);
     if (bvh_levels > W8_MAX_LEVELS || deepest + 1u > 64u)
-        return fail(HIPR_ERROR_UNSUPPORTED, "hipr_rebuild_scene_trees: the new BVH2 has %u levels of nodes and its deepest leaf at %u, the kernels walk 64", bvh_levels, deepest);
+        return fail(HIPR_ERROR_UNSUPPORTED, "%s: the new BVH2 has %u levels of nodes and its deepest leaf at %u, the kernels walk 64", who, bvh_levels, deepest);
+    // a fresh upload of so small a scene would choose another search (ResidentScene::choose_variant) and build other arrays: the host path serves it
+    if (edit && node_count <= 64u) return fail(HIPR_ERROR_UNSUPPORTED, "%s: the new BVH2 has %u nodes, the 8-wide search serves more than 64; rebuild on the host and call hipr_upload_scene", who, node_count);
     const auto t2 = std::chrono::steady_clock::now();
 
     // the hand-over and the collapse
@@ -2148,22 +2232,25 @@ int hipr_rebuild_scene_trees(HiprContext* c, uint32_t max_depth, HiprBvhNode* ou
     else for (uint32_t l = 0; l < bvh_levels; ++l) level_first[l + 1] = level_first[l] + built.level_nodes[l];
     W8State S = {};
     S.nodes = b.out_nodes.as<HiprBvhNode>(); S.node_count = node_count;
-    S.triangles = b.triangles.as<HiprTriangle>(); S.order = b.order.as<uint32_t>(); S.triangle_count = count;
+    S.triangles = b.triangles.as<HiprTriangle>(); S.order = b.order.as<uint32_t>(); S.triangle_count = new_count;
     S.level_nodes = x.level_nodes.as<uint32_t>(); S.reachable = node_count; S.single_leaf = built.level_nodes.empty() ? 1u : 0u;
     S.counts = w.counts.as<uint32_t>(); S.block_sums = w.block_sums.as<uint32_t>(); S.status = w.status.as<uint32_t>();
     HiprWide8BuildResult wide8 = {};
-    if (int st = collapse_on_the_device(c, "hipr_rebuild_scene_trees", S, level_first, 0xFFFFFFFFu, wide8)) return st == HIPR_ERROR_INVALID_ARGUMENT ? HIPR_ERROR_UNSUPPORTED : st;
-    if (wide8.height > 33u) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_rebuild_scene_trees: the new 8-wide tree is %u levels high, the kernels' stacks hold 33; rebuild on the host", wide8.height);
-    if ((out_nodes && node_count > node_capacity) || (out_slots && wide8.slot_count > slot_capacity)) return fail(HIPR_ERROR_HIP, "hipr_rebuild_scene_trees: %u nodes and %u slots built, more than the bounds checked", node_count, wide8.slot_count);
+    if (int st = collapse_on_the_device(c, who, S, level_first, 0xFFFFFFFFu, wide8)) return st == HIPR_ERROR_INVALID_ARGUMENT ? HIPR_ERROR_UNSUPPORTED : st;
+    if (wide8.height > 33u) return fail(HIPR_ERROR_UNSUPPORTED, "%s: the new 8-wide tree is %u levels high, the kernels' stacks hold 33; rebuild on the host", who, wide8.height);
+    if ((out_nodes && node_count > node_capacity) || (out_slots && wide8.slot_count > slot_capacity)) return fail(HIPR_ERROR_HIP, "%s: %u nodes and %u slots built, more than the bounds checked", who, node_count, wide8.slot_count);
     std::vector<HiprSlot8> host_slots(wide8.slot_count);      // the refit's lists are made from the host's copy, as at upload
     HIP_TRY(hipMemcpyAsync(host_slots.data(), S.slots, host_slots.size() * sizeof(HiprSlot8), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     const auto t3 = std::chrono::steady_clock::now();
 
     // nothing refuses from here on: the new resident arrays
+    const ResidentScene::RebuiltTrees::NewSet new_set = {new_count, x.instances.as<HiprInstance>(), edit ? &edit->instances : nullptr, flatten_status[EDIT_STATUS_NOT_OPAQUE] == 0,
+                                                         flatten_status[EDIT_STATUS_COATED] != 0};
     const ResidentScene::RebuiltTrees trees = {b.triangles.as<HiprTriangle>(), x.flat_class.as<uint8_t>(), b.order.as<uint32_t>(), b.out_nodes.as<HiprBvhNode>(), node_count, deepest,
-                                               S.slots, host_slots.data(), wide8};
+                                               S.slots, host_slots.data(), wide8, edit ? &new_set : nullptr};
     if (int st = r.install_rebuilt_trees(trees, stream)) return st;
+    if (edit) edit->triangle_count = new_count;
     const auto t4 = std::chrono::steady_clock::now();
     if (out_nodes) HIP_TRY(hipMemcpyAsync(out_nodes, b.out_nodes.ptr, size_t(node_count) * sizeof(HiprBvhNode), hipMemcpyDeviceToHost, stream));
     if (out_order) HIP_TRY(hipMemcpyAsync(out_order, b.order.ptr, n * 4, hipMemcpyDeviceToHost, stream));
@@ -2174,8 +2261,71 @@ int hipr_rebuild_scene_trees(HiprContext* c, uint32_t max_depth, HiprBvhNode* ou
     auto ms = [](std::chrono::steady_clock::time_point from, std::chrono::steady_clock::time_point to) { return std::chrono::duration<double, std::milli>(to - from).count(); };
     x.flatten_ms = ms(t0, t1); x.bvh2_ms = ms(t1, t2); x.collapse_ms = ms(t2, t3); x.install_ms = ms(t3, t4); x.readback_ms = ms(t4, t5);
     if (std::getenv("HIPR_BVH_TIMING"))
-        fprintf(stderr, "[hipr] hipr_rebuild_scene_trees: %u triangles, %u nodes, %u slots: flatten order %.3f ms, BVH2 %.3f ms, collapse + slots to the host %.3f ms, new resident arrays %.3f ms, read-back %.3f ms\n", count, node_count,
+        fprintf(stderr, "[hipr] %s: %u triangles, %u nodes, %u slots: flatten order %.3f ms, BVH2 %.3f ms, collapse + slots to the host %.3f ms, new resident arrays %.3f ms, read-back %.3f ms\n", who, new_count, node_count,
                 wide8.slot_count, x.flatten_ms, x.bvh2_ms, x.collapse_ms, x.install_ms, x.readback_ms);
+    return HIPR_OK;
+}
+
+int hipr_rebuild_scene_trees(HiprContext* c, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_order, HiprSlot8* out_slots, uint32_t slot_capacity,
+                             HiprSceneRebuildResult* out) {
+    return rebuild_trees_on_the_device(c, "hipr_rebuild_scene_trees", nullptr, max_depth, out_nodes, node_capacity, out_order, out_slots, slot_capacity, out);
+}
+
+// Every refusal of hipr_edit_scene_instances that looks at the list and the host's books alone, and the new list with its tables on the way: no HIP call.
+static int check_instance_edit(const ResidentScene& r, const HiprInstanceEdit* edits, uint32_t edit_count, InstanceEdit& plan) {
+    const char* who = "hipr_edit_scene_instances";
+    if (!edits) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null list", who);
+    const uint32_t resident = uint32_t(r.uploaded_instances.size()), primitive_total = r.uploaded_index_count / 3;
+    plan.instances.resize(edit_count);
+    plan.source.assign(edit_count, BUILD_NONE);
+    plan.primitive_count.assign(edit_count, 0u);
+    plan.old_to_new.assign(resident, BUILD_NONE);
+    for (uint32_t i = 0; i < edit_count; ++i) {
+        const HiprInstanceEdit& e = edits[i];
+        if (e.source != HIPR_EDIT_NEW_INSTANCE) {
+            if (e.source >= resident) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: entry %u keeps instance %u of %u", who, i, e.source, resident);
+            if (plan.old_to_new[e.source] != BUILD_NONE) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: entry %u names instance %u, which entry %u keeps already", who, i, e.source, plan.old_to_new[e.source]);
+            plan.old_to_new[e.source] = i;
+            plan.source[i] = e.source;
+            plan.instances[i] = r.uploaded_instances[e.source];
+            continue;
+        }
+        const HiprInstance& inst = e.instance;
+        if (inst.index_offset > primitive_total || e.primitive_count > primitive_total - inst.index_offset || inst.vertex_offset > r.uploaded_vertex_count)
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: entry %u (index offset %u, %u primitives, vertex offset %u) lies outside the uploaded pools of %u triples and %u vertices", who, i, inst.index_offset,
+                        e.primitive_count, inst.vertex_offset, primitive_total, r.uploaded_vertex_count);
+        if (inst.material_index < 0 || size_t(inst.material_index) >= r.uploaded_materials.size())
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: entry %u references material %d of %zu", who, i, inst.material_index, r.uploaded_materials.size());
+        char invalid[256];
+        if (invalid_material(r.uploaded_materials[size_t(inst.material_index)], uint32_t(inst.material_index), uint32_t(r.uploaded_textures.size()), invalid, sizeof(invalid)))
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: entry %u: %s", who, i, invalid);
+        if (inst.mesh_flags & (HIPR_MESH_TEXCOORDS | HIPR_MESH_TINTS | HIPR_MESH_EMISSIVE) & ~r.uploaded_mesh_attributes)
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: entry %u flags an attribute whose pool was not uploaded", who, i);
+        for (int k = 0; k < 12; ++k)
+            if (!std::isfinite(inst.object_to_world[k])) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: the matrix of entry %u is not finite", who, i);
+        plan.instances[i] = inst;
+        plan.primitive_count[i] = e.primitive_count;
+    }
+    return HIPR_OK;
+}
+
+// Models added and removed on the device (instance_edit.h): the list checked on the host, then the rebuild's core over the new list.
+int hipr_edit_scene_instances(HiprContext* c, const HiprInstanceEdit* edits, uint32_t edit_count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_order,
+                              uint32_t order_capacity, HiprSlot8* out_slots, uint32_t slot_capacity, HiprSceneEditResult* out) {
+    const char* who = "hipr_edit_scene_instances";
+    if (int st = check_context(c)) return st;
+    const ResidentScene& r = c->scene;
+    if (!r.ready && !r.awaits_rebuild) return fail(HIPR_ERROR_NOT_READY, "%s: no scene uploaded, or one a failed call left behind", who);
+    if (!out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null result", who);
+    InstanceEdit plan;
+    plan.order_capacity = order_capacity;
+    if (int st = check_instance_edit(r, edits, edit_count, plan)) return st;
+    if (edit_count == 0) return fail(HIPR_ERROR_UNSUPPORTED, "%s: an empty list; a scene without models is the host path's", who);
+    HiprSceneRebuildResult trees = {};
+    if (int st = rebuild_trees_on_the_device(c, who, &plan, max_depth, out_nodes, node_capacity, out_order, out_slots, slot_capacity, &trees)) return st;
+    *out = {};
+    out->triangle_count = plan.triangle_count; out->instance_count = edit_count;
+    out->node_count = trees.node_count; out->deepest = trees.deepest; out->wide8 = trees.wide8; out->half_area = trees.half_area;
     return HIPR_OK;
 }
 

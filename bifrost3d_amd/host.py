@@ -35,6 +35,12 @@ def load_host_library() -> C.CDLL:
     lib.hiprh_scene_order.argtypes = [vp, C.POINTER(C.c_uint)]
     lib.hiprh_scene_order.restype = C.POINTER(C.c_uint)
     lib.hiprh_scene_rebuild_counts.argtypes = [vp, C.POINTER(C.c_uint)]
+    lib.hiprh_scene_remove_model.argtypes = [vp, C.c_uint]
+    lib.hiprh_scene_insert_model.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_uint]
+    lib.hiprh_scene_insert_model.restype = C.c_uint
+    lib.hiprh_scene_model_info.argtypes = [vp, C.c_uint, C.POINTER(C.c_uint)]
+    lib.hiprh_scene_staged_edits.argtypes = [vp, C.POINTER(capi.HiprInstanceEdit), C.c_uint]
+    lib.hiprh_scene_adopt_edited_trees.argtypes = [vp, vp, C.c_uint, vp, C.c_uint, C.c_uint, vp, C.POINTER(capi.HiprWide8BuildResult)]
     lib.hiprh_scene_materials.argtypes = [vp, C.POINTER(C.c_uint)]
     lib.hiprh_scene_materials.restype = C.POINTER(capi.HiprMaterial)
     lib.hiprh_scene_instances.argtypes = [vp, C.POINTER(C.c_uint)]
@@ -229,6 +235,56 @@ class Scene:
         status = self.lib.hiprh_scene_adopt_trees(self.handle, C.c_void_p(nodes.ctypes.data), len(nodes), order_pointer, int(deepest), C.c_void_p(slots.ctypes.data), C.byref(wide8))
         if status < 0:
             raise capi.HiprError("hiprh_scene_adopt_trees failed")
+        return status == 1
+
+    def remove_model(self, model_index: int) -> bool:
+        """SceneBuilder::remove_model: the model leaves the instance list; `desc` must not be read until rebuild() or adopt_edited_trees() has caught up. False when
+        the scene has no such model."""
+        status = self.lib.hiprh_scene_remove_model(self.handle, model_index)
+        if status < 0:
+            raise capi.HiprError("hiprh_scene_remove_model failed")
+        return status == 1
+
+    def insert_model(self, position: int, mesh: int, material: int, translation, rotation=(0.0, 0.0, 0.0, 1.0), scale: float = 1.0, model_index: int = 0) -> int:
+        """SceneBuilder::insert_model: a model of a mesh and a material the scene holds at `position` of the instance list (past the end: appended). Returns the model
+        index used; `desc` must not be read until rebuild() or adopt_edited_trees() has caught up."""
+        used = self.lib.hiprh_scene_insert_model(self.handle, position, mesh, material, (C.c_float * 3)(*translation), (C.c_float * 4)(*rotation), scale, model_index)
+        if used == 0:
+            raise capi.HiprError("hiprh_scene_insert_model failed")
+        return int(used)
+
+    def model_info(self, model_index: int) -> dict:
+        """The mesh, the material and the place in the instance list of a model's first instance."""
+        out = (C.c_uint * 3)()
+        if self.lib.hiprh_scene_model_info(self.handle, model_index, out) != 1:
+            raise capi.HiprError(f"the scene has no model {model_index}")
+        return dict(mesh=int(out[0]), material=int(out[1]), position=int(out[2]))
+
+    def staged_instance_edits(self):
+        """SceneBuilder::staged_instance_edits: the ctypes array of capi.HiprInstanceEdit Context.edit_scene_instances takes for the edits since the last build, or None
+        when they are not the device's to apply (a pool has grown, a transform is staged as well)."""
+        count = self.lib.hiprh_scene_staged_edits(self.handle, None, 0)
+        if count == -2:
+            return None
+        if count < 0:
+            raise capi.HiprError("hiprh_scene_staged_edits failed")
+        edits = (capi.HiprInstanceEdit * count)()
+        self.lib.hiprh_scene_staged_edits(self.handle, edits, count)
+        return edits
+
+    def adopt_edited_trees(self, nodes: np.ndarray, order: np.ndarray, deepest: int, slots: np.ndarray, wide8) -> bool:
+        """SceneBuilder::adopt_edited_trees: the trees Context.edit_scene_instances made of the edited instance list taken over in place of a rebuild; arguments as
+        adopt_trees'. False, with nothing touched, when they do not fit the scene."""
+        nodes = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 16)
+        order = np.ascontiguousarray(order, np.uint32)
+        slots = np.ascontiguousarray(slots, np.uint32).reshape(-1, 16)
+        if isinstance(wide8, dict):
+            wide8 = capi.HiprWide8BuildResult(wide8["slot_count"], wide8["height"], (C.c_float * 3)(*[float(v) for v in wide8["grid_min"]]), (C.c_float * 3)(*[float(v) for v in wide8["grid_cell"]]),
+                                              wide8["node_count"], wide8["leaf_count"], wide8["paired_leaves"])
+        slots_pointer = C.c_void_p(slots.ctypes.data) if wide8.slot_count == len(slots) else None      # a length that does not fit is the library's to refuse
+        status = self.lib.hiprh_scene_adopt_edited_trees(self.handle, C.c_void_p(nodes.ctypes.data), len(nodes), C.c_void_p(order.ctypes.data), len(order), int(deepest), slots_pointer, C.byref(wide8))
+        if status < 0:
+            raise capi.HiprError("hiprh_scene_adopt_edited_trees failed")
         return status == 1
 
     def desc_triangle_count(self) -> int:

@@ -117,7 +117,7 @@ static std::vector<HiprLight> collect_lights() {
     return lights;
 }
 
-void flatten_bifrost_scene(SceneBuilder& sb) {
+void flatten_bifrost_scene(SceneBuilder& sb, std::map<unsigned int, uint32_t>& mesh_index) {
 
     // Textures and materials keep their Bifrost indices (slot 0 = invalid), like the reference's per-ID arrays.
     for (unsigned int t = 1; t < Textures::capacity(); ++t) {
@@ -134,7 +134,7 @@ void flatten_bifrost_scene(SceneBuilder& sb) {
     for (unsigned int m = 1; m < Materials::capacity(); ++m) sb.add_material(material_alive[m] ? upload_material(MaterialID(m)) : HiprMaterial{});
 
     // Meshes are added once and shared by the models that reference them (load_mesh, OR/Renderer.cpp:92-136).
-    std::map<unsigned int, uint32_t> mesh_index;
+    mesh_index.clear();      // kept by the caller: a model created later over one of these meshes is an edit of the resident scene
     for (MeshModelID model_ID : MeshModels::get_iterable()) {
         MeshModel model = model_ID;
         Mesh mesh = model.get_mesh();
@@ -174,6 +174,10 @@ void flatten_bifrost_scene(SceneBuilder& sb) {
     }
     sb.finalize();
 }
+void flatten_bifrost_scene(SceneBuilder& sb) {
+    std::map<unsigned int, uint32_t> mesh_index;
+    flatten_bifrost_scene(sb, mesh_index);
+}
 
 
 struct Renderer::Implementation {
@@ -210,7 +214,8 @@ struct Renderer::Implementation {
     int arithmetic = HIPR_ARITHMETIC_FAST;      // set_arithmetic: applied to every member context of every camera's group
     HiprSceneState scene_state = {{0, 0, 0}, 3};                     // next_event_sample_count = 3, OR/Renderer.cpp:479
     std::unique_ptr<SceneBuilder> scene;
-    Renderer::SceneUpdateCounts scene_updates = {0, 0, 0, 0};
+    std::map<unsigned int, uint32_t> scene_mesh_index;      // Bifrost mesh ID -> the scene builder's mesh
+    Renderer::SceneUpdateCounts scene_updates = {0, 0, 0, 0, 0};
     Renderer::SceneBuildCounts retired_builds = {0, 0};      // of the scene builders that are gone
     Renderer::SceneCollapseCounts retired_collapses = {0, 0};
     Renderer::SceneRebuildCounts scene_rebuilds = {0, 0};
@@ -303,7 +308,7 @@ struct Renderer::Implementation {
             // ... and the 8-wide collapse with it (csrc/wide8_build.h, likewise byte for byte) unless HIPR_DEVICE_COLLAPSE=0 keeps it on the host.
             if (device_collapse_wanted()) scene->set_wide8_source(Wide8Source{build_wide8_on_a_live_group, this});
         }
-        flatten_bifrost_scene(*scene);
+        flatten_bifrost_scene(*scene, scene_mesh_index);
         for (CameraState& c : per_camera_state) c.scene_uploaded = false;
     }
 
@@ -401,6 +406,67 @@ struct Renderer::Implementation {
         return true;
     }
 
+    // HIPR_DEVICE_INSTANCE_EDIT=1: a tick whose only scene dirt is models created over meshes the builder holds and models destroyed edits the resident scenes
+    // (hipr_edit_scene_instances; csrc/instance_edit.h; OR/Renderer.cpp:138-182, :1043-1110 adds or removes a child of the root group) instead of retiring the scene. The
+    // instance list is brought into MeshModels iteration order -- the order flatten_bifrost_scene uses -- the first uploaded camera edits with outputs and the scene
+    // builder adopts them (SceneBuilder::adopt_edited_trees), every other uploaded camera edits without outputs. false: the caller takes the full path, silently --
+    // the variable unset, a camera that is not traced through the 8-wide tree or waits for something, a mesh the builder does not hold, any refusal. The builder may
+    // then hold staged edits: the caller retires it. Off by default, as the rebuild path is (profiles/instance_edit_device_vs_host.txt has the figures).
+    bool edit_instances_on_the_device() {
+        const char* wanted = std::getenv("HIPR_DEVICE_INSTANCE_EDIT");
+        if (!wanted || std::atoi(wanted) == 0 || !scene || scene->has_staged_transforms()) return false;
+        CameraState* first = nullptr;
+        for (CameraState& c : per_camera_state) {
+            if (!c.context || !c.scene_uploaded) continue;      // uploads the description later, with everything in it
+            int variant = -1;
+            if (c.geometry_update_pending || hipr_get_trace_variant(hipr_group_context(c.context, 0), &variant) != HIPR_OK || variant != HIPR_TRACE_WIDE8_PERSISTENT) return false;
+            if (!first) first = &c;
+        }
+        if (!first) return false;
+        const uint32_t triangles_before = scene->desc_triangle_count();
+        for (MeshModelID model_ID : MeshModels::get_changed_models())
+            if (MeshModels::get_changes(model_ID).contains(MeshModels::Change::Destroyed)) scene->remove_model(model_ID.get_index());      // false: created and destroyed since the last tick
+        uint32_t rank = 0;
+        for (MeshModelID model_ID : MeshModels::get_iterable()) {
+            if (MeshModels::get_changes(model_ID).contains(MeshModels::Change::Created)) {
+                MeshModel model = model_ID;
+                const auto mesh = scene_mesh_index.find(model.get_mesh().get_ID());
+                const uint32_t material = model.get_material().get_ID().get_index();
+                if (mesh == scene_mesh_index.end() || material >= scene->materials().size()) return false;      // a pool would grow
+                scene->insert_model(rank, mesh->second, material, model.get_scene_node().get_global_transform(), model_ID.get_index());
+            }
+            ++rank;
+        }
+        const std::vector<HiprInstance>& instances = scene->instances();
+        if (instances.size() != rank) return false;
+        rank = 0;
+        for (MeshModelID model_ID : MeshModels::get_iterable())
+            if (uint32_t(instances[rank++].instance_id) != ((1u << 30) | model_ID.get_index())) return false;      // not the order a flatten would give
+        std::vector<HiprInstanceEdit> edits;
+        if (!scene->staged_instance_edits(edits) || edits.empty()) return false;
+        uint64_t bound = triangles_before;
+        for (const HiprInstanceEdit& e : edits) bound += e.source == HIPR_EDIT_NEW_INSTANCE ? e.primitive_count : 0u;
+        const uint32_t n = uint32_t(std::min<uint64_t>(bound, 0xFFFFFFFFull));
+        const uint32_t node_capacity = std::max(std::max(n, 1u) - 1u, 1u), slot_capacity = uint32_t(std::min<uint64_t>(2ull * n, 0xFFFFFFull));
+        struct Room { void* p; ~Room() { std::free(p); } };
+        Room nodes = {std::malloc(size_t(node_capacity) * sizeof(HiprBvhNode))}, order = {std::malloc(size_t(std::max(n, 1u)) * 4)}, slots = {std::malloc(size_t(std::max(slot_capacity, 1u)) * sizeof(HiprSlot8))};
+        HiprSceneEditResult edited = {};
+        for (CameraState& c : per_camera_state) c.drop_batch();
+        const bool done = nodes.p && order.p && slots.p &&
+                          hipr_group_edit_scene_instances(first->context, edits.data(), uint32_t(edits.size()), scene->bvh_max_depth_limit(), static_cast<HiprBvhNode*>(nodes.p), node_capacity,
+                                                          static_cast<uint32_t*>(order.p), n, static_cast<HiprSlot8*>(slots.p), slot_capacity, &edited) == HIPR_OK;
+        if (!done || !scene->adopt_edited_trees(static_cast<const HiprBvhNode*>(nodes.p), edited.node_count, static_cast<const uint32_t*>(order.p), edited.triangle_count, edited.deepest,
+                                                static_cast<const HiprSlot8*>(slots.p), edited.wide8))
+            return false;
+        for (CameraState& c : per_camera_state) {
+            if (&c == first || !c.context || !c.scene_uploaded) continue;
+            HiprSceneEditResult same = {};
+            if (hipr_group_edit_scene_instances(c.context, edits.data(), uint32_t(edits.size()), scene->bvh_max_depth_limit(), nullptr, 0, nullptr, 0, nullptr, 0, &same) != HIPR_OK) c.scene_uploaded = false;
+        }
+        ++scene_updates.instance_edits;
+        return true;
+    }
+
     // The material-only tick on the device (hipr_update_scene_materials; OR/Renderer.cpp:753-850: the reference rewrites one slot of its material buffer): the
     // scene builder brings its own description along without a rebuild, and every camera with an uploaded scene has the changed slots copied into its resident
     // pools and the arrays derived from materials rewritten by kernels. A camera that waits for its upload takes the whole description later. false: the caller
@@ -422,7 +488,7 @@ struct Renderer::Implementation {
 
     // ---- handle_updates -----------------------------------------------------------------------------------------------
     void handle_updates() {
-        bool should_reset_accumulations = false, scene_dirty = false;
+        bool should_reset_accumulations = false, scene_dirty = false, models_edited = false;
 
         for (CameraID cam_ID : Cameras::get_changed_cameras()) {   // OR/Renderer.cpp:581-619
             auto changes = Cameras::get_changes(cam_ID);
@@ -478,7 +544,10 @@ struct Renderer::Implementation {
         for (SceneNodeID node_ID : SceneNodes::get_changed_nodes()) {
             if (!SceneNodes::get_changes(node_ID).contains(SceneNodes::Change::Transform)) continue;
             for (MeshModelID m : MeshModels::get_iterable())
-                if (MeshModels::get_scene_node_ID(m) == node_ID) { moved_models.emplace_back(m.get_index(), SceneNodes::get_global_transform(node_ID)); should_reset_accumulations = true; }
+                if (MeshModels::get_scene_node_ID(m) == node_ID && !MeshModels::get_changes(m).contains(MeshModels::Change::Created)) {      // a created model brings its transform along
+                    moved_models.emplace_back(m.get_index(), SceneNodes::get_global_transform(node_ID));
+                    should_reset_accumulations = true;
+                }
             for (LightSourceID l : LightSources::get_iterable())
                 if (LightSources::get_node_ID(l) == node_ID) { lights_moved = true; should_reset_accumulations = true; }
         }
@@ -491,7 +560,8 @@ struct Renderer::Implementation {
                 for (size_t i = 0; i < instances.size(); ++i)
                     if (uint32_t(instances[i].instance_id) == ((1u << 30) | model_ID.get_index()))
                         material_assignments.push_back({uint32_t(i), int32_t(MeshModel(model_ID).get_material().get_ID().get_index())});
-            } else scene_dirty = true;
+            } else if (scene) models_edited = true;      // created or destroyed: an edit of the resident scene where that is the tick's only dirt, else a new scene
+            else scene_dirty = true;
         }
 
         for (SceneRootID scene_ID : SceneRoots::get_changed_scenes()) {   // :1112-1200
@@ -515,8 +585,12 @@ struct Renderer::Implementation {
         // Material edits are applied to the resident scene when they are the tick's only dirt; with anything else in the tick, or when the device path declines,
         // they make a new scene as they always did.
         if (materials_dirty) scene_dirty = true;
+        // Created and destroyed models likewise: with any other dirt in the tick they make a new scene.
+        if (models_edited && (!moved_models.empty() || lights_moved || !changed_materials.empty() || !material_assignments.empty())) scene_dirty = true;
         if (!changed_materials.empty() || !material_assignments.empty())
             if (scene_dirty || !scene || !moved_models.empty() || lights_moved || !update_materials_on_the_device(changed_materials, material_assignments)) scene_dirty = true;
+
+        if (models_edited && (scene_dirty || !edit_instances_on_the_device())) scene_dirty = true;
 
         if (!scene_dirty && scene && (!moved_models.empty() || lights_moved)) {
             // transform-only tick: refit in place; a tree the motion has stretched too far is rebuilt by the scene builder itself

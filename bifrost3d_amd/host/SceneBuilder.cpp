@@ -96,11 +96,13 @@ uint32_t SceneBuilder::add_mesh(MeshData mesh) {
     m_any_tints |= (r.flags & HIPR_MESH_TINTS) != 0;
     m_any_emission |= (r.flags & HIPR_MESH_EMISSIVE) != 0;
     m_meshes.push_back(r);
+    m_pools_grew = true;
     return uint32_t(m_meshes.size() - 1);
 }
 
 uint32_t SceneBuilder::add_material(const HiprMaterial& material) {
     m_materials.push_back(material);
+    m_pools_grew = true;
     return uint32_t(m_materials.size() - 1);
 }
 
@@ -115,6 +117,7 @@ uint32_t SceneBuilder::add_texture(const ImageData& image, bool repeat_u, bool r
     t.is_sRGB = image.is_sRGB;
     m_texels.insert(m_texels.end(), image.pixels.begin(), image.pixels.end());
     m_textures.push_back(t);
+    m_pools_grew = true;
     return uint32_t(m_textures.size() - 1);
 }
 
@@ -129,6 +132,7 @@ uint32_t SceneBuilder::index_offset_for(uint32_t mesh, const float* object_to_wo
     if (!mirrors(object_to_world)) return r.index_offset;
     if (r.mirrored_index_offset == 0xFFFFFFFFu) {
         r.mirrored_index_offset = uint32_t(m_indices.size() / 3);
+        m_pools_grew = true;
         for (uint32_t p = 0; p < r.primitive_count; ++p) {
             const size_t at = 3 * size_t(r.index_offset + p);
             const uint32_t a = m_indices[at], b = m_indices[at + 1], c = m_indices[at + 2];
@@ -139,6 +143,49 @@ uint32_t SceneBuilder::index_offset_for(uint32_t mesh, const float* object_to_wo
 }
 
 uint32_t SceneBuilder::add_model(uint32_t mesh, uint32_t material, const Transform& transform, uint32_t explicit_model_index) {
+    return insert_model(uint32_t(m_instances.size()), mesh, material, transform, explicit_model_index);
+}
+
+// An edit of the instance list of a built scene leaves the triangles and the trees behind, as a staged transform does.
+void SceneBuilder::note_instance_edit() {
+    if (!m_built) return;
+    m_staged = true;
+    // a move staged before the edit is marked by the old list's indices: from here on only a rebuild sorts it out, which is what m_staged_flips asks for
+    m_staged_flips = m_staged_flips || std::find(m_staged_moved.begin(), m_staged_moved.end(), true) != m_staged_moved.end();
+    m_staged_moved.assign(m_instances.size(), false);
+}
+
+bool SceneBuilder::has_staged_edits() const {
+    if (!m_built) return false;
+    if (m_built_index.size() != m_built_instance_count) return true;
+    for (size_t i = 0; i < m_built_index.size(); ++i)
+        if (m_built_index[i] != i) return true;
+    return false;
+}
+
+bool SceneBuilder::remove_model(uint32_t model_index) {
+    bool found = false;
+    for (size_t i = m_instances.size(); i-- > 0;)
+        if (uint32_t(m_instances[i].instance_id) == ((1u << 30) | model_index)) {
+            m_instances.erase(m_instances.begin() + ptrdiff_t(i));
+            m_instance_mesh.erase(m_instance_mesh.begin() + ptrdiff_t(i));
+            m_built_index.erase(m_built_index.begin() + ptrdiff_t(i));
+            found = true;
+        }
+    if (found) note_instance_edit();
+    return found;
+}
+
+bool SceneBuilder::model_info(uint32_t model_index, uint32_t& mesh, uint32_t& material, uint32_t& position) const {
+    for (size_t i = 0; i < m_instances.size(); ++i)
+        if (uint32_t(m_instances[i].instance_id) == ((1u << 30) | model_index)) {
+            mesh = m_instance_mesh[i]; material = uint32_t(m_instances[i].material_index); position = uint32_t(i);
+            return true;
+        }
+    return false;
+}
+
+uint32_t SceneBuilder::insert_model(uint32_t position, uint32_t mesh, uint32_t material, const Transform& transform, uint32_t explicit_model_index) {
     // create_model + transformable_model, OptiXRenderer/Renderer.cpp:138-182
     const MeshRecord& r = m_meshes[mesh];
     HiprInstance inst = {};
@@ -151,8 +198,11 @@ uint32_t SceneBuilder::add_model(uint32_t mesh, uint32_t material, const Transfo
     inst.instance_id = int32_t((1u << 30) | model_index);                 // InstanceID::make(MeshModel, index)
     inst.material_index = int32_t(material);
     inst.mesh_flags = mesh_flags;
-    m_instances.push_back(inst);
-    m_instance_mesh.push_back(mesh);
+    const size_t at = std::min<size_t>(position, m_instances.size());
+    m_instances.insert(m_instances.begin() + ptrdiff_t(at), inst);
+    m_instance_mesh.insert(m_instance_mesh.begin() + ptrdiff_t(at), mesh);
+    m_built_index.insert(m_built_index.begin() + ptrdiff_t(at), NOT_BUILT);
+    note_instance_edit();
     return model_index;
 }
 
@@ -174,31 +224,34 @@ void SceneBuilder::force_shading_model(uint16_t shading_model) {
     for (size_t i = 1; i < m_materials.size(); ++i) m_materials[i].shading_model = shading_model;
 }
 
+// The world-space triangles of one instance, primitives in order, appended to `world`; m_bounds grows with them.
+void SceneBuilder::flatten_instance(uint32_t i, std::vector<HiprTriangle>& world) {
+    const HiprInstance& inst = m_instances[i];
+    const MeshRecord& mesh = m_meshes[m_instance_mesh[i]];
+    const float* M = inst.object_to_world;
+    const HiprMaterial& material = m_materials[inst.material_index];
+    auto to_world = [&](uint32_t v, float* out) {
+        const float* p = m_geometry[mesh.vertex_offset + v].position;
+        for (int r = 0; r < 3; ++r) out[r] = M[4 * r] * p[0] + M[4 * r + 1] * p[1] + M[4 * r + 2] * p[2] + M[4 * r + 3];
+        m_bounds.grow_to_contain(Vector3f(out[0], out[1], out[2]));
+    };
+    for (uint32_t p = 0; p < mesh.primitive_count; ++p) {
+        const uint32_t* idx = &m_indices[3 * size_t(inst.index_offset + p)];      // the instance's triples: mirrored instances have their own
+        HiprTriangle t = {};
+        to_world(idx[0], t.v0); to_world(idx[1], t.v1); to_world(idx[2], t.v2);
+        t.instance_index = i;
+        t.primitive_index = p;
+        // covered_everywhere: a triangle of a material that is not statically opaque may still be
+        t.flags = hipr::triangle_flags(material, inst, p, m_indices.data(), m_texcoords.data(), m_textures.data(), uint32_t(m_textures.size()), m_texels.data());
+        world.push_back(t);
+    }
+}
+
 void SceneBuilder::finalize(uint32_t bvh_max_depth) {
     const auto t_start = std::chrono::steady_clock::now();
     std::vector<HiprTriangle> world;
     m_bounds = AABB::invalid();
-    for (uint32_t i = 0; i < m_instances.size(); ++i) {
-        const HiprInstance& inst = m_instances[i];
-        const MeshRecord& mesh = m_meshes[m_instance_mesh[i]];
-        const float* M = inst.object_to_world;
-        const HiprMaterial& material = m_materials[inst.material_index];
-        auto to_world = [&](uint32_t v, float* out) {
-            const float* p = m_geometry[mesh.vertex_offset + v].position;
-            for (int r = 0; r < 3; ++r) out[r] = M[4 * r] * p[0] + M[4 * r + 1] * p[1] + M[4 * r + 2] * p[2] + M[4 * r + 3];
-            m_bounds.grow_to_contain(Vector3f(out[0], out[1], out[2]));
-        };
-        for (uint32_t p = 0; p < mesh.primitive_count; ++p) {
-            const uint32_t* idx = &m_indices[3 * size_t(inst.index_offset + p)];      // the instance's triples: mirrored instances have their own
-            HiprTriangle t = {};
-            to_world(idx[0], t.v0); to_world(idx[1], t.v1); to_world(idx[2], t.v2);
-            t.instance_index = i;
-            t.primitive_index = p;
-            // covered_everywhere: a triangle of a material that is not statically opaque may still be
-            t.flags = hipr::triangle_flags(material, inst, p, m_indices.data(), m_texcoords.data(), m_textures.data(), uint32_t(m_textures.size()), m_texels.data());
-            world.push_back(t);
-        }
-    }
+    for (uint32_t i = 0; i < m_instances.size(); ++i) flatten_instance(i, world);
 
     m_bvh_max_depth_limit = bvh_max_depth;
     const auto t_flat = std::chrono::steady_clock::now();
@@ -219,6 +272,10 @@ void SceneBuilder::build_trees_over(const std::vector<HiprTriangle>& world, cons
     m_built_bvh_area = bvh_child_area(m_bvh);
     m_triangles.resize(world.size());
     for (size_t k = 0; k < world.size(); ++k) m_triangles[k] = world[m_bvh.order[k]];
+    m_built = true; m_pools_grew = false;      // the triangles and the trees are those of the instance list and the pools as they stand
+    m_built_instance_count = uint32_t(m_instances.size());
+    m_built_index.resize(m_instances.size());
+    for (size_t i = 0; i < m_built_index.size(); ++i) m_built_index[i] = uint32_t(i);
 
     HiprSceneDesc& d = m_desc;
     d = {};
@@ -290,6 +347,7 @@ bool SceneBuilder::update_model_transforms(const std::vector<std::pair<uint32_t,
 
 bool SceneBuilder::apply_staged_transforms(double rebuild_threshold) {
     if (!m_staged) return true;
+    if (has_staged_edits()) { rebuild(); return false; }      // another set of triangles: nothing to refit
     const std::vector<bool> moved = m_staged_moved;
     const bool flips = m_staged_flips;
     m_staged = false; m_staged_flips = false;
@@ -352,11 +410,10 @@ int adopted_wide8(void* context, const HiprBvhNode*, uint32_t, const HiprTriangl
 }
 }
 
-bool SceneBuilder::adopt_rebuilt_trees(const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, uint32_t deepest, const HiprSlot8* slots, const HiprWide8BuildResult& wide8) {
-    const uint32_t n = uint32_t(m_triangles.size());
-    auto refuse = [&] { ++m_rebuild_counts.refused; return false; };
-    // counts that do not fit; an instance turned inside out is drawn from other index triples, which changes the set of triangles
-    if (!nodes || !order || !slots || n == 0 || m_bvh.order.size() != n || m_staged_flips) return refuse();
+// What both adoptions ask of trees over `n` triangles before they touch anything: counts that fit, an `order` that is a permutation, child and leaf references in range.
+bool SceneBuilder::trees_fit(uint32_t n, const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, const HiprSlot8* slots, const HiprWide8BuildResult& wide8) const {
+    auto refuse = [] { return false; };
+    if (!nodes || !order || !slots || n == 0) return refuse();
     if (node_count == 0 || node_count > std::max(n, 2u) - 1u || wide8.slot_count == 0 || wide8.slot_count > std::min<uint64_t>(2ull * n, 0xFFFFFFull)) return refuse();
     std::vector<bool> seen(n, false);
     for (uint32_t k = 0; k < n; ++k) {      // a permutation
@@ -383,6 +440,14 @@ bool SceneBuilder::adopt_rebuilt_trees(const HiprBvhNode* nodes, uint32_t node_c
             }
         }
     }
+    return true;
+}
+
+bool SceneBuilder::adopt_rebuilt_trees(const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, uint32_t deepest, const HiprSlot8* slots, const HiprWide8BuildResult& wide8) {
+    const uint32_t n = uint32_t(m_triangles.size());
+    auto refuse = [&] { ++m_rebuild_counts.refused; return false; };
+    // counts that do not fit; an instance turned inside out is drawn from other index triples, which changes the set of triangles -- and so does an edited instance list
+    if (m_bvh.order.size() != n || m_staged_flips || has_staged_edits() || !trees_fit(n, nodes, node_count, order, slots, wide8)) return refuse();
     // everything staged reaches the builder's own triangles, without a refit of trees that are about to be replaced and without a flatten
     const std::vector<bool> moved = m_staged_moved.size() == m_instances.size() ? m_staged_moved : std::vector<bool>(m_instances.size(), false);
     m_staged = false;
@@ -400,6 +465,69 @@ bool SceneBuilder::adopt_rebuilt_trees(const HiprBvhNode* nodes, uint32_t node_c
     Bvh2SourceReport report;
     Wide8SourceReport wide8_report;
     build_trees_over(world, Bvh2Source{adopted_bvh2, &adopted}, report, Wide8Source{adopted_wide8, &adopted}, wide8_report);      // a host configured away from the default trees builds its own, as rebuild() would
+    ++m_rebuild_counts.adopted;
+    return true;
+}
+
+bool SceneBuilder::staged_instance_edits(std::vector<HiprInstanceEdit>& edits) const {
+    edits.clear();
+    if (!m_built || m_pools_grew || m_staged_flips || std::find(m_staged_moved.begin(), m_staged_moved.end(), true) != m_staged_moved.end()) return false;
+    edits.resize(m_instances.size());
+    for (size_t i = 0; i < m_instances.size(); ++i) {
+        HiprInstanceEdit& e = edits[i];
+        e = {};
+        e.source = m_built_index[i] == NOT_BUILT ? HIPR_EDIT_NEW_INSTANCE : m_built_index[i];
+        if (m_built_index[i] == NOT_BUILT) { e.instance = m_instances[i]; e.primitive_count = m_meshes[m_instance_mesh[i]].primitive_count; }
+    }
+    return true;
+}
+
+bool SceneBuilder::adopt_edited_trees(const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, uint32_t order_count, uint32_t deepest, const HiprSlot8* slots, const HiprWide8BuildResult& wide8) {
+    auto refuse = [&] { ++m_rebuild_counts.refused; return false; };
+    std::vector<HiprInstanceEdit> unused;
+    if (!staged_instance_edits(unused) || m_bvh.order.size() != m_triangles.size()) return refuse();      // what the device could not have been given
+    // first[] of the list as it stands, and where the built list's instances went
+    std::vector<uint32_t> first(m_instances.size() + 1, 0u), new_index(m_built_instance_count, NOT_BUILT);
+    uint64_t total = 0;
+    for (size_t i = 0; i < m_instances.size(); ++i) {
+        total += m_meshes[m_instance_mesh[i]].primitive_count;
+        first[i + 1] = uint32_t(total);
+        if (m_built_index[i] != NOT_BUILT) new_index[m_built_index[i]] = uint32_t(i);
+    }
+    if (total == 0 || total > 0xFFFFFFFFull || order_count != total || !trees_fit(uint32_t(total), nodes, node_count, order, slots, wide8)) return refuse();
+    const uint32_t n = uint32_t(total);
+    std::vector<HiprTriangle> world(n);
+    std::vector<bool> placed(n, false);
+    for (const HiprTriangle& t : m_triangles) {      // kept triangles to their place in the new flatten order; removed ranges are dropped
+        const uint32_t to = t.instance_index < new_index.size() ? new_index[t.instance_index] : NOT_BUILT;
+        if (to == NOT_BUILT) continue;
+        if (t.primitive_index >= first[to + 1] - first[to] || placed[first[to] + t.primitive_index]) return refuse();
+        HiprTriangle& w = world[first[to] + t.primitive_index];
+        w = t;
+        w.instance_index = to;
+        placed[first[to] + t.primitive_index] = true;
+    }
+    const AABB bounds_before = m_bounds;
+    std::vector<HiprTriangle> created;
+    for (size_t i = 0; i < m_instances.size(); ++i) {      // only the new instances are flattened
+        if (m_built_index[i] != NOT_BUILT) continue;
+        created.clear();
+        flatten_instance(uint32_t(i), created);
+        for (size_t p = 0; p < created.size(); ++p) { world[first[i] + p] = created[p]; placed[first[i] + p] = true; }
+    }
+    if (std::find(placed.begin(), placed.end(), false) != placed.end()) { m_bounds = bounds_before; return refuse(); }
+    m_staged = false; m_staged_flips = false;
+    m_staged_moved.assign(m_instances.size(), false);
+    m_bounds = AABB::invalid();      // grown in the order finalize() grows them in
+    for (const HiprTriangle& t : world) {
+        m_bounds.grow_to_contain(Vector3f(t.v0[0], t.v0[1], t.v0[2]));
+        m_bounds.grow_to_contain(Vector3f(t.v1[0], t.v1[1], t.v1[2]));
+        m_bounds.grow_to_contain(Vector3f(t.v2[0], t.v2[1], t.v2[2]));
+    }
+    AdoptedTrees adopted = {nodes, node_count, order, deepest, slots, wide8};
+    Bvh2SourceReport report;
+    Wide8SourceReport wide8_report;
+    build_trees_over(world, Bvh2Source{adopted_bvh2, &adopted}, report, Wide8Source{adopted_wide8, &adopted}, wide8_report);
     ++m_rebuild_counts.adopted;
     return true;
 }

@@ -106,6 +106,25 @@ public:
     // array and scalar, what rebuild() leaves. Returns false, with nothing touched, for counts that do not fit, an `order` that is no permutation, a child or
     // leaf reference out of range, or a staged transform that turns an instance inside out. rebuild_counts(): calls that adopted, calls that refused.
     bool adopt_rebuilt_trees(const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, uint32_t deepest, const HiprSlot8* slots, const HiprWide8BuildResult& wide8);
+    // Models destroyed and created after finalize() (the reference removes or adds a child of its root group, OR/Renderer.cpp:138-182, :1043-1110). Meshes and pools
+    // are never dropped: desc() keeps every pool and offset. Both touch the instance list only -- like a staged transform they leave the triangles and the trees
+    // behind, and desc() must not be read until rebuild(), apply_staged_transforms() (which rebuilds) or adopt_edited_trees() has caught up.
+    // remove_model: every instance of the model leaves the list; false when the scene has none. insert_model: the new instance stands at `position` of the list
+    // (at the end for a position past it; add_model after finalize() is that append); `model_index` as add_model's.
+    bool remove_model(uint32_t model_index);
+    uint32_t insert_model(uint32_t position, uint32_t mesh, uint32_t material, const Transform& transform, uint32_t model_index = 0);
+    bool has_staged_edits() const;
+    // What hipr_edit_scene_instances takes for the edits since the last build: the new list in order, kept instances named by their index in the list the trees were
+    // built over, new ones with their record and primitive count. False -- "not on the device" -- when nothing is built yet, when a pool has grown since (a new mesh,
+    // material or texture; the mirrored index copy of a mirrored new instance), or when a transform is staged as well: the caller takes the full path.
+    bool staged_instance_edits(std::vector<HiprInstanceEdit>& edits) const;
+    // adopt_rebuilt_trees generalised to an edited instance list (the trees hipr_edit_scene_instances made): the builder's own triangles of kept instances go to their
+    // place in the new list's flatten order with their new instance index, removed ranges are dropped, ONLY the new instances are flattened, and everything goes
+    // through `order` (`order_count` words) into the new trees' order. desc() is then, in every array and scalar, what rebuild() leaves. Refuses as adopt_rebuilt_trees
+    // does, with nothing touched; counted in rebuild_counts().
+    bool adopt_edited_trees(const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, uint32_t order_count, uint32_t deepest, const HiprSlot8* slots, const HiprWide8BuildResult& wide8);
+    // The mesh, the material and the place in the instance list of the (first) instance of a model; false when the scene has none.
+    bool model_info(uint32_t model_index, uint32_t& mesh, uint32_t& material, uint32_t& position) const;
     struct RebuildCounts { unsigned adopted = 0, refused = 0; };
     RebuildCounts rebuild_counts() const { return m_rebuild_counts; }
     uint32_t desc_triangle_count() const { return uint32_t(m_triangles.size()); }      // desc().triangle_count, also while transforms are staged
@@ -138,6 +157,13 @@ private:
     uint32_t index_offset_for(uint32_t mesh, const float* object_to_world);
     void build_trees_over(const std::vector<HiprTriangle>& world, const Bvh2Source& bvh2_source, Bvh2SourceReport& report, const Wide8Source& wide8_source, Wide8SourceReport& wide8_report);
     void move_triangles(const std::vector<bool>& moved);
+    void flatten_instance(uint32_t instance, std::vector<HiprTriangle>& world);
+    bool trees_fit(uint32_t triangle_count, const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, const HiprSlot8* slots, const HiprWide8BuildResult& wide8) const;
+    void note_instance_edit();
+    static constexpr uint32_t NOT_BUILT = 0xFFFFFFFFu;
+    std::vector<uint32_t> m_built_index;      // per instance: its index in the list the triangles and the trees were built over, NOT_BUILT for one created since
+    uint32_t m_built_instance_count = 0;      // the length of that list
+    bool m_built = false, m_pools_grew = false;      // trees exist; a pool has grown since they were built
     RebuildCounts m_rebuild_counts;
     bool record_model_transforms(const std::vector<std::pair<uint32_t, Transform>>& model_transforms, std::vector<HiprInstanceTransform>* moved_instances);
     bool m_staged = false, m_staged_flips = false;      // transforms recorded in m_instances that m_triangles / m_bvh do not carry yet

@@ -380,6 +380,47 @@ const unsigned* hiprh_scene_order(void* scene, unsigned* out_count) {
     *out_count = unsigned(order.size());
     return order.data();
 }
+// SceneBuilder::remove_model: every instance of the model leaves the instance list; the triangles and the trees stay behind (hiprh_scene_desc must not be asked until
+// hiprh_scene_rebuild or hiprh_scene_adopt_edited_trees has caught up). Returns 1, 0 when the scene has no such model, -1 on error.
+int hiprh_scene_remove_model(void* scene, unsigned model_index) {
+    if (!scene) return -1;
+    try { return static_cast<SceneBuilder*>(scene)->remove_model(model_index) ? 1 : 0; }
+    catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_remove_model: %s\n", e.what()); return -1; }
+}
+// SceneBuilder::insert_model: a model of mesh `mesh` and material `material` at `position` of the instance list (past the end: appended), posed as
+// hiprh_scene_move_model poses. Returns the model index used, 0 on bad arguments.
+unsigned hiprh_scene_insert_model(void* scene, unsigned position, unsigned mesh, unsigned material, const float* translation3, const float* rotation4, float scale, unsigned model_index) {
+    if (!scene || !translation3 || !rotation4) return 0;
+    SceneBuilder* sb = static_cast<SceneBuilder*>(scene);
+    if (mesh >= sb->mesh_count() || material >= sb->materials().size()) return 0;
+    const Transform t(Vector3f(translation3[0], translation3[1], translation3[2]), Bifrost::Math::Quaternionf(rotation4[0], rotation4[1], rotation4[2], rotation4[3]), scale);
+    try { return sb->insert_model(position, mesh, material, t, model_index); }
+    catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_insert_model: %s\n", e.what()); return 0; }
+}
+// out[0] = mesh, out[1] = material, out[2] = place in the instance list of the model's first instance. Returns 1, 0 when the scene has no such model.
+int hiprh_scene_model_info(void* scene, unsigned model_index, unsigned* out3) {
+    if (!scene || !out3) return -1;
+    return static_cast<const SceneBuilder*>(scene)->model_info(model_index, out3[0], out3[1], out3[2]) ? 1 : 0;
+}
+// SceneBuilder::staged_instance_edits: the list hipr_edit_scene_instances takes for the edits since the last build, up to `capacity` entries written. Returns the
+// length of the list, -2 when the edits are not the device's to apply (a pool has grown, a transform is staged, nothing is built), -1 on error.
+int hiprh_scene_staged_edits(void* scene, HiprInstanceEdit* out, unsigned capacity) {
+    if (!scene) return -1;
+    try {
+        std::vector<HiprInstanceEdit> edits;
+        if (!static_cast<const SceneBuilder*>(scene)->staged_instance_edits(edits)) return -2;
+        if (out) std::copy(edits.begin(), edits.begin() + std::min<size_t>(capacity, edits.size()), out);
+        return int(edits.size());
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_staged_edits: %s\n", e.what()); return -1; }
+}
+// SceneBuilder::adopt_edited_trees: the trees hipr_edit_scene_instances made taken over in place of a rebuild. Returns 1 when adopted, 0 when refused (nothing
+// touched), -1 on error.
+int hiprh_scene_adopt_edited_trees(void* scene, const HiprBvhNode* nodes, unsigned node_count, const unsigned* order, unsigned order_count, unsigned deepest, const HiprSlot8* slots,
+                                   const HiprWide8BuildResult* wide8) {
+    if (!scene || !wide8) return -1;
+    try { return static_cast<SceneBuilder*>(scene)->adopt_edited_trees(nodes, node_count, order, order_count, deepest, slots, *wide8) ? 1 : 0; }
+    catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_adopt_edited_trees: %s\n", e.what()); return -1; }
+}
 // out[0] = calls of hiprh_scene_adopt_trees that adopted, out[1] = calls that refused.
 int hiprh_scene_rebuild_counts(void* scene, unsigned* out2) {
     if (!scene || !out2) return -1;

@@ -77,6 +77,7 @@ class Context:
         self._scene = scene   # keep the host arrays alive until uploaded (copy happens inside)
         self._rebuilt_counts = None
         self._check(self.lib.hipr_upload_scene(self.handle, C.byref(scene.desc)), "hipr_upload_scene")
+        self._resident_counts = (scene.desc.triangle_count, scene.desc.instance_count, scene.desc.material_count)      # an edit of the instance list changes the first two
         state = scene.state
         self._check(self.lib.hipr_set_scene_state(self.handle, C.byref(state)), "hipr_set_scene_state")
 
@@ -84,6 +85,7 @@ class Context:
         self._scene = scene
         self._rebuilt_counts = None
         self._check(self.lib.hipr_update_scene_geometry(self.handle, C.byref(scene.desc)), "hipr_update_scene_geometry")
+        self._resident_counts = (scene.desc.triangle_count, scene.desc.instance_count, scene.desc.material_count)      # an edit of the instance list changes the first two
 
     def refit_scene_transforms(self, moved=(), lights=None) -> dict:
         """hipr_refit_scene_transforms: `moved` is a sequence of (instance index, 3x4 matrix) -- Scene.model_pose() -- refitted on the device; `lights`: None keeps the
@@ -173,6 +175,40 @@ class Context:
             out.update(nodes=nodes[:result.node_count], order=order, slots=slots[:w.slot_count])
         return out
 
+    def edit_scene_instances(self, edits, max_depth: int = 62, read_back: bool = True, group=None, capacities=None) -> dict:
+        """hipr_edit_scene_instances: models of the resident scene added and removed on the device. `edits` is the NEW instance list in order, a ctypes array of
+        capi.HiprInstanceEdit (Scene.staged_instance_edits makes it) or a sequence of them. Returns a dict of status, triangle_count, instance_count, node_count,
+        deepest, wide8 (as build_wide8's result), half_area and -- `read_back` -- nodes, order and slots (Scene.adopt_edited_trees takes them). On a status other than
+        HIPR_OK the dict holds the status and the arrays whole as the call left them. `capacities`: (nodes, order words, slots) of the read-back arrays, by default
+        what the largest list the pools allow can need. `group`: a HiprGroup handle, for hipr_group_edit_scene_instances."""
+        if edits is not None and not isinstance(edits, C.Array):
+            edits = (capi.HiprInstanceEdit * len(edits))(*edits)
+        count = len(edits) if edits is not None else 0
+        triangles = self._resident_counts[0]      # not the host scene's: its description lags behind while edits are staged
+        bound = triangles + sum(int(e.primitive_count) for e in edits if e.source == capi.EDIT_NEW_INSTANCE) if edits is not None else triangles
+        node_room, order_room, slot_room = capacities or (max(bound - 1, 1), max(bound, 1), max(min(2 * bound, 0xFFFFFF), 1))
+        nodes = np.zeros((node_room, 16), np.uint32) if read_back else None
+        order = np.zeros(order_room, np.uint32) if read_back else None
+        slots = np.zeros((slot_room, 16), np.uint32) if read_back else None
+        result = capi.HiprSceneEditResult()
+        pointer = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        call, handle = (self.lib.hipr_group_edit_scene_instances, group) if group is not None else (self.lib.hipr_edit_scene_instances, self.handle)
+        status = call(handle, edits, count, max_depth, pointer(nodes), len(nodes) if read_back else 0, pointer(order), len(order) if read_back else 0, pointer(slots),
+                      len(slots) if read_back else 0, C.byref(result))
+        if status != capi.HIPR_OK:
+            return dict(status=status, nodes=nodes, order=order, slots=slots)
+        w = result.wide8
+        if group is None:
+            self._rebuilt_counts = (result.node_count, w.slot_count)
+            self._resident_counts = (result.triangle_count, result.instance_count, self._resident_counts[2])
+        out = dict(status=status, triangle_count=result.triangle_count, instance_count=result.instance_count, node_count=result.node_count, deepest=result.deepest,
+                   half_area=float(result.half_area),
+                   wide8=dict(slot_count=w.slot_count, height=w.height, grid_min=np.array(w.grid_min[:], np.float32), grid_cell=np.array(w.grid_cell[:], np.float32), node_count=w.node_count,
+                              leaf_count=w.leaf_count, paired_leaves=w.paired_leaves), raw=result)
+        if read_back:
+            out.update(nodes=nodes[:result.node_count], order=order[:result.triangle_count], slots=slots[:w.slot_count])
+        return out
+
     def rebuild_times(self) -> dict:
         """Milliseconds of the last rebuild_scene_trees: flatten order, BVH2, collapse (with the slots copied to the host), the new resident arrays, the outputs' read-back."""
         out = (C.c_double * 5)()
@@ -188,12 +224,14 @@ class Context:
     def read_scene_buffer(self, which: int) -> np.ndarray:
         """The scene array the device holds (hipr_debug_read_scene_buffer): capi.SCENE_BUFFER_TRIANGLES -> (triangles, 12) uint32 words, SCENE_BUFFER_WIDE8_SLOTS -> (slots, 16),
         _TRACE_TRIANGLES -> (triangles, 12), _SHADE_TRIANGLES -> (triangles, 32), _TRIANGLE_CLASS -> (triangles,) uint8, _MATERIALS -> (materials, 16), _INSTANCES -> (instances, 20), SCENE_BUFFER_NODES -> (BVH2 nodes, 16)."""
-        desc = self._scene.desc
-        node_count, slot_count = getattr(self, "_rebuilt_counts", None) or (desc.node_count, desc.wide8_slot_count)      # a device rebuild changes both
-        shape, dtype = {capi.SCENE_BUFFER_TRIANGLES: ((desc.triangle_count, 12), np.uint32), capi.SCENE_BUFFER_WIDE8_SLOTS: ((slot_count, 16), np.uint32), capi.SCENE_BUFFER_NODES: ((node_count, 16), np.uint32),
-                        capi.SCENE_BUFFER_TRACE_TRIANGLES: ((desc.triangle_count, 12), np.uint32), capi.SCENE_BUFFER_SHADE_TRIANGLES: ((desc.triangle_count, 32), np.uint32),
-                        capi.SCENE_BUFFER_TRIANGLE_CLASS: ((desc.triangle_count,), np.uint8), capi.SCENE_BUFFER_MATERIALS: ((desc.material_count, 16), np.uint32),
-                        capi.SCENE_BUFFER_INSTANCES: ((desc.instance_count, 20), np.uint32)}.get(which, ((0,), np.uint8))
+        # the device's counts, not the host scene's: a device rebuild changes the first two, and the description lags behind while edits or moves are staged in it
+        node_count, slot_count = getattr(self, "_rebuilt_counts", None) or (self._scene.desc.node_count, self._scene.desc.wide8_slot_count)
+        counts = getattr(self, "_resident_counts", None)      # absent on a context whose scene was uploaded past this wrapper: then the description is the device's
+        triangle_count, instance_count, material_count = counts or (self._scene.desc.triangle_count, self._scene.desc.instance_count, self._scene.desc.material_count)
+        shape, dtype = {capi.SCENE_BUFFER_TRIANGLES: ((triangle_count, 12), np.uint32), capi.SCENE_BUFFER_WIDE8_SLOTS: ((slot_count, 16), np.uint32), capi.SCENE_BUFFER_NODES: ((node_count, 16), np.uint32),
+                        capi.SCENE_BUFFER_TRACE_TRIANGLES: ((triangle_count, 12), np.uint32), capi.SCENE_BUFFER_SHADE_TRIANGLES: ((triangle_count, 32), np.uint32),
+                        capi.SCENE_BUFFER_TRIANGLE_CLASS: ((triangle_count,), np.uint8), capi.SCENE_BUFFER_MATERIALS: ((material_count, 16), np.uint32),
+                        capi.SCENE_BUFFER_INSTANCES: ((instance_count, 20), np.uint32)}.get(which, ((0,), np.uint8))
         out = np.zeros(shape, dtype)
         self._check(self.lib.hipr_debug_read_scene_buffer(self.handle, int(which), C.c_void_p(out.ctypes.data), out.nbytes), "hipr_debug_read_scene_buffer")
         return out

@@ -442,6 +442,49 @@ typedef struct HiprSceneRebuildResult {
 } HiprSceneRebuildResult;
 int hipr_rebuild_scene_trees(HiprContext* context, uint32_t max_depth, HiprBvhNode* out_nodes /* may be NULL */, uint32_t node_capacity, uint32_t* out_order /* may be NULL */,
                              HiprSlot8* out_slots /* may be NULL */, uint32_t slot_capacity, HiprSceneRebuildResult* out);
+/* Models of the RESIDENT scene added and removed on the device (the reference leaves geometry where it lives, adds or removes a child of its root group and marks
+ * the acceleration dirty, OR/Renderer.cpp:138-182, :1043-1110): a model destroyed, or created over a mesh whose vertices and index triples the uploaded pools
+ * already hold, changes no pool, so no flatten on the host and no upload is needed. `edits` is the NEW instance list, IN ORDER -- the scene builder flattens
+ * instances in order and both tree builders depend on that order. An entry with `source` < the resident instance count keeps that resident instance, with the
+ * matrix and the material the device holds (`instance` and `primitive_count` are ignored); an entry with `source` == HIPR_EDIT_NEW_INSTANCE brings `instance`, and
+ * `primitive_count`, the triangles of its mesh (an instance does not carry its count). Appending, inserting, removing and any mix of them are this one list.
+ * Kernels bring the kept triangles into the new list's flatten order and make the new instances' triangles there -- corners, flags and class byte by the scene
+ * builder's own expressions over the resident pools (csrc/instance_edit.h) -- then the call goes on as hipr_rebuild_scene_trees does, over the new count, and
+ * installs the new triangle and instance arrays with the trees. Afterwards the device holds, byte for byte, what SceneBuilder::remove_model / insert_model,
+ * rebuild() and hipr_upload_scene on a fresh context put into the triangles, the instances, the BVH2 nodes, the 8-wide slots and everything derived from them;
+ * the 4-wide array is left as hipr_rebuild_scene_trees leaves it. Outputs as hipr_rebuild_scene_trees'; `out_order` receives out->triangle_count words, and
+ * `order_capacity` is the room it has. The call accepts the states hipr_rebuild_scene_trees accepts. Checked on the host before anything is written:
+ *   HIPR_ERROR_NOT_READY          no scene, or a scene a failed call left behind;
+ *   HIPR_ERROR_INVALID_ARGUMENT   a null `edits` or `out`; a `source` that is neither HIPR_EDIT_NEW_INSTANCE nor a resident instance; a resident instance named
+ *                                 twice; a new instance whose (index_offset, primitive_count) or vertex_offset lies outside the uploaded index / vertex pools,
+ *                                 whose material index lies outside the uploaded material pool or names a material hipr_validate_scene would refuse, which
+ *                                 flags an attribute whose pool was not uploaded, or whose matrix is not finite;
+ *   HIPR_ERROR_UNSUPPORTED        the conditions hipr_rebuild_scene_trees refuses on; an empty list.
+ * Checked once the kept instances' triangles are counted (a kernel over the resident triangles that writes scratch only), before anything else runs:
+ *   HIPR_ERROR_UNSUPPORTED        the new list yields no triangle, or more than a leaf reference holds (2^28);
+ *   HIPR_ERROR_INVALID_ARGUMENT   a non-null output with less room than the NEW triangle count t asks for: max(t, 1) - 1 (or 1) nodes, t order words,
+ *                                 min(2 t, 0xFFFFFF) slots.
+ * Found on the device, in scratch, before anything resident is replaced, all HIPR_ERROR_UNSUPPORTED with the reason in hipr_last_error(): an index triple of a
+ * new instance that points outside the vertex pool (the index is checked before the vertex is loaded: it is never read through); a flatten position claimed
+ * twice or not at all; a decline of the BVH2 build; a BVH2 of at most 64 nodes (a fresh upload would choose another search and build other arrays); trees higher
+ * than the kernels walk, or more than 0xFFFFFF slots. Every refusal leaves the resident scene exactly as the call found it -- not ready included -- and the
+ * outputs untouched. A HIP failure once the new arrays are being installed leaves no scene, as with the other writers. */
+#define HIPR_EDIT_NEW_INSTANCE 0xFFFFFFFFu
+typedef struct HiprInstanceEdit {
+    uint32_t source;                     /* a resident instance's index (kept), or HIPR_EDIT_NEW_INSTANCE */
+    uint32_t primitive_count;            /* new instances: the triangles of the mesh */
+    HiprInstance instance;               /* new instances */
+} HiprInstanceEdit;
+typedef struct HiprSceneEditResult {
+    uint32_t triangle_count, instance_count;      /* of the resident scene afterwards */
+    uint32_t node_count, deepest;        /* the BVH2, as hipr_build_bvh2 reports them */
+    HiprWide8BuildResult wide8;          /* as hipr_build_wide8 reports it */
+    uint32_t _pad;
+    double half_area;                    /* child_half_area of the new tree = the scene's new uploaded_half_area */
+} HiprSceneEditResult;
+int hipr_edit_scene_instances(HiprContext* context, const HiprInstanceEdit* edits, uint32_t edit_count, uint32_t max_depth, HiprBvhNode* out_nodes /* may be NULL */,
+                              uint32_t node_capacity, uint32_t* out_order /* may be NULL */, uint32_t order_capacity, HiprSlot8* out_slots /* may be NULL */,
+                              uint32_t slot_capacity, HiprSceneEditResult* out);
 int hipr_set_scene_state(HiprContext* context, const HiprSceneState* state);
 
 /* Entry points, numbered like OR/Types.h:33-44. set_backend() of the host renderer maps Backend values onto them
@@ -529,6 +572,9 @@ int hipr_group_build_wide8(HiprGroup* group, const HiprBvhNode* nodes, uint32_t 
                            HiprSlot8* out_slots, uint32_t slot_capacity, HiprWide8BuildResult* out);   /* collapses on member 0 */
 int hipr_group_rebuild_scene_trees(HiprGroup* group, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_order, HiprSlot8* out_slots,
                                    uint32_t slot_capacity, HiprSceneRebuildResult* out);   /* every member rebuilds; member 0's arrays are handed out; their results must agree */
+int hipr_group_edit_scene_instances(HiprGroup* group, const HiprInstanceEdit* edits, uint32_t edit_count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity,
+                                    uint32_t* out_order, uint32_t order_capacity, HiprSlot8* out_slots, uint32_t slot_capacity,
+                                    HiprSceneEditResult* out);   /* every member edits; member 0's arrays are handed out; their results must agree */
 int hipr_group_update_scene_materials(HiprGroup* group, const HiprMaterialUpdate* materials, uint32_t material_count,
                                       const HiprInstanceMaterial* assignments, uint32_t assignment_count);   /* every member checks before any member writes */
 int hipr_group_set_scene_state(HiprGroup* group, const HiprSceneState* state);
