@@ -140,6 +140,20 @@ class HiprSceneEditResult(C.Structure):
     _fields_ = [("triangle_count", c_u32), ("instance_count", c_u32), ("node_count", c_u32), ("deepest", c_u32), ("wide8", HiprWide8BuildResult), ("_pad", c_u32), ("half_area", C.c_double)]
 
 
+SEGMENT_FROM_HOST = 0xFFFFFFFF
+
+
+class HiprIndexSegment(C.Structure):
+    _fields_ = [("mirrored_from", c_u32), ("index_count", c_u32)]
+
+
+class HiprPoolGrowth(C.Structure):
+    _fields_ = [("geometry", C.POINTER(HiprVertexGeometry)), ("texcoords", C.POINTER(c_f)), ("tints", C.POINTER(c_u32)), ("emissions", C.POINTER(c_f)), ("indices", C.POINTER(c_u32)),
+                ("segments", C.POINTER(HiprIndexSegment)), ("materials", C.POINTER(HiprMaterial)), ("textures", C.POINTER(HiprTexture)), ("texels", C.POINTER(c_u8)), ("texel_bytes", c_u64),
+                ("vertex_count", c_u32), ("texcoord_vertices", c_u32), ("tint_vertices", c_u32), ("emission_vertices", c_u32),
+                ("index_count", c_u32), ("segment_count", c_u32), ("material_count", c_u32), ("texture_count", c_u32)]
+
+
 class HiprRefitResult(C.Structure):
     _fields_ = [("needs_rebuild", c_i32), ("child_half_area", C.c_double), ("uploaded_half_area", C.c_double), ("grid_min", c_f * 3), ("grid_cell", c_f * 3)]
 
@@ -175,6 +189,9 @@ def instance_materials(assignments):
 HIPR_ERROR_INVALID_ARGUMENT, HIPR_ERROR_NOT_READY, HIPR_ERROR_UNSUPPORTED = -1, -5, -6
 SCENE_BUFFER_TRIANGLES, SCENE_BUFFER_WIDE8_SLOTS, SCENE_BUFFER_TRACE_TRIANGLES, SCENE_BUFFER_SHADE_TRIANGLES, SCENE_BUFFER_TRIANGLE_CLASS, SCENE_BUFFER_MATERIALS, SCENE_BUFFER_INSTANCES = 0, 1, 2, 3, 4, 5, 6
 SCENE_BUFFER_NODES = 7      # the BVH2; not among SCENE_BUFFERS, which lists what every writer of the resident scene is held to
+TEXEL_R8, TEXEL_RGBA8, TEXEL_R32F, TEXEL_RGBA32F = 1, 4, 17, 20
+# the pools hipr_append_scene_pools grows; not among SCENE_BUFFERS either: tests of the growth keep a tuple of their own
+SCENE_BUFFER_INDICES, SCENE_BUFFER_GEOMETRY, SCENE_BUFFER_TEXCOORDS, SCENE_BUFFER_TINTS, SCENE_BUFFER_EMISSIONS, SCENE_BUFFER_TEXTURES, SCENE_BUFFER_TEXELS = 8, 9, 10, 11, 12, 13, 14
 SCENE_BUFFERS = (SCENE_BUFFER_TRIANGLES, SCENE_BUFFER_WIDE8_SLOTS, SCENE_BUFFER_TRACE_TRIANGLES, SCENE_BUFFER_SHADE_TRIANGLES, SCENE_BUFFER_TRIANGLE_CLASS, SCENE_BUFFER_MATERIALS, SCENE_BUFFER_INSTANCES)
 TRACE_BVH2, TRACE_WIDE_PERSISTENT, TRACE_EXHAUSTIVE, TRACE_WIDE8_PERSISTENT = 0, 1, 2, 3
 SHADING_DEFAULT, SHADING_DIFFUSE, SHADING_TRANSMISSIVE = 0, 1, 2
@@ -191,11 +208,12 @@ class HiprKernelTimes(C.Structure):
 assert C.sizeof(HiprMaterial) == 64 and C.sizeof(HiprLight) == 48 and C.sizeof(HiprVertexGeometry) == 16
 assert C.sizeof(HiprTexture) == 24 and C.sizeof(HiprCameraState) == 180 and C.sizeof(HiprTriangle) == 48 and C.sizeof(HiprBvhNode) == 64 and C.sizeof(HiprInstance) == 80
 assert C.sizeof(HiprInstanceEdit) == 88 and C.sizeof(HiprSceneEditResult) == 72
+assert C.sizeof(HiprIndexSegment) == 8 and C.sizeof(HiprPoolGrowth) == 112
 
 # Every symbol include/hiprenderer_c.h declares; tests check the library exports all of them.
 C_ABI_SYMBOLS = (
     "hipr_create", "hipr_destroy", "hipr_last_error", "hipr_device_count", "hipr_set_stream",
-    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_build_bvh2", "hipr_group_build_bvh2", "hipr_debug_build_times", "hipr_build_wide8", "hipr_group_build_wide8", "hipr_debug_collapse_times", "hipr_rebuild_scene_trees", "hipr_group_rebuild_scene_trees", "hipr_edit_scene_instances", "hipr_group_edit_scene_instances", "hipr_debug_rebuild_times", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
+    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_build_bvh2", "hipr_group_build_bvh2", "hipr_debug_build_times", "hipr_build_wide8", "hipr_group_build_wide8", "hipr_debug_collapse_times", "hipr_rebuild_scene_trees", "hipr_group_rebuild_scene_trees", "hipr_edit_scene_instances", "hipr_group_edit_scene_instances", "hipr_append_scene_pools", "hipr_group_append_scene_pools", "hipr_debug_scene_buffer_bytes", "hipr_debug_append_times", "hipr_debug_rebuild_times", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
     "hipr_set_frame", "hipr_owned_pixel_count",
     "hipr_render_pass", "hipr_set_samples_per_pass", "hipr_trace_pass", "hipr_accumulate_samples", "hipr_read_accumulation", "hipr_scatter_tiles", "hipr_synchronize", "hipr_get_counters",
     "hipr_device_malloc", "hipr_device_free", "hipr_device_memset", "hipr_copy_to_host", "hipr_present_flipped",
@@ -254,6 +272,10 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.hipr_group_rebuild_scene_trees.argtypes = [vp, c_u32, vp, c_u32, vp, vp, c_u32, C.POINTER(HiprSceneRebuildResult)]
     lib.hipr_edit_scene_instances.argtypes = [vp, C.POINTER(HiprInstanceEdit), c_u32, c_u32, vp, c_u32, vp, c_u32, vp, c_u32, C.POINTER(HiprSceneEditResult)]
     lib.hipr_group_edit_scene_instances.argtypes = [vp, C.POINTER(HiprInstanceEdit), c_u32, c_u32, vp, c_u32, vp, c_u32, vp, c_u32, C.POINTER(HiprSceneEditResult)]
+    lib.hipr_append_scene_pools.argtypes = [vp, C.POINTER(HiprPoolGrowth)]
+    lib.hipr_group_append_scene_pools.argtypes = [vp, C.POINTER(HiprPoolGrowth)]
+    lib.hipr_debug_scene_buffer_bytes.argtypes = [vp, C.c_int, C.POINTER(c_u64)]
+    lib.hipr_debug_append_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.hipr_debug_rebuild_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.hipr_debug_read_scene_buffer.argtypes = [vp, C.c_int, vp, c_u64]
     lib.hipr_set_scene_state.argtypes = [vp, C.POINTER(HiprSceneState)]

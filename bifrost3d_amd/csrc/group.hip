@@ -39,6 +39,7 @@
 
 extern "C" int hipr_internal_check_material_update(HiprContext* context, const HiprMaterialUpdate* materials, uint32_t material_count, const HiprInstanceMaterial* assignments,
                                                    uint32_t assignment_count);   // hiprenderer.hip: the refusals of hipr_update_scene_materials on their own
+extern "C" int hipr_internal_check_pool_growth(HiprContext* context, const HiprPoolGrowth* growth);   // hiprenderer.hip: every refusal of hipr_append_scene_pools short of a failed allocation
 extern "C" void hipr_internal_set_last_error(const char* message);   // hiprenderer.hip: hipr_last_error() is per thread; a worker's message is handed to the caller's
 
 namespace {
@@ -394,6 +395,14 @@ int hipr_group_edit_scene_instances(HiprGroup* g, const HiprInstanceEdit* edits,
         }
     *out = results[0];
     return HIPR_OK;
+}
+
+// hipr_append_scene_pools on every member: every member checks before any member writes, so a description one member refuses leaves all of them as they were.
+int hipr_group_append_scene_pools(HiprGroup* g, const HiprPoolGrowth* growth) {
+    if (!g || g->members.empty()) return HIPR_ERROR_INVALID_ARGUMENT;
+    for (Member& m : g->members)
+        if (int s = hipr_internal_check_pool_growth(m.context, growth)) return s;
+    return for_each_member(g, [&](Member& m, uint32_t) { return hipr_append_scene_pools(m.context, growth); });
 }
 
 int hipr_group_update_scene_materials(HiprGroup* g, const HiprMaterialUpdate* materials, uint32_t material_count, const HiprInstanceMaterial* assignments, uint32_t assignment_count) {

@@ -19,6 +19,7 @@
 #include "wide8_build.h"
 #include "scene_rebuild.h"
 #include "instance_edit.h"
+#include "pool_growth.h"
 #include "launch.h"
 
 #include <hip/hip_runtime.h>
@@ -137,7 +138,7 @@ struct Preflight {
 
 // The scene the device holds: the uploaded pools, what is derived from them, the argument blocks the kernels take and the host's copies of what later calls are
 // checked against. Its writers -- upload() (hipr_upload_scene), update_geometry() (hipr_update_scene_geometry), refit_transforms() (hipr_refit_scene_transforms)
-// and update_materials() (hipr_update_scene_materials) -- are called once every refusal is behind the entry point and every queued pass has finished, and go: ready = false, device work, publish pointers, counts and
+// update_materials() (hipr_update_scene_materials), install_rebuilt_trees() and append_pools() (hipr_append_scene_pools) -- are called once every refusal is behind the entry point and every queued pass has finished, and go: ready = false, device work, publish pointers, counts and
 // flags, ready = true. One that fails on the way leaves a scene that answers HIPR_ERROR_NOT_READY until an upload succeeds, never one that names freed memory.
 struct ResidentScene {
     DeviceBuffer nodes, wide_nodes, wide8_slots, triangles, instances, lights;                                     // what a geometry update brings again
@@ -216,6 +217,10 @@ struct ResidentScene {
         const NewSet* new_set;
     };
     int install_rebuilt_trees(const RebuiltTrees& built, hipStream_t stream);
+    // The device work of hipr_append_scene_pools, which has checked the description against the host copies (hipr_internal_check_pool_growth): the pools grown at their tails.
+    int append_pools(const HiprPoolGrowth& growth, hipStream_t stream);
+    double append_ms[3] = {0.0, 0.0, 0.0};      // of the last append_pools: the allocations (host clock), the device-to-device copies of the resident parts, the tails and the mirror segments (events)
+    Event append_events[3];             // made by the first append_pools
 
 private:
     int upload_pools(const HiprSceneDesc* s, bool all_pools, hipStream_t stream);
@@ -980,24 +985,28 @@ const char* invalid_material(const HiprMaterial& m, uint32_t index, uint32_t tex
     return nullptr;
 }
 
+// What makes ONE texture unusable against a texel pool of `texel_bytes`: an unknown format, an empty extent, texels that do not lie inside the pool or start off
+// their alignment. The check of validate_scene for every texture of a description, and of hipr_append_scene_pools for every texture it brings, against the grown pool.
+const char* invalid_texture(const HiprTexture& t, uint32_t index, uint64_t texel_bytes, char* message, size_t message_size) {
+    const uint64_t size = t.format == HIPR_TEXEL_R8 ? 1u : (t.format == HIPR_TEXEL_RGBA8 ? 4u : (t.format == HIPR_TEXEL_R32F ? 4u : (t.format == HIPR_TEXEL_RGBA32F ? 16u : 0u)));
+    if (size == 0) { snprintf(message, message_size, "texture %u has the unknown texel format %u", index, unsigned(t.format)); return message; }
+    if (t.width == 0 || t.height == 0) { snprintf(message, message_size, "texture %u is %u x %u", index, t.width, t.height); return message; }
+    const uint64_t bytes = uint64_t(t.width) * t.height * size;
+    if (t.texel_offset > texel_bytes || bytes > texel_bytes - t.texel_offset || t.texel_offset % (size == 16 ? 16 : 4) != 0) {
+        snprintf(message, message_size, "texture %u (%u x %u, offset %llu) does not fit the %llu byte texel pool", index, t.width, t.height, (unsigned long long)t.texel_offset, (unsigned long long)texel_bytes);
+        return message;
+    }
+    return nullptr;
+}
+
 const char* validate_scene(const HiprSceneDesc* s, uint32_t& wide_stack_need, char* message, size_t message_size) {
 #define INVALID(...) do { snprintf(message, message_size, __VA_ARGS__); return message; } while (0)
     wide_stack_need = 0;
-    auto texel_size = [](uint8_t format) -> uint64_t {
-        return format == HIPR_TEXEL_R8 ? 1u : (format == HIPR_TEXEL_RGBA8 ? 4u : (format == HIPR_TEXEL_R32F ? 4u : (format == HIPR_TEXEL_RGBA32F ? 16u : 0u)));
-    };
     if (s->texture_count && !s->textures) INVALID("texture_count is %u but textures is null", s->texture_count);
     if (s->light_count && !s->lights) INVALID("light_count is %u but lights is null", s->light_count);
     if (s->texel_bytes && !s->texels) INVALID("texel_bytes is %llu but texels is null", (unsigned long long)s->texel_bytes);
-    for (uint32_t i = 1; i < s->texture_count; ++i) {   // slot 0 = none
-        const HiprTexture& t = s->textures[i];
-        const uint64_t size = texel_size(t.format);
-        if (size == 0) INVALID("texture %u has the unknown texel format %u", i, unsigned(t.format));
-        if (t.width == 0 || t.height == 0) INVALID("texture %u is %u x %u", i, t.width, t.height);
-        const uint64_t bytes = uint64_t(t.width) * t.height * size;
-        if (t.texel_offset > s->texel_bytes || bytes > s->texel_bytes - t.texel_offset || t.texel_offset % (size == 16 ? 16 : 4) != 0)
-            INVALID("texture %u (%u x %u, offset %llu) does not fit the %llu byte texel pool", i, t.width, t.height, (unsigned long long)t.texel_offset, (unsigned long long)s->texel_bytes);
-    }
+    for (uint32_t i = 1; i < s->texture_count; ++i)   // slot 0 = none
+        if (invalid_texture(s->textures[i], i, s->texel_bytes, message, message_size)) return message;
     for (uint32_t i = 0; i < s->material_count; ++i)
         if (invalid_material(s->materials[i], i, s->texture_count, message, message_size)) return message;
     const uint32_t primitive_total = s->index_count / 3;
@@ -1524,6 +1533,94 @@ int ResidentScene::update_materials(const HiprMaterialUpdate* changed, uint32_t 
     all_triangles_opaque = reduction[0] != 0;
     any_coated_triangle = reduction[1] != 0;
     ready = true;
+    return HIPR_OK;
+}
+
+// The device work of hipr_append_scene_pools (pool_growth.h). Every new buffer is allocated BEFORE the scene is touched: a failed allocation frees what it got and
+// leaves the scene as found. A pool whose buffer has the room (a larger scene was uploaded before) takes its tail in place; the others get a buffer of exactly the
+// new size -- no headroom: what it is worth has not been measured (the pools of the 10 M atrium are 152 MB and copy in 0.1 ms; a texel pool can be gigabytes). Then, as the other writers: not ready,
+// the copies and the mirror kernel on the stream, the new pointers in `args`, the host copies, the switches -- and the state the call found, ready or awaiting a
+// rebuild: no tree, triangle or instance references a tail, so nothing derived from them changes.
+int ResidentScene::append_pools(const HiprPoolGrowth& g, hipStream_t st) {
+    struct Pool { DeviceBuffer* pool; size_t keep, tail_bytes; const void* tail; DeviceBuffer fresh; };
+    const size_t vertices = uploaded_vertex_count;
+    // an attribute pool the device holds takes its tail; one it does not hold comes whole (or not at all)
+    auto attribute = [&](DeviceBuffer* pool, uint32_t bit, const void* array, uint32_t covered, size_t stride) -> Pool {
+        return {pool, uploaded_mesh_attributes & bit ? vertices * stride : 0u, size_t(covered) * stride, array, DeviceBuffer()};
+    };
+    size_t segment_words = 0;
+    for (uint32_t k = 0; k < g.segment_count; ++k) segment_words += g.segments[k].index_count;
+    Pool pools[] = {
+        {&indices, size_t(uploaded_index_count) * 4, segment_words * 4, nullptr, DeviceBuffer()},      // its tail is the segments'
+        {&geometry, vertices * sizeof(HiprVertexGeometry), size_t(g.vertex_count) * sizeof(HiprVertexGeometry), g.geometry, DeviceBuffer()},
+        attribute(&texcoords, HIPR_MESH_TEXCOORDS, g.texcoords, g.texcoord_vertices, 8),
+        attribute(&tints, HIPR_MESH_TINTS, g.tints, g.tint_vertices, 4),
+        attribute(&emissions, HIPR_MESH_EMISSIVE, g.emissions, g.emission_vertices, 12),
+        {&materials, uploaded_materials.size() * sizeof(HiprMaterial), size_t(g.material_count) * sizeof(HiprMaterial), g.materials, DeviceBuffer()},
+        {&textures, uploaded_textures.size() * sizeof(HiprTexture), size_t(g.texture_count) * sizeof(HiprTexture), g.textures, DeviceBuffer()},
+        {&texels, size_t(uploaded_texel_bytes), size_t(g.texel_bytes), g.texels, DeviceBuffer()},
+    };
+    const auto t0 = std::chrono::steady_clock::now();
+    for (Pool& p : pools)
+        if (p.tail_bytes && !(p.pool->ptr && p.pool->bytes >= p.keep + p.tail_bytes))
+            if (p.fresh.resize(p.keep + p.tail_bytes)) {
+                (void)hipGetLastError();      // the failed allocation's error is answered here: it must not meet the next call's check
+                return HIPR_ERROR_OUT_OF_MEMORY;      // `pools` goes, and with it what the others got
+            }
+    const auto t1 = std::chrono::steady_clock::now();
+    const bool was_ready = ready, awaited_rebuild = awaits_rebuild;
+    begin_write();
+    // the resident parts into the new allocations first; events around them tell their time from the tails' without a synchronise of their own
+    for (Event& e : append_events)
+        if (!e) e = make_event(hipEventDefault);
+    const bool timed = append_events[0] && append_events[1] && append_events[2];
+    if (timed) HIP_TRY(hipEventRecord(append_events[0], st));
+    for (Pool& p : pools)
+        if (p.tail_bytes && p.fresh.ptr) HIP_TRY(queue_pool_growth(p.fresh.ptr, p.pool->ptr, p.keep, nullptr, 0u, st));
+    if (timed) HIP_TRY(hipEventRecord(append_events[1], st));
+    for (Pool& p : pools) {
+        if (!p.tail_bytes) continue;
+        void* grown = p.fresh.ptr ? p.fresh.ptr : p.pool->ptr;
+        HIP_TRY(queue_pool_growth(grown, grown, p.keep, p.tail, p.tail ? p.tail_bytes : 0u, st));
+        if (p.pool != &indices) continue;
+        // the segments in order: a mirror reads what the stream has put there by then, earlier segments of this call included
+        uint32_t* words = static_cast<uint32_t*>(grown);
+        size_t position = uploaded_index_count, taken = 0;
+        for (uint32_t k = 0; k < g.segment_count; ++k) {
+            const HiprIndexSegment& s = g.segments[k];
+            if (s.mirrored_from == HIPR_SEGMENT_FROM_HOST) {
+                if (s.index_count) HIP_TRY(hipMemcpyAsync(words + position, g.indices + taken, size_t(s.index_count) * 4, hipMemcpyHostToDevice, st));
+                taken += s.index_count;
+            } else queue_mirror_triples(words, s.mirrored_from, uint32_t(position / 3), s.index_count / 3, st);
+            position += s.index_count;
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    if (timed) HIP_TRY(hipEventRecord(append_events[2], st));
+    HIP_TRY(hipStreamSynchronize(st));      // the caller's arrays are read; the old buffers are free to go
+    float copies_ms = 0.0f, tails_ms = 0.0f;
+    if (timed) { HIP_TRY(hipEventElapsedTime(&copies_ms, append_events[0], append_events[1])); HIP_TRY(hipEventElapsedTime(&tails_ms, append_events[1], append_events[2])); }
+    append_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count(); append_ms[1] = copies_ms; append_ms[2] = tails_ms;
+    for (Pool& p : pools)
+        if (p.fresh.ptr) std::swap(*p.pool, p.fresh);      // the old buffer goes with `pools`
+    args.indices = indices.as<uint32_t>();
+    args.geometry = geometry.as<float4>();
+    args.texcoords = texcoords.as<float2>();
+    args.tints = tints.as<uint32_t>();
+    args.emissions = emissions.as<float>();
+    args.materials = materials.as<HiprMaterial>();
+    args.textures = textures.as<HiprTexture>();
+    args.texels = texels.as<uint8_t>();
+    uploaded_materials.insert(uploaded_materials.end(), g.materials, g.materials + g.material_count);
+    uploaded_textures.insert(uploaded_textures.end(), g.textures, g.textures + g.texture_count);
+    uploaded_texture_count = uint32_t(uploaded_textures.size());
+    uploaded_vertex_count += g.vertex_count;
+    uploaded_index_count += uint32_t(segment_words);
+    uploaded_mesh_attributes |= (g.texcoord_vertices ? HIPR_MESH_TEXCOORDS : 0u) | (g.tint_vertices ? HIPR_MESH_TINTS : 0u) | (g.emission_vertices ? HIPR_MESH_EMISSIVE : 0u);
+    uploaded_texel_bytes += g.texel_bytes;
+    derive_switches_from_pools();
+    ready = was_ready;
+    awaits_rebuild = awaited_rebuild;
     return HIPR_OK;
 }
 
@@ -2329,11 +2426,93 @@ int hipr_edit_scene_instances(HiprContext* c, const HiprInstanceEdit* edits, uin
     return HIPR_OK;
 }
 
+// Not part of the public header: every refusal of hipr_append_scene_pools that is not a failed allocation, and nothing else -- no HIP call, the device and the
+// books stay as they are. The group asks every member before any member writes.
+int hipr_internal_check_pool_growth(HiprContext* c, const HiprPoolGrowth* g) {
+    const char* who = "hipr_append_scene_pools";
+    if (int st = check_context(c)) return st;
+    const ResidentScene& r = c->scene;
+    if (!r.ready && !r.awaits_rebuild) return fail(HIPR_ERROR_NOT_READY, "%s: no scene uploaded, or one a failed call left behind", who);
+    if (!g) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null description", who);
+    if ((g->vertex_count && !g->geometry) || (g->texcoord_vertices && !g->texcoords) || (g->tint_vertices && !g->tints) || (g->emission_vertices && !g->emissions) || (g->index_count && !g->indices) ||
+        (g->segment_count && !g->segments) || (g->material_count && !g->materials) || (g->texture_count && !g->textures) || (g->texel_bytes && !g->texels))
+        return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null array with a non-zero count", who);
+    const uint64_t limit = 0xFFFFFFFFull, vertices = uint64_t(r.uploaded_vertex_count) + g->vertex_count;
+    if (vertices > limit) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: %u + %u vertices do not fit 32 bits", who, r.uploaded_vertex_count, g->vertex_count);
+    const struct { const char* name; uint32_t bit, covered; } attributes[3] = {{"texcoords", HIPR_MESH_TEXCOORDS, g->texcoord_vertices}, {"tints", HIPR_MESH_TINTS, g->tint_vertices},
+                                                                               {"emissions", HIPR_MESH_EMISSIVE, g->emission_vertices}};
+    for (const auto& a : attributes) {
+        if (r.uploaded_mesh_attributes & a.bit) {
+            if (a.covered != g->vertex_count)
+                return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: the %s pool is resident and takes its tail, %u entries; %u given", who, a.name, g->vertex_count, a.covered);
+        } else if (a.covered != 0 && a.covered != vertices)
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: the %s pool is not resident and comes whole, %llu entries, or not at all; %u given", who, a.name, (unsigned long long)vertices, a.covered);
+    }
+    if (g->segment_count && r.uploaded_index_count % 3u) return fail(HIPR_ERROR_UNSUPPORTED, "%s: the uploaded index pool of %u words is not one of whole triples", who, r.uploaded_index_count);
+    uint64_t position = r.uploaded_index_count, from_host = 0;
+    for (uint32_t k = 0; k < g->segment_count; ++k) {
+        const HiprIndexSegment& s = g->segments[k];
+        if (s.index_count % 3u) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: segment %u has %u index words, not whole triples", who, k, s.index_count);
+        if (s.mirrored_from == HIPR_SEGMENT_FROM_HOST) from_host += s.index_count;
+        else if (3ull * s.mirrored_from + s.index_count > position)
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: segment %u mirrors %u triples from triple %u on, the pool holds %llu there", who, k, s.index_count / 3u, s.mirrored_from, (unsigned long long)(position / 3u));
+        position += s.index_count;
+        if (position > limit) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: the grown index pool does not fit 32 bits", who);
+    }
+    if (from_host != g->index_count) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: the host segments take %llu index words, %u given", who, (unsigned long long)from_host, g->index_count);
+    const uint64_t material_total = uint64_t(r.uploaded_materials.size()) + g->material_count, texture_total = uint64_t(r.uploaded_textures.size()) + g->texture_count;
+    if (material_total > limit || texture_total > limit || g->texel_bytes > ~0ull - r.uploaded_texel_bytes) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: the grown material, texture or texel pool does not fit its count", who);
+    char invalid[256];
+    for (uint32_t k = 0; k < g->texture_count; ++k)
+        if (invalid_texture(g->textures[k], uint32_t(r.uploaded_textures.size()) + k, r.uploaded_texel_bytes + g->texel_bytes, invalid, sizeof(invalid))) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: %s", who, invalid);
+    for (uint32_t k = 0; k < g->material_count; ++k)
+        if (invalid_material(g->materials[k], uint32_t(r.uploaded_materials.size()) + k, uint32_t(texture_total), invalid, sizeof(invalid))) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: %s", who, invalid);
+    return HIPR_OK;
+}
+
+// The resident pools grown at their tails (pool_growth.h): the description checked on the host, then ResidentScene::append_pools.
+int hipr_append_scene_pools(HiprContext* c, const HiprPoolGrowth* g) {
+    if (int st = hipr_internal_check_pool_growth(c, g)) return st;
+    if (!g->vertex_count && !g->texcoord_vertices && !g->tint_vertices && !g->emission_vertices && !g->segment_count && !g->material_count && !g->texture_count && !g->texel_bytes) return HIPR_OK;
+    if (int finish_status = finish_all(c)) return finish_status;      // no pending pass may go on over buffers that are about to move
+    c->break_chain(c->stream);
+    return c->scene.append_pools(*g, c->stream);
+}
+
+int hipr_debug_append_times(HiprContext* c, double* out3_ms) {
+    if (!c || !out3_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_append_times: null argument");
+    for (int k = 0; k < 3; ++k) out3_ms[k] = c->scene.append_ms[k];
+    return HIPR_OK;
+}
+
 int hipr_debug_rebuild_times(HiprContext* c, double* out5_ms) {
     if (!c || !out5_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_rebuild_times: null argument");
     const RebuildScratch& x = c->rebuild;
     out5_ms[0] = x.flatten_ms; out5_ms[1] = x.bvh2_ms; out5_ms[2] = x.collapse_ms; out5_ms[3] = x.install_ms; out5_ms[4] = x.readback_ms;
     return HIPR_OK;
+}
+
+// Where the device holds scene array `which`, and how many bytes of it the scene's counts make readable; false for an unknown array.
+static bool scene_buffer(const ResidentScene& r, int which, const void*& from, uint64_t& bytes) {
+    const uint64_t triangles = r.args.triangle_count, vertices = r.uploaded_vertex_count;
+    auto attribute = [&](const DeviceBuffer& pool, uint32_t bit, uint64_t stride) { from = pool.ptr; bytes = r.uploaded_mesh_attributes & bit ? vertices * stride : 0u; };      // an absent pool: zero bytes
+    if (which == HIPR_SCENE_BUFFER_TRIANGLES) { from = r.triangles.ptr; bytes = triangles * sizeof(HiprTriangle); }
+    else if (which == HIPR_SCENE_BUFFER_WIDE8_SLOTS) { from = r.wide8_slots.ptr; bytes = uint64_t(r.wide8.slot_count) * sizeof(HiprSlot8); }
+    else if (which == HIPR_SCENE_BUFFER_TRACE_TRIANGLES) { from = r.trace_triangles.ptr; bytes = triangles * 3 * sizeof(float4); }
+    else if (which == HIPR_SCENE_BUFFER_SHADE_TRIANGLES) { from = r.shade_triangles.ptr; bytes = triangles * SHADE_TRIANGLE_QUADS * sizeof(float4); }
+    else if (which == HIPR_SCENE_BUFFER_TRIANGLE_CLASS) { from = r.triangle_class.ptr; bytes = triangles; }
+    else if (which == HIPR_SCENE_BUFFER_MATERIALS) { from = r.materials.ptr; bytes = uint64_t(r.uploaded_materials.size()) * sizeof(HiprMaterial); }
+    else if (which == HIPR_SCENE_BUFFER_INSTANCES) { from = r.instances.ptr; bytes = uint64_t(r.uploaded_instances.size()) * sizeof(HiprInstance); }
+    else if (which == HIPR_SCENE_BUFFER_NODES) { from = r.nodes.ptr; bytes = uint64_t(r.args.node_count) * sizeof(HiprBvhNode); }
+    else if (which == HIPR_SCENE_BUFFER_INDICES) { from = r.indices.ptr; bytes = uint64_t(r.uploaded_index_count) * 4; }
+    else if (which == HIPR_SCENE_BUFFER_GEOMETRY) { from = r.geometry.ptr; bytes = vertices * sizeof(HiprVertexGeometry); }
+    else if (which == HIPR_SCENE_BUFFER_TEXCOORDS) attribute(r.texcoords, HIPR_MESH_TEXCOORDS, 8);
+    else if (which == HIPR_SCENE_BUFFER_TINTS) attribute(r.tints, HIPR_MESH_TINTS, 4);
+    else if (which == HIPR_SCENE_BUFFER_EMISSIONS) attribute(r.emissions, HIPR_MESH_EMISSIVE, 12);
+    else if (which == HIPR_SCENE_BUFFER_TEXTURES) { from = r.textures.ptr; bytes = uint64_t(r.uploaded_textures.size()) * sizeof(HiprTexture); }
+    else if (which == HIPR_SCENE_BUFFER_TEXELS) { from = r.texels.ptr; bytes = r.uploaded_texel_bytes; }
+    else return false;
+    return true;
 }
 
 int hipr_debug_read_scene_buffer(HiprContext* c, int which, void* out, uint64_t capacity_bytes) {
@@ -2342,18 +2521,19 @@ int hipr_debug_read_scene_buffer(HiprContext* c, int which, void* out, uint64_t 
     if (c->scene.args.triangle_count == 0 && c->scene.wide8.slot_count == 0) return fail(HIPR_ERROR_NOT_READY, "hipr_debug_read_scene_buffer: no scene uploaded");
     const void* from = nullptr;
     uint64_t bytes = 0;
-    if (which == HIPR_SCENE_BUFFER_TRIANGLES) { from = c->scene.triangles.ptr; bytes = uint64_t(c->scene.args.triangle_count) * sizeof(HiprTriangle); }
-    else if (which == HIPR_SCENE_BUFFER_WIDE8_SLOTS) { from = c->scene.wide8_slots.ptr; bytes = uint64_t(c->scene.wide8.slot_count) * sizeof(HiprSlot8); }
-    else if (which == HIPR_SCENE_BUFFER_TRACE_TRIANGLES) { from = c->scene.trace_triangles.ptr; bytes = uint64_t(c->scene.args.triangle_count) * 3 * sizeof(float4); }
-    else if (which == HIPR_SCENE_BUFFER_SHADE_TRIANGLES) { from = c->scene.shade_triangles.ptr; bytes = uint64_t(c->scene.args.triangle_count) * SHADE_TRIANGLE_QUADS * sizeof(float4); }
-    else if (which == HIPR_SCENE_BUFFER_TRIANGLE_CLASS) { from = c->scene.triangle_class.ptr; bytes = uint64_t(c->scene.args.triangle_count); }
-    else if (which == HIPR_SCENE_BUFFER_MATERIALS) { from = c->scene.materials.ptr; bytes = uint64_t(c->scene.uploaded_materials.size()) * sizeof(HiprMaterial); }
-    else if (which == HIPR_SCENE_BUFFER_INSTANCES) { from = c->scene.instances.ptr; bytes = uint64_t(c->scene.uploaded_instances.size()) * sizeof(HiprInstance); }
-    else if (which == HIPR_SCENE_BUFFER_NODES) { from = c->scene.nodes.ptr; bytes = uint64_t(c->scene.args.node_count) * sizeof(HiprBvhNode); }
-    else return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: unknown buffer %d", which);
+    if (!scene_buffer(c->scene, which, from, bytes)) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: unknown buffer %d", which);
     if (capacity_bytes < bytes) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_read_scene_buffer: %llu bytes needed, %llu given", (unsigned long long)bytes, (unsigned long long)capacity_bytes);
     if (int finish_status = finish_all(c)) return finish_status;
     if (bytes) HIP_TRY(hipMemcpy(out, from, bytes, hipMemcpyDeviceToHost));
+    return HIPR_OK;
+}
+
+int hipr_debug_scene_buffer_bytes(HiprContext* c, int which, uint64_t* out_bytes) {
+    if (int st = check_context(c)) return st;
+    if (!out_bytes) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_scene_buffer_bytes: null output");
+    if (c->scene.args.triangle_count == 0 && c->scene.wide8.slot_count == 0) return fail(HIPR_ERROR_NOT_READY, "hipr_debug_scene_buffer_bytes: no scene uploaded");
+    const void* from = nullptr;
+    if (!scene_buffer(c->scene, which, from, *out_bytes)) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_scene_buffer_bytes: unknown buffer %d", which);
     return HIPR_OK;
 }
 

@@ -41,6 +41,11 @@ def load_host_library() -> C.CDLL:
     lib.hiprh_scene_model_info.argtypes = [vp, C.c_uint, C.POINTER(C.c_uint)]
     lib.hiprh_scene_staged_edits.argtypes = [vp, C.POINTER(capi.HiprInstanceEdit), C.c_uint]
     lib.hiprh_scene_adopt_edited_trees.argtypes = [vp, vp, C.c_uint, vp, C.c_uint, C.c_uint, vp, C.POINTER(capi.HiprWide8BuildResult)]
+    fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint)
+    lib.hiprh_scene_add_mesh.argtypes = [vp, fp, fp, fp, up, fp, C.c_uint, up, C.c_uint]
+    lib.hiprh_scene_add_material.argtypes = [vp, C.POINTER(capi.HiprMaterial)]
+    lib.hiprh_scene_add_texture.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.POINTER(C.c_ubyte), C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.hiprh_scene_staged_growth.argtypes = [vp, C.POINTER(capi.HiprPoolGrowth), C.POINTER(capi.HiprInstanceEdit), C.c_uint]
     lib.hiprh_scene_materials.argtypes = [vp, C.POINTER(C.c_uint)]
     lib.hiprh_scene_materials.restype = C.POINTER(capi.HiprMaterial)
     lib.hiprh_scene_instances.argtypes = [vp, C.POINTER(C.c_uint)]
@@ -271,6 +276,51 @@ class Scene:
         edits = (capi.HiprInstanceEdit * count)()
         self.lib.hiprh_scene_staged_edits(self.handle, edits, count)
         return edits
+
+    def add_mesh(self, positions, primitives, normals=None, texcoords=None, tints=None, emission=None) -> int:
+        """SceneBuilder::add_mesh: `positions` (vertices, 3), `primitives` (triangles, 3) vertex indices; optional, one per vertex: `normals` (.., 3), `texcoords` (.., 2),
+        `tints` (..,) uint32 (tint rgb, roughness), `emission` (.., 3). Returns the mesh index. After a build the pools lead the description until rebuild() or an
+        adoption has caught up (staged_scene_growth)."""
+        positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        primitives = np.ascontiguousarray(primitives, np.uint32).reshape(-1, 3)
+        per_vertex = lambda a, dtype, width: None if a is None else np.ascontiguousarray(a, dtype).reshape(len(positions), width)
+        normals, texcoords, tints, emission = per_vertex(normals, np.float32, 3), per_vertex(texcoords, np.float32, 2), per_vertex(tints, np.uint32, 1), per_vertex(emission, np.float32, 3)
+        floats = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+        words = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint))
+        mesh = self.lib.hiprh_scene_add_mesh(self.handle, floats(positions), floats(normals), floats(texcoords), words(tints), floats(emission), len(positions), words(primitives), len(primitives))
+        if mesh < 0:
+            raise capi.HiprError("hiprh_scene_add_mesh failed")
+        return int(mesh)
+
+    def add_material(self, material: capi.HiprMaterial) -> int:
+        """SceneBuilder::add_material. Returns the material index."""
+        index = self.lib.hiprh_scene_add_material(self.handle, C.byref(material))
+        if index < 0:
+            raise capi.HiprError("hiprh_scene_add_material failed")
+        return int(index)
+
+    def add_texture(self, pixels: np.ndarray, width: int, height: int, texel_format: int, is_sRGB: bool = False, repeat=(True, True), linear=(True, True)) -> int:
+        """SceneBuilder::add_texture: `pixels` are the width x height texels of `texel_format` (capi.TEXEL_*) as bytes. Returns the texture index."""
+        pixels = np.ascontiguousarray(pixels).view(np.uint8).reshape(-1)
+        index = self.lib.hiprh_scene_add_texture(self.handle, width, height, texel_format, int(is_sRGB), pixels.ctypes.data_as(C.POINTER(C.c_ubyte)), pixels.nbytes, int(repeat[0]), int(repeat[1]),
+                                                 int(linear[0]), int(linear[1]))
+        if index < 0:
+            raise capi.HiprError("hiprh_scene_add_texture failed")
+        return int(index)
+
+    def staged_scene_growth(self):
+        """SceneBuilder::staged_scene_growth: (capi.HiprPoolGrowth, ctypes array of capi.HiprInstanceEdit) for everything since the last build or adoption -- what
+        Context.append_scene_pools and Context.edit_scene_instances take, in that order -- or None when it is not the device's to apply (nothing built, a transform
+        staged, an environment set since). The growth's pointers hold until the next call of this method and the next add_* call."""
+        growth = capi.HiprPoolGrowth()
+        count = self.lib.hiprh_scene_staged_growth(self.handle, C.byref(growth), None, 0)
+        if count == -2:
+            return None
+        if count < 0:
+            raise capi.HiprError("hiprh_scene_staged_growth failed")
+        edits = (capi.HiprInstanceEdit * count)()
+        self.lib.hiprh_scene_staged_growth(self.handle, C.byref(growth), edits, count)
+        return growth, edits
 
     def adopt_edited_trees(self, nodes: np.ndarray, order: np.ndarray, deepest: int, slots: np.ndarray, wide8) -> bool:
         """SceneBuilder::adopt_edited_trees: the trees Context.edit_scene_instances made of the edited instance list taken over in place of a rebuild; arguments as

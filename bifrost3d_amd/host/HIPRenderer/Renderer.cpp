@@ -117,10 +117,26 @@ static std::vector<HiprLight> collect_lights() {
     return lights;
 }
 
-void flatten_bifrost_scene(SceneBuilder& sb, std::map<unsigned int, uint32_t>& mesh_index) {
+// The mesh as SceneBuilder::add_mesh takes it (load_mesh, OR/Renderer.cpp:92-136).
+static MeshData mesh_data(Mesh mesh) {
+    MeshData data;
+    const unsigned int vertex_count = mesh.get_vertex_count(), primitive_count = mesh.get_primitive_count();
+    data.positions.assign(mesh.get_positions(), mesh.get_positions() + vertex_count);
+    if (mesh.get_normals()) data.normals.assign(mesh.get_normals(), mesh.get_normals() + vertex_count);
+    if (mesh.get_texcoords()) data.texcoords.assign(mesh.get_texcoords(), mesh.get_texcoords() + vertex_count);
+    if (mesh.get_tint_and_roughness()) {
+        data.tints.resize(vertex_count);
+        std::memcpy(data.tints.data(), mesh.get_tint_and_roughness(), vertex_count * 4);
+    }
+    if (mesh.get_emission()) data.emission.assign(mesh.get_emission(), mesh.get_emission() + vertex_count);
+    data.primitives.assign(mesh.get_primitives(), mesh.get_primitives() + primitive_count);
+    return data;
+}
 
-    // Textures and materials keep their Bifrost indices (slot 0 = invalid), like the reference's per-ID arrays.
-    for (unsigned int t = 1; t < Textures::capacity(); ++t) {
+// Textures and materials keep their Bifrost indices (slot 0 = invalid), like the reference's per-ID arrays: the slots from the builder's pool sizes up to the
+// managers' capacities are added, dead ones as fillers. A flatten starts from the empty pools; a growth of the resident scene from the pools as they stand.
+static void add_textures_and_materials_up_to_capacity(SceneBuilder& sb) {
+    for (unsigned int t = unsigned(sb.texture_count()); t < Textures::capacity(); ++t) {
         TextureID id(t);
         ImageData image;
         bool alive = Textures::get_image_ID(id) != ImageID::invalid_UID();
@@ -131,7 +147,11 @@ void flatten_bifrost_scene(SceneBuilder& sb, std::map<unsigned int, uint32_t>& m
     }
     std::vector<bool> material_alive(Materials::capacity(), false);
     for (MaterialID id : Materials::get_iterable()) material_alive[id] = true;
-    for (unsigned int m = 1; m < Materials::capacity(); ++m) sb.add_material(material_alive[m] ? upload_material(MaterialID(m)) : HiprMaterial{});
+    for (unsigned int m = unsigned(sb.materials().size()); m < Materials::capacity(); ++m) sb.add_material(material_alive[m] ? upload_material(MaterialID(m)) : HiprMaterial{});
+}
+
+void flatten_bifrost_scene(SceneBuilder& sb, std::map<unsigned int, uint32_t>& mesh_index) {
+    add_textures_and_materials_up_to_capacity(sb);
 
     // Meshes are added once and shared by the models that reference them (load_mesh, OR/Renderer.cpp:92-136).
     mesh_index.clear();      // kept by the caller: a model created later over one of these meshes is an edit of the resident scene
@@ -139,20 +159,7 @@ void flatten_bifrost_scene(SceneBuilder& sb, std::map<unsigned int, uint32_t>& m
         MeshModel model = model_ID;
         Mesh mesh = model.get_mesh();
         auto it = mesh_index.find(mesh.get_ID());
-        if (it == mesh_index.end()) {
-            MeshData data;
-            const unsigned int vertex_count = mesh.get_vertex_count(), primitive_count = mesh.get_primitive_count();
-            data.positions.assign(mesh.get_positions(), mesh.get_positions() + vertex_count);
-            if (mesh.get_normals()) data.normals.assign(mesh.get_normals(), mesh.get_normals() + vertex_count);
-            if (mesh.get_texcoords()) data.texcoords.assign(mesh.get_texcoords(), mesh.get_texcoords() + vertex_count);
-            if (mesh.get_tint_and_roughness()) {
-                data.tints.resize(vertex_count);
-                std::memcpy(data.tints.data(), mesh.get_tint_and_roughness(), vertex_count * 4);
-            }
-            if (mesh.get_emission()) data.emission.assign(mesh.get_emission(), mesh.get_emission() + vertex_count);
-            data.primitives.assign(mesh.get_primitives(), mesh.get_primitives() + primitive_count);
-            it = mesh_index.emplace(mesh.get_ID(), sb.add_mesh(std::move(data))).first;
-        }
+        if (it == mesh_index.end()) it = mesh_index.emplace(mesh.get_ID(), sb.add_mesh(mesh_data(mesh))).first;
         // create_model: InstanceID = (MeshModel << 30) | model index, material_index = MaterialID index (OR/Renderer.cpp:138-159)
         sb.add_model(it->second, model.get_material().get_ID().get_index(), model.get_scene_node().get_global_transform(), model_ID.get_index());
     }
@@ -215,7 +222,7 @@ struct Renderer::Implementation {
     HiprSceneState scene_state = {{0, 0, 0}, 3};                     // next_event_sample_count = 3, OR/Renderer.cpp:479
     std::unique_ptr<SceneBuilder> scene;
     std::map<unsigned int, uint32_t> scene_mesh_index;      // Bifrost mesh ID -> the scene builder's mesh
-    Renderer::SceneUpdateCounts scene_updates = {0, 0, 0, 0, 0};
+    Renderer::SceneUpdateCounts scene_updates = {0, 0, 0, 0, 0, 0};
     Renderer::SceneBuildCounts retired_builds = {0, 0};      // of the scene builders that are gone
     Renderer::SceneCollapseCounts retired_collapses = {0, 0};
     Renderer::SceneRebuildCounts scene_rebuilds = {0, 0};
@@ -412,9 +419,18 @@ struct Renderer::Implementation {
     // builder adopts them (SceneBuilder::adopt_edited_trees), every other uploaded camera edits without outputs. false: the caller takes the full path, silently --
     // the variable unset, a camera that is not traced through the 8-wide tree or waits for something, a mesh the builder does not hold, any refusal. The builder may
     // then hold staged edits: the caller retires it. Off by default, as the rebuild path is (profiles/instance_edit_device_vs_host.txt has the figures).
-    bool edit_instances_on_the_device() {
+    //
+    // `grow` (HIPR_DEVICE_POOL_GROWTH=1, asked for by grow_pools_wanted()): the tick also brings meshes, materials or textures the builder does not hold. They go
+    // through the builder's add_* calls -- textures and materials up to the managers' capacities as a flatten adds them, a created model's mesh when the builder has
+    // none for it -- and every camera first has the tails appended to its resident pools (hipr_append_scene_pools; csrc/pool_growth.h; OR/Renderer.cpp:92-136
+    // load_mesh, :703-812), then edits as above with what SceneBuilder::staged_scene_growth lists. Counted in pool_growths instead.
+    static bool grow_pools_wanted() {
+        const char* wanted = std::getenv("HIPR_DEVICE_POOL_GROWTH");
+        return wanted && std::atoi(wanted) != 0;
+    }
+    bool edit_instances_on_the_device(bool grow = false) {
         const char* wanted = std::getenv("HIPR_DEVICE_INSTANCE_EDIT");
-        if (!wanted || std::atoi(wanted) == 0 || !scene || scene->has_staged_transforms()) return false;
+        if (!(grow ? grow_pools_wanted() : wanted && std::atoi(wanted) != 0) || !scene || scene->has_staged_transforms()) return false;
         CameraState* first = nullptr;
         for (CameraState& c : per_camera_state) {
             if (!c.context || !c.scene_uploaded) continue;      // uploads the description later, with everything in it
@@ -424,14 +440,16 @@ struct Renderer::Implementation {
         }
         if (!first) return false;
         const uint32_t triangles_before = scene->desc_triangle_count();
+        if (grow) add_textures_and_materials_up_to_capacity(*scene);
         for (MeshModelID model_ID : MeshModels::get_changed_models())
             if (MeshModels::get_changes(model_ID).contains(MeshModels::Change::Destroyed)) scene->remove_model(model_ID.get_index());      // false: created and destroyed since the last tick
         uint32_t rank = 0;
         for (MeshModelID model_ID : MeshModels::get_iterable()) {
             if (MeshModels::get_changes(model_ID).contains(MeshModels::Change::Created)) {
                 MeshModel model = model_ID;
-                const auto mesh = scene_mesh_index.find(model.get_mesh().get_ID());
+                auto mesh = scene_mesh_index.find(model.get_mesh().get_ID());
                 const uint32_t material = model.get_material().get_ID().get_index();
+                if (mesh == scene_mesh_index.end() && grow) mesh = scene_mesh_index.emplace(model.get_mesh().get_ID(), scene->add_mesh(mesh_data(model.get_mesh()))).first;
                 if (mesh == scene_mesh_index.end() || material >= scene->materials().size()) return false;      // a pool would grow
                 scene->insert_model(rank, mesh->second, material, model.get_scene_node().get_global_transform(), model_ID.get_index());
             }
@@ -443,7 +461,8 @@ struct Renderer::Implementation {
         for (MeshModelID model_ID : MeshModels::get_iterable())
             if (uint32_t(instances[rank++].instance_id) != ((1u << 30) | model_ID.get_index())) return false;      // not the order a flatten would give
         std::vector<HiprInstanceEdit> edits;
-        if (!scene->staged_instance_edits(edits) || edits.empty()) return false;
+        SceneBuilder::StagedGrowth growth;
+        if (!(grow ? scene->staged_scene_growth(growth, edits) : scene->staged_instance_edits(edits)) || edits.empty()) return false;
         uint64_t bound = triangles_before;
         for (const HiprInstanceEdit& e : edits) bound += e.source == HIPR_EDIT_NEW_INSTANCE ? e.primitive_count : 0u;
         const uint32_t n = uint32_t(std::min<uint64_t>(bound, 0xFFFFFFFFull));
@@ -452,7 +471,7 @@ struct Renderer::Implementation {
         Room nodes = {std::malloc(size_t(node_capacity) * sizeof(HiprBvhNode))}, order = {std::malloc(size_t(std::max(n, 1u)) * 4)}, slots = {std::malloc(size_t(std::max(slot_capacity, 1u)) * sizeof(HiprSlot8))};
         HiprSceneEditResult edited = {};
         for (CameraState& c : per_camera_state) c.drop_batch();
-        const bool done = nodes.p && order.p && slots.p &&
+        const bool done = nodes.p && order.p && slots.p && (!grow || hipr_group_append_scene_pools(first->context, &growth.growth) == HIPR_OK) &&
                           hipr_group_edit_scene_instances(first->context, edits.data(), uint32_t(edits.size()), scene->bvh_max_depth_limit(), static_cast<HiprBvhNode*>(nodes.p), node_capacity,
                                                           static_cast<uint32_t*>(order.p), n, static_cast<HiprSlot8*>(slots.p), slot_capacity, &edited) == HIPR_OK;
         if (!done || !scene->adopt_edited_trees(static_cast<const HiprBvhNode*>(nodes.p), edited.node_count, static_cast<const uint32_t*>(order.p), edited.triangle_count, edited.deepest,
@@ -461,9 +480,11 @@ struct Renderer::Implementation {
         for (CameraState& c : per_camera_state) {
             if (&c == first || !c.context || !c.scene_uploaded) continue;
             HiprSceneEditResult same = {};
-            if (hipr_group_edit_scene_instances(c.context, edits.data(), uint32_t(edits.size()), scene->bvh_max_depth_limit(), nullptr, 0, nullptr, 0, nullptr, 0, &same) != HIPR_OK) c.scene_uploaded = false;
+            if ((grow && hipr_group_append_scene_pools(c.context, &growth.growth) != HIPR_OK) ||
+                hipr_group_edit_scene_instances(c.context, edits.data(), uint32_t(edits.size()), scene->bvh_max_depth_limit(), nullptr, 0, nullptr, 0, nullptr, 0, &same) != HIPR_OK)
+                c.scene_uploaded = false;
         }
-        ++scene_updates.instance_edits;
+        ++(grow ? scene_updates.pool_growths : scene_updates.instance_edits);
         return true;
     }
 
@@ -489,6 +510,10 @@ struct Renderer::Implementation {
     // ---- handle_updates -----------------------------------------------------------------------------------------------
     void handle_updates() {
         bool should_reset_accumulations = false, scene_dirty = false, models_edited = false;
+        // HIPR_DEVICE_POOL_GROWTH=1: meshes created or destroyed, materials created past the builder's pool and images and textures created past it are dirt the
+        // resident scene can take at the tails of its pools, where models created or destroyed are the only other dirt of the tick (edit_instances_on_the_device).
+        const bool pools_may_grow = scene && grow_pools_wanted();
+        bool pools_grow = false;
 
         for (CameraID cam_ID : Cameras::get_changed_cameras()) {   // OR/Renderer.cpp:581-619
             auto changes = Cameras::get_changes(cam_ID);
@@ -514,19 +539,29 @@ struct Renderer::Implementation {
         }
 
         for (MeshID mesh_ID : Meshes::get_changed_meshes())
-            if (Meshes::get_changes(mesh_ID).any_set(Meshes::Change::Created, Meshes::Change::Destroyed)) scene_dirty = true;
-        if (!Images::get_changed_images().is_empty() || !Textures::get_changed_textures().is_empty()) scene_dirty = true;
+            if (Meshes::get_changes(mesh_ID).any_set(Meshes::Change::Created, Meshes::Change::Destroyed)) {
+                (pools_may_grow ? pools_grow : scene_dirty) = true;      // a destroyed mesh's data stays pooled ...
+                scene_mesh_index.erase(mesh_ID.get_index());      // ... but its ID is recycled after the tick: whatever mesh carries it from here on is not the one the builder holds
+            }
+        if (!Images::get_changed_images().is_empty() || !Textures::get_changed_textures().is_empty()) {
+            bool created_past_the_pool = pools_may_grow;
+            for (ImageID image_ID : Images::get_changed_images()) created_past_the_pool = created_past_the_pool && Images::get_changes(image_ID) == Images::Change::Created;
+            for (TextureID texture_ID : Textures::get_changed_textures())
+                created_past_the_pool = created_past_the_pool && Textures::get_changes(texture_ID) == Textures::Change::Created && texture_ID.get_index() >= scene->texture_count();
+            (created_past_the_pool ? pools_grow : scene_dirty) = true;
+        }
 
         // Materials (:753-850). A changed material inside the uploaded pool is an edit of the resident scene (update_materials_on_the_device); a pool that grew is a new scene.
         std::vector<HiprMaterialUpdate> changed_materials;
         std::vector<HiprInstanceMaterial> material_assignments;
-        bool materials_dirty = false;
+        bool materials_dirty = false, only_created_materials = true;      // the latter: every entry of changed_materials is a material created in a free slot of the pool
         for (MaterialID material_ID : Materials::get_changed_materials()) {
             auto changes = Materials::get_changes(material_ID);
             if (!changes.any_set(Materials::Change::Created, Materials::Change::Updated, Materials::Change::ShadingModel)) continue;
             should_reset_accumulations = true;
             if (scene && !changes.contains(Materials::Change::Destroyed) && material_ID.get_index() < scene->materials().size())
-                changed_materials.push_back({uint32_t(material_ID.get_index()), upload_material(material_ID)});
+                { changed_materials.push_back({uint32_t(material_ID.get_index()), upload_material(material_ID)}); only_created_materials = only_created_materials && changes.contains(Materials::Change::Created); }
+            else if (pools_may_grow && !changes.contains(Materials::Change::Destroyed)) pools_grow = true;      // created past the pool
             else materials_dirty = true;
         }
         // Lights (:852-1008): created or destroyed lights change the light count (a new scene description); updated ones are replaced in place.
@@ -586,11 +621,13 @@ struct Renderer::Implementation {
         // they make a new scene as they always did.
         if (materials_dirty) scene_dirty = true;
         // Created and destroyed models likewise: with any other dirt in the tick they make a new scene.
-        if (models_edited && (!moved_models.empty() || lights_moved || !changed_materials.empty() || !material_assignments.empty())) scene_dirty = true;
+        // (With pools that may grow, a material created in a free slot of the pool is the material edit below, and the models follow it.)
+        if (models_edited && (!moved_models.empty() || lights_moved || (!changed_materials.empty() && !(pools_may_grow && pools_grow && only_created_materials)) || !material_assignments.empty())) scene_dirty = true;
         if (!changed_materials.empty() || !material_assignments.empty())
             if (scene_dirty || !scene || !moved_models.empty() || lights_moved || !update_materials_on_the_device(changed_materials, material_assignments)) scene_dirty = true;
 
-        if (models_edited && (scene_dirty || !edit_instances_on_the_device())) scene_dirty = true;
+        if (pools_grow && !models_edited) scene_dirty = true;      // nothing draws the new data yet: the next scene brings it
+        if (models_edited && (scene_dirty || !edit_instances_on_the_device(pools_grow))) scene_dirty = true;
 
         if (!scene_dirty && scene && (!moved_models.empty() || lights_moved)) {
             // transform-only tick: refit in place; a tree the motion has stretched too far is rebuilt by the scene builder itself

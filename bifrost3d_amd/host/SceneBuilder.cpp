@@ -78,6 +78,7 @@ uint32_t SceneBuilder::add_mesh(MeshData mesh) {
     if (!mesh.emission.empty()) r.flags |= HIPR_MESH_EMISSIVE;
 
     for (const Vector3ui& p : mesh.primitives) { m_indices.push_back(p.x); m_indices.push_back(p.y); m_indices.push_back(p.z); }
+    m_index_log.push_back({HIPR_SEGMENT_FROM_HOST, 3u * r.primitive_count});
     for (uint32_t i = 0; i < r.vertex_count; ++i) {
         HiprVertexGeometry g = {};
         g.position[0] = mesh.positions[i].x; g.position[1] = mesh.positions[i].y; g.position[2] = mesh.positions[i].z;
@@ -133,6 +134,7 @@ uint32_t SceneBuilder::index_offset_for(uint32_t mesh, const float* object_to_wo
     if (r.mirrored_index_offset == 0xFFFFFFFFu) {
         r.mirrored_index_offset = uint32_t(m_indices.size() / 3);
         m_pools_grew = true;
+        m_index_log.push_back({r.index_offset, 3u * r.primitive_count});
         for (uint32_t p = 0; p < r.primitive_count; ++p) {
             const size_t at = 3 * size_t(r.index_offset + p);
             const uint32_t a = m_indices[at], b = m_indices[at + 1], c = m_indices[at + 2];
@@ -213,6 +215,7 @@ void SceneBuilder::set_environment(uint32_t texture_index, uint32_t pdf_width, u
     m_environment_samples = std::move(samples);
     m_environment = {int32_t(texture_index), pdf_width, pdf_height, nullptr, nullptr, uint32_t(m_environment_samples.size())};
     m_has_environment = true;
+    m_environment_set_since = m_built;
     if (m_environment_samples.size() > 1) {   // next_event_estimation_possible (PresampledEnvironmentMap.h:64)
         HiprLight light = {};
         light.flags = HIPR_LIGHT_PRESAMPLED_ENVIRONMENT;
@@ -274,6 +277,9 @@ void SceneBuilder::build_trees_over(const std::vector<HiprTriangle>& world, cons
     for (size_t k = 0; k < world.size(); ++k) m_triangles[k] = world[m_bvh.order[k]];
     m_built = true; m_pools_grew = false;      // the triangles and the trees are those of the instance list and the pools as they stand
     m_built_instance_count = uint32_t(m_instances.size());
+    m_built_pools = {m_indices.size(), m_geometry.size(), m_materials.size(), m_textures.size(), m_texels.size(), m_lights.size(), m_any_texcoords, m_any_tints, m_any_emission};
+    m_index_log.clear();
+    m_environment_set_since = false;
     m_built_index.resize(m_instances.size());
     for (size_t i = 0; i < m_built_index.size(); ++i) m_built_index[i] = uint32_t(i);
 
@@ -471,7 +477,58 @@ bool SceneBuilder::adopt_rebuilt_trees(const HiprBvhNode* nodes, uint32_t node_c
 
 bool SceneBuilder::staged_instance_edits(std::vector<HiprInstanceEdit>& edits) const {
     edits.clear();
-    if (!m_built || m_pools_grew || m_staged_flips || std::find(m_staged_moved.begin(), m_staged_moved.end(), true) != m_staged_moved.end()) return false;
+    return !m_pools_grew && list_instance_edits(edits);
+}
+
+bool SceneBuilder::staged_scene_growth(StagedGrowth& out, std::vector<HiprInstanceEdit>& edits) const {
+    out = {};
+    edits.clear();
+    const PoolSizes& b = m_built_pools;
+    if (m_environment_set_since || m_lights.size() != b.lights || !list_instance_edits(edits)) { edits.clear(); return false; }
+    HiprPoolGrowth& g = out.growth;
+    const size_t vertices = m_geometry.size(), created = vertices - b.vertices;
+    g.vertex_count = uint32_t(created);
+    g.geometry = created ? m_geometry.data() + b.vertices : nullptr;
+    // a pool that existed takes its tail; one that has come into being since comes whole, with whatever add_mesh put there for the meshes without the attribute
+    if (b.texcoords) { g.texcoord_vertices = uint32_t(created); g.texcoords = created ? m_texcoords.data() + 2 * b.vertices : nullptr; }
+    else if (m_any_texcoords) { g.texcoord_vertices = uint32_t(vertices); g.texcoords = m_texcoords.data(); }
+    if (b.tints) { g.tint_vertices = uint32_t(created); g.tints = created ? m_tints.data() + b.vertices : nullptr; }
+    else if (m_any_tints) { g.tint_vertices = uint32_t(vertices); g.tints = m_tints.data(); }
+    if (b.emission) { g.emission_vertices = uint32_t(created); g.emissions = created ? m_emissions.data() + 3 * b.vertices : nullptr; }
+    else if (m_any_emission) { g.emission_vertices = uint32_t(vertices); g.emissions = m_emissions.data(); }
+    // the index tail: the log's ranges in order, neighbouring mesh ranges as one segment
+    size_t words = 0, from_host = 0;
+    bool mirrors_between = false;
+    for (const HiprIndexSegment& range : m_index_log) {
+        if (range.mirrored_from == HIPR_SEGMENT_FROM_HOST) { mirrors_between = mirrors_between || from_host != words; from_host += range.index_count; }
+        if (range.mirrored_from == HIPR_SEGMENT_FROM_HOST && !out.segments.empty() && out.segments.back().mirrored_from == HIPR_SEGMENT_FROM_HOST) out.segments.back().index_count += range.index_count;
+        else out.segments.push_back(range);
+        words += range.index_count;
+    }
+    if (b.index_words + words != m_indices.size()) { out = {}; edits.clear(); return false; }      // the log does not tell the tail: the full path
+    if (mirrors_between) {
+        size_t at = b.index_words;
+        for (const HiprIndexSegment& range : m_index_log) {
+            if (range.mirrored_from == HIPR_SEGMENT_FROM_HOST) out.host_indices.insert(out.host_indices.end(), m_indices.begin() + ptrdiff_t(at), m_indices.begin() + ptrdiff_t(at + range.index_count));
+            at += range.index_count;
+        }
+    }
+    g.index_count = uint32_t(from_host);
+    g.indices = !from_host ? nullptr : (mirrors_between ? out.host_indices.data() : m_indices.data() + b.index_words);
+    g.segment_count = uint32_t(out.segments.size());
+    g.segments = out.segments.empty() ? nullptr : out.segments.data();
+    g.material_count = uint32_t(m_materials.size() - b.materials);
+    g.materials = g.material_count ? m_materials.data() + b.materials : nullptr;
+    g.texture_count = uint32_t(m_textures.size() - b.textures);
+    g.textures = g.texture_count ? m_textures.data() + b.textures : nullptr;
+    g.texel_bytes = uint64_t(m_texels.size() - b.texel_bytes);
+    g.texels = g.texel_bytes ? m_texels.data() + b.texel_bytes : nullptr;
+    return true;
+}
+
+bool SceneBuilder::list_instance_edits(std::vector<HiprInstanceEdit>& edits) const {
+    edits.clear();
+    if (!m_built || m_staged_flips || std::find(m_staged_moved.begin(), m_staged_moved.end(), true) != m_staged_moved.end()) return false;
     edits.resize(m_instances.size());
     for (size_t i = 0; i < m_instances.size(); ++i) {
         HiprInstanceEdit& e = edits[i];
@@ -485,7 +542,8 @@ bool SceneBuilder::staged_instance_edits(std::vector<HiprInstanceEdit>& edits) c
 bool SceneBuilder::adopt_edited_trees(const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, uint32_t order_count, uint32_t deepest, const HiprSlot8* slots, const HiprWide8BuildResult& wide8) {
     auto refuse = [&] { ++m_rebuild_counts.refused; return false; };
     std::vector<HiprInstanceEdit> unused;
-    if (!staged_instance_edits(unused) || m_bvh.order.size() != m_triangles.size()) return refuse();      // what the device could not have been given
+    StagedGrowth unused_growth;
+    if (!staged_scene_growth(unused_growth, unused) || m_bvh.order.size() != m_triangles.size()) return refuse();      // what the device could not have been given
     // first[] of the list as it stands, and where the built list's instances went
     std::vector<uint32_t> first(m_instances.size() + 1, 0u), new_index(m_built_instance_count, NOT_BUILT);
     uint64_t total = 0;

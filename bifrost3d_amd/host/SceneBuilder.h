@@ -118,8 +118,20 @@ public:
     // built over, new ones with their record and primitive count. False -- "not on the device" -- when nothing is built yet, when a pool has grown since (a new mesh,
     // material or texture; the mirrored index copy of a mirrored new instance), or when a transform is staged as well: the caller takes the full path.
     bool staged_instance_edits(std::vector<HiprInstanceEdit>& edits) const;
+    // What hipr_append_scene_pools AND hipr_edit_scene_instances take for everything since the last build or adoption, pool growth included: `growth.growth` carries
+    // the tails of the pools -- new vertices, with an optional per-vertex pool's tail where the pool existed at that point and the WHOLE pool where it did not; the
+    // index tail as segments, from the log add_mesh and index_offset_for keep: mesh triples from the host, mirrored copies as mirrors of the range they copy; new
+    // materials, textures and texels -- and `edits` the instance list as staged_instance_edits makes it. The pointers of `growth.growth` point into the builder's pools
+    // and into `growth`: they hold until the next add_* call and as long as `growth` lives. False -- "not on the device" -- when nothing is built yet, when a transform
+    // is staged as well, or when an environment was set or a light added since.
+    struct StagedGrowth {
+        HiprPoolGrowth growth = {};
+        std::vector<HiprIndexSegment> segments;
+        std::vector<uint32_t> host_indices;      // the host segments' words, when mirrors lie between them in the pool; otherwise `growth.indices` points into the pool
+    };
+    bool staged_scene_growth(StagedGrowth& growth, std::vector<HiprInstanceEdit>& edits) const;
     // adopt_rebuilt_trees generalised to an edited instance list (the trees hipr_edit_scene_instances made): the builder's own triangles of kept instances go to their
-    // place in the new list's flatten order with their new instance index, removed ranges are dropped, ONLY the new instances are flattened, and everything goes
+    // place in the new list's flatten order with their new instance index, removed ranges are dropped, ONLY the new instances are flattened -- from the builder's own pools, grown or not -- and everything goes
     // through `order` (`order_count` words) into the new trees' order. desc() is then, in every array and scalar, what rebuild() leaves. Refuses as adopt_rebuilt_trees
     // does, with nothing touched; counted in rebuild_counts().
     bool adopt_edited_trees(const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, uint32_t order_count, uint32_t deepest, const HiprSlot8* slots, const HiprWide8BuildResult& wide8);
@@ -147,6 +159,7 @@ public:
     CameraDescription camera;
     AABB bounds() const { assert(!m_staged && "apply_staged_transforms() first"); return m_bounds; }
     size_t mesh_count() const { return m_meshes.size(); }
+    size_t texture_count() const { return m_textures.size(); }      // slot 0, "no texture", included
     size_t model_count() const { return m_instances.size(); }
 
 private:
@@ -160,6 +173,14 @@ private:
     void flatten_instance(uint32_t instance, std::vector<HiprTriangle>& world);
     bool trees_fit(uint32_t triangle_count, const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, const HiprSlot8* slots, const HiprWide8BuildResult& wide8) const;
     void note_instance_edit();
+    bool list_instance_edits(std::vector<HiprInstanceEdit>& edits) const;      // staged_instance_edits without its question about the pools
+    // The pool sizes at the last build or adoption (build_trees_over): what the device holds when it follows the builder, and where the tails begin.
+    struct PoolSizes { size_t index_words = 0, vertices = 0, materials = 0, textures = 0, texel_bytes = 0, lights = 0; bool texcoords = false, tints = false, emission = false; };
+    PoolSizes m_built_pools;
+    // The ranges m_indices has grown by since then, in order: a mesh's triples (mirrored_from == HIPR_SEGMENT_FROM_HOST) or the mirrored copy of the triples from
+    // `mirrored_from` on. Cleared with every build.
+    std::vector<HiprIndexSegment> m_index_log;
+    bool m_environment_set_since = false;      // set_environment after the last build: the environment's data is an upload's business
     static constexpr uint32_t NOT_BUILT = 0xFFFFFFFFu;
     std::vector<uint32_t> m_built_index;      // per instance: its index in the list the triangles and the trees were built over, NOT_BUILT for one created since
     uint32_t m_built_instance_count = 0;      // the length of that list

@@ -421,6 +421,59 @@ int hiprh_scene_adopt_edited_trees(void* scene, const HiprBvhNode* nodes, unsign
     try { return static_cast<SceneBuilder*>(scene)->adopt_edited_trees(nodes, node_count, order, order_count, deepest, slots, *wide8) ? 1 : 0; }
     catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_adopt_edited_trees: %s\n", e.what()); return -1; }
 }
+// SceneBuilder::add_mesh from plain arrays: `vertex_count` positions (3 floats each) and, each NULL or one per vertex, normals (3 floats), texcoords (2 floats),
+// tints (1 word) and emission (3 floats); `primitive_count` index triples. Returns the mesh index, -1 on error (a null array, an index past the vertices).
+int hiprh_scene_add_mesh(void* scene, const float* positions, const float* normals, const float* texcoords, const unsigned* tints, const float* emission, unsigned vertex_count, const unsigned* primitives,
+                         unsigned primitive_count) {
+    if (!scene || !positions || !primitives || !vertex_count || !primitive_count) return -1;
+    for (size_t k = 0; k < 3 * size_t(primitive_count); ++k)
+        if (primitives[k] >= vertex_count) return -1;
+    try {
+        MeshData mesh;
+        for (unsigned v = 0; v < vertex_count; ++v) {
+            mesh.positions.push_back(Vector3f(positions[3 * v], positions[3 * v + 1], positions[3 * v + 2]));
+            if (normals) mesh.normals.push_back(Vector3f(normals[3 * v], normals[3 * v + 1], normals[3 * v + 2]));
+            if (texcoords) mesh.texcoords.push_back(Vector2f{texcoords[2 * v], texcoords[2 * v + 1]});
+            if (tints) mesh.tints.push_back(tints[v]);
+            if (emission) mesh.emission.push_back(Vector3f(emission[3 * v], emission[3 * v + 1], emission[3 * v + 2]));
+        }
+        for (unsigned p = 0; p < primitive_count; ++p) mesh.primitives.push_back(Vector3ui{primitives[3 * p], primitives[3 * p + 1], primitives[3 * p + 2]});
+        return int(static_cast<SceneBuilder*>(scene)->add_mesh(std::move(mesh)));
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_add_mesh: %s\n", e.what()); return -1; }
+}
+// SceneBuilder::add_material. Returns the material index, -1 on error.
+int hiprh_scene_add_material(void* scene, const HiprMaterial* material) {
+    if (!scene || !material) return -1;
+    try { return int(static_cast<SceneBuilder*>(scene)->add_material(*material)); }
+    catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_add_material: %s\n", e.what()); return -1; }
+}
+// SceneBuilder::add_texture: `pixels` are width x height texels of `format` (HIPR_TEXEL_*), `byte_count` of them. Returns the texture index, -1 on error.
+int hiprh_scene_add_texture(void* scene, unsigned width, unsigned height, unsigned format, int is_sRGB, const unsigned char* pixels, unsigned long long byte_count, int repeat_u, int repeat_v,
+                            int linear_magnification, int linear_minification) {
+    if (!scene || !pixels || !width || !height) return -1;
+    const unsigned long long texel = format == HIPR_TEXEL_R8 ? 1u : (format == HIPR_TEXEL_RGBA8 || format == HIPR_TEXEL_R32F ? 4u : (format == HIPR_TEXEL_RGBA32F ? 16u : 0u));
+    if (!texel || byte_count != texel * width * height) return -1;
+    try {
+        ImageData image;
+        image.width = width; image.height = height; image.format = uint8_t(format); image.is_sRGB = is_sRGB != 0;
+        image.pixels.assign(pixels, pixels + byte_count);
+        return int(static_cast<SceneBuilder*>(scene)->add_texture(image, repeat_u != 0, repeat_v != 0, linear_magnification != 0, linear_minification != 0));
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_add_texture: %s\n", e.what()); return -1; }
+}
+// SceneBuilder::staged_scene_growth: what hipr_append_scene_pools (`out_growth`) and hipr_edit_scene_instances (`out_edits`, up to `capacity` entries written) take
+// for everything since the last build or adoption. The pointers of `out_growth` hold until the next call of this function on the calling thread and the next
+// hiprh_scene_add_* call on the scene. Returns the length of the edit list, -2 when it is not the device's to apply, -1 on error.
+int hiprh_scene_staged_growth(void* scene, HiprPoolGrowth* out_growth, HiprInstanceEdit* out_edits, unsigned capacity) {
+    if (!scene || !out_growth) return -1;
+    try {
+        static thread_local SceneBuilder::StagedGrowth staged;
+        std::vector<HiprInstanceEdit> edits;
+        if (!static_cast<const SceneBuilder*>(scene)->staged_scene_growth(staged, edits)) return -2;
+        *out_growth = staged.growth;
+        if (out_edits) std::copy(edits.begin(), edits.begin() + std::min<size_t>(capacity, edits.size()), out_edits);
+        return int(edits.size());
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_staged_growth: %s\n", e.what()); return -1; }
+}
 // out[0] = calls of hiprh_scene_adopt_trees that adopted, out[1] = calls that refused.
 int hiprh_scene_rebuild_counts(void* scene, unsigned* out2) {
     if (!scene || !out2) return -1;

@@ -209,6 +209,23 @@ class Context:
             out.update(nodes=nodes[:result.node_count], order=order[:result.triangle_count], slots=slots[:w.slot_count])
         return out
 
+    def append_scene_pools(self, growth, group=None) -> int:
+        """hipr_append_scene_pools: the resident pools grown at their tails, the step before edit_scene_instances when a model comes over a new mesh, material or
+        texture. `growth` is a capi.HiprPoolGrowth (Scene.staged_scene_growth makes it, with the edit list). Returns the status: a refusal leaves the scene as found
+        and is the caller's to answer with the full path. `group`: a HiprGroup handle, for hipr_group_append_scene_pools."""
+        call, handle = (self.lib.hipr_group_append_scene_pools, group) if group is not None else (self.lib.hipr_append_scene_pools, self.handle)
+        status = call(handle, C.byref(growth) if growth is not None else None)
+        counts = getattr(self, "_resident_counts", None)
+        if status == capi.HIPR_OK and group is None and counts is not None:
+            self._resident_counts = (counts[0], counts[1], counts[2] + growth.material_count)
+        return status
+
+    def append_times(self) -> dict:
+        """Milliseconds of the last append_scene_pools: the new allocations, the device-to-device copies of the resident parts, the tails with the mirror segments."""
+        out = (C.c_double * 3)()
+        self._check(self.lib.hipr_debug_append_times(self.handle, out), "hipr_debug_append_times")
+        return dict(allocation=out[0], resident_copies=out[1], tails=out[2])
+
     def rebuild_times(self) -> dict:
         """Milliseconds of the last rebuild_scene_trees: flatten order, BVH2, collapse (with the slots copied to the host), the new resident arrays, the outputs' read-back."""
         out = (C.c_double * 5)()
@@ -223,7 +240,19 @@ class Context:
 
     def read_scene_buffer(self, which: int) -> np.ndarray:
         """The scene array the device holds (hipr_debug_read_scene_buffer): capi.SCENE_BUFFER_TRIANGLES -> (triangles, 12) uint32 words, SCENE_BUFFER_WIDE8_SLOTS -> (slots, 16),
-        _TRACE_TRIANGLES -> (triangles, 12), _SHADE_TRIANGLES -> (triangles, 32), _TRIANGLE_CLASS -> (triangles,) uint8, _MATERIALS -> (materials, 16), _INSTANCES -> (instances, 20), SCENE_BUFFER_NODES -> (BVH2 nodes, 16)."""
+        _TRACE_TRIANGLES -> (triangles, 12), _SHADE_TRIANGLES -> (triangles, 32), _TRIANGLE_CLASS -> (triangles,) uint8, _MATERIALS -> (materials, 16), _INSTANCES -> (instances, 20), SCENE_BUFFER_NODES -> (BVH2 nodes, 16). The pools append_scene_pools grows, each as long as
+        the device's count says (hipr_debug_scene_buffer_bytes): _INDICES -> (words,) uint32, _GEOMETRY -> (vertices, 4), _TEXCOORDS -> (vertices, 2), _TINTS -> (vertices,),
+        _EMISSIONS -> (vertices, 3), _TEXTURES -> (textures, 6), all uint32 words, _TEXELS -> (bytes,) uint8; a pool the device does not hold has no rows."""
+        pools = {capi.SCENE_BUFFER_INDICES: (1, np.uint32), capi.SCENE_BUFFER_GEOMETRY: (4, np.uint32), capi.SCENE_BUFFER_TEXCOORDS: (2, np.uint32), capi.SCENE_BUFFER_TINTS: (1, np.uint32),
+                 capi.SCENE_BUFFER_EMISSIONS: (3, np.uint32), capi.SCENE_BUFFER_TEXTURES: (6, np.uint32), capi.SCENE_BUFFER_TEXELS: (1, np.uint8)}
+        if which in pools:
+            width, dtype = pools[which]
+            size = capi.c_u64()
+            self._check(self.lib.hipr_debug_scene_buffer_bytes(self.handle, int(which), C.byref(size)), "hipr_debug_scene_buffer_bytes")
+            rows = size.value // (width * np.dtype(dtype).itemsize)
+            out = np.zeros((rows, width) if width > 1 else (rows,), dtype)
+            self._check(self.lib.hipr_debug_read_scene_buffer(self.handle, int(which), C.c_void_p(out.ctypes.data if rows else C.addressof(size)), out.nbytes), "hipr_debug_read_scene_buffer")
+            return out
         # the device's counts, not the host scene's: a device rebuild changes the first two, and the description lags behind while edits or moves are staged in it
         node_count, slot_count = getattr(self, "_rebuilt_counts", None) or (self._scene.desc.node_count, self._scene.desc.wide8_slot_count)
         counts = getattr(self, "_resident_counts", None)      # absent on a context whose scene was uploaded past this wrapper: then the description is the device's

@@ -485,6 +485,55 @@ typedef struct HiprSceneEditResult {
 int hipr_edit_scene_instances(HiprContext* context, const HiprInstanceEdit* edits, uint32_t edit_count, uint32_t max_depth, HiprBvhNode* out_nodes /* may be NULL */,
                               uint32_t node_capacity, uint32_t* out_order /* may be NULL */, uint32_t order_capacity, HiprSlot8* out_slots /* may be NULL */,
                               uint32_t slot_capacity, HiprSceneEditResult* out);
+/* The pools of the RESIDENT scene grown at their tails (the reference loads a mesh into buffers of its own, OR/Renderer.cpp:92-136 load_mesh, and a texture or a
+ * material into its slot, :703-812 textures and upload_material, and leaves the rest of the scene where it lives): the step before hipr_edit_scene_instances when
+ * a model is created over a mesh, a material or a texture the device does not hold yet. Every pool of a HiprSceneDesc that the scene builder makes is
+ * append-only, so one description carries what is new in all of them:
+ *   vertices     `vertex_count` records appended to `geometry`. The optional per-vertex pools (`texcoords` 2 floats, `tints` 1 word, `emissions` 3 floats per
+ *                vertex) each come with the number of vertices their array covers: a pool the device HOLDS takes its tail, `vertex_count` entries, and that tail
+ *                is mandatory; a pool the device does not hold stays absent (NULL, 0) or comes WHOLE, resident + `vertex_count` entries, exactly as the scene
+ *                builder holds it -- what stands in it for the vertices of meshes without the attribute is the builder's business, not this header's;
+ *   indices      an ordered list of segments, which together make the tail of the index pool. A segment with `mirrored_from` == HIPR_SEGMENT_FROM_HOST takes the
+ *                next `index_count` words of `indices`; any other segment is a MIRROR: a copy of the `index_count / 3` triples from triple `mirrored_from` on of
+ *                the pool AS IT STANDS WHEN THE SEGMENT IS REACHED -- earlier segments of the same call included -- with the second and third corner exchanged
+ *                (the triples a mirroring instance is drawn from); it is made by a kernel (csrc/pool_growth.h) and transfers nothing. `index_count` of the
+ *                description is the sum of the host segments;
+ *   materials    `material_count` records appended to the material pool;
+ *   textures     `texture_count` records appended to `textures`, `texel_bytes` bytes appended to `texels`; the records carry ABSOLUTE texel offsets.
+ * Afterwards every pool holds, byte for byte, what SceneBuilder::add_mesh / add_material / add_texture, rebuild() and hipr_upload_scene on a fresh context put
+ * there, and the switches derived from the pools are derived again. No tree, triangle or instance is touched: no instance references a tail yet. Index VALUES are
+ * not checked here: hipr_edit_scene_instances checks every index of a new instance against the vertex pool -- the grown one -- before it loads the vertex. The call
+ * accepts the states hipr_edit_scene_instances accepts (ready, or awaiting a rebuild after a refit) and leaves the state it found. Checked on the host before the
+ * device is touched:
+ *   HIPR_ERROR_NOT_READY          no scene, or a scene a failed call left behind;
+ *   HIPR_ERROR_INVALID_ARGUMENT   a null description; a null array with a non-zero count; a segment whose `index_count` is no multiple of 3; host segments that do
+ *                                 not add up to `index_count`; a mirror range outside the pool as it stands at that segment; a resident attribute pool without its
+ *                                 tail, or an attribute array that is neither the tail nor the whole pool; a sum of counts that does not fit 32 bits (vertices,
+ *                                 index words, materials, textures); a texture whose extent, format or texel_offset hipr_validate_scene would refuse against the
+ *                                 GROWN texel pool; a material it would refuse against the GROWN texture count.
+ *   HIPR_ERROR_UNSUPPORTED        segments for a scene whose uploaded index pool is not one of whole triples.
+ * An empty description is HIPR_OK and changes nothing. A pool whose buffer has no room is allocated anew, all of them before anything is written: a failed
+ * allocation is HIPR_ERROR_OUT_OF_MEMORY and leaves the scene as found. A HIP failure after that leaves no scene, as with the other writers. */
+#define HIPR_SEGMENT_FROM_HOST 0xFFFFFFFFu
+typedef struct HiprIndexSegment {
+    uint32_t mirrored_from;              /* HIPR_SEGMENT_FROM_HOST, or the first triple of the range a mirror segment copies */
+    uint32_t index_count;                /* index words of the segment: whole triples */
+} HiprIndexSegment;
+typedef struct HiprPoolGrowth {
+    const HiprVertexGeometry* geometry;  /* vertex_count */
+    const float* texcoords;              /* 2 x texcoord_vertices */
+    const uint32_t* tints;               /* tint_vertices */
+    const float* emissions;              /* 3 x emission_vertices */
+    const uint32_t* indices;             /* index_count: the host segments' words, in order */
+    const HiprIndexSegment* segments;    /* segment_count */
+    const HiprMaterial* materials;       /* material_count */
+    const HiprTexture* textures;         /* texture_count */
+    const uint8_t* texels;               /* texel_bytes */
+    uint64_t texel_bytes;
+    uint32_t vertex_count, texcoord_vertices, tint_vertices, emission_vertices;
+    uint32_t index_count, segment_count, material_count, texture_count;
+} HiprPoolGrowth;
+int hipr_append_scene_pools(HiprContext* context, const HiprPoolGrowth* growth);
 int hipr_set_scene_state(HiprContext* context, const HiprSceneState* state);
 
 /* Entry points, numbered like OR/Types.h:33-44. set_backend() of the host renderer maps Backend values onto them
@@ -575,6 +624,7 @@ int hipr_group_rebuild_scene_trees(HiprGroup* group, uint32_t max_depth, HiprBvh
 int hipr_group_edit_scene_instances(HiprGroup* group, const HiprInstanceEdit* edits, uint32_t edit_count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity,
                                     uint32_t* out_order, uint32_t order_capacity, HiprSlot8* out_slots, uint32_t slot_capacity,
                                     HiprSceneEditResult* out);   /* every member edits; member 0's arrays are handed out; their results must agree */
+int hipr_group_append_scene_pools(HiprGroup* group, const HiprPoolGrowth* growth);   /* every member checks before any member writes */
 int hipr_group_update_scene_materials(HiprGroup* group, const HiprMaterialUpdate* materials, uint32_t material_count,
                                       const HiprInstanceMaterial* assignments, uint32_t assignment_count);   /* every member checks before any member writes */
 int hipr_group_set_scene_state(HiprGroup* group, const HiprSceneState* state);
@@ -723,10 +773,19 @@ int hipr_debug_trace_fused(HiprContext* context, const float* closest_rays, cons
 int hipr_debug_classify_hits(HiprContext* context, const float* hits_n4, uint32_t n, int coat_classes, uint32_t grid, uint32_t* out_order);
 /* The uploaded (or device-refitted, or material-updated) scene arrays as the device holds them: HiprTriangle[triangle_count], HiprSlot8[wide8_slot_count], the
  * trace records (48 bytes per triangle), the shading records (128 bytes per triangle), the class bytes of the listing pass (one per triangle),
- * HiprMaterial[material_count], HiprInstance[instance_count]. */
+ * HiprMaterial[material_count], HiprInstance[instance_count]; and the pools hipr_append_scene_pools grows, each exactly as long as its count: the index words,
+ * HiprVertexGeometry[vertex_count], the texcoords, tints and emissions (an absent pool reads as zero bytes), HiprTexture[texture_count], the texel bytes.
+ * hipr_debug_scene_buffer_bytes: the bytes a read of `which` takes. */
 enum { HIPR_SCENE_BUFFER_TRIANGLES = 0, HIPR_SCENE_BUFFER_WIDE8_SLOTS = 1, HIPR_SCENE_BUFFER_TRACE_TRIANGLES = 2, HIPR_SCENE_BUFFER_SHADE_TRIANGLES = 3,
-       HIPR_SCENE_BUFFER_TRIANGLE_CLASS = 4, HIPR_SCENE_BUFFER_MATERIALS = 5, HIPR_SCENE_BUFFER_INSTANCES = 6, HIPR_SCENE_BUFFER_NODES = 7 /* the BVH2 */ };
+       HIPR_SCENE_BUFFER_TRIANGLE_CLASS = 4, HIPR_SCENE_BUFFER_MATERIALS = 5, HIPR_SCENE_BUFFER_INSTANCES = 6, HIPR_SCENE_BUFFER_NODES = 7 /* the BVH2 */,
+       HIPR_SCENE_BUFFER_INDICES = 8, HIPR_SCENE_BUFFER_GEOMETRY = 9, HIPR_SCENE_BUFFER_TEXCOORDS = 10, HIPR_SCENE_BUFFER_TINTS = 11, HIPR_SCENE_BUFFER_EMISSIONS = 12,
+       HIPR_SCENE_BUFFER_TEXTURES = 13, HIPR_SCENE_BUFFER_TEXELS = 14 };
 int hipr_debug_read_scene_buffer(HiprContext* context, int which, void* out, uint64_t capacity_bytes);
+int hipr_debug_scene_buffer_bytes(HiprContext* context, int which, uint64_t* out_bytes);
+/* Milliseconds of the context's last successful hipr_append_scene_pools that did any work: the new allocations (the host's clock), the device-to-device copies of
+ * the resident parts into them and the host-to-device tails with the mirror segments (both between events on the stream: the call does not synchronise for them)
+ * (tools/pool_growth_probe.py). The old buffers are freed after the third. */
+int hipr_debug_append_times(HiprContext* context, double* out3_ms);
 /* Milliseconds of the context's last successful hipr_build_bvh2, which add up to the call: the argument checks (the pass over all corners for one that is not
  * finite), scratch allocation + upload, kernels, read-back (tools/device_build_probe.py). */
 int hipr_debug_build_times(HiprContext* context, double* out4_ms);
