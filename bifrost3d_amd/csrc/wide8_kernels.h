@@ -70,6 +70,26 @@ __device__ __forceinline__ void record_barycentrics(uint32_t flags, int which, f
     v = sv == 0u ? rw : (sv == 1u ? ru : rv);
 }
 
+// The analytic lights a closest-hit ray is tested against when it retires (LightSources.cu:31-70): sphere and spot lights with a radius above 0.
+HD bool is_analytic_light(uint32_t flags, float radius) {
+    const uint32_t type = flags & HIPR_LIGHT_TYPE_MASK;
+    return (type == HIPR_LIGHT_SPHERE || type == HIPR_LIGHT_SPOT) && radius > 0.0f;
+}
+// ... and the distance at which the ray meets one (NaN where it passes by).
+HD float analytic_light_distance(const HiprLight& l, f3 o, f3 d) {
+    return (l.flags & HIPR_LIGHT_TYPE_MASK) == HIPR_LIGHT_SPHERE ? ray_sphere(o, d, L3(l, 3), l.data[6]) : ray_disk(o, d, L3(l, 3), L3(l, 7), l.data[6]);
+}
+
+// What a lane is doing, in the one word `item`: the slot (24 bits) of the node it visits next, the same with the top bit set for a leaf record, or one of two values
+// for a lane without work -- its ray traversed and waiting to be retired, or no ray at all. The wave's votes are then single compares of a register with a small
+// constant: carried as three booleans, each vote cost a select and a compare, and each boolean three scalar mask operations per iteration to keep.
+constexpr uint32_t ITEM_RECORD = 0x80000000u, ITEM_FINISHED = 0xFFFFFFFEu, ITEM_IDLE = 0xFFFFFFFFu;
+__device__ __forceinline__ bool item_active(uint32_t item) { return item < ITEM_FINISHED; }
+__device__ __forceinline__ bool item_on_record(uint32_t item) { return int32_t(item) < int32_t(ITEM_FINISHED); }
+__device__ __forceinline__ bool item_on_node(uint32_t item) { return int32_t(item) >= 0; }
+// the slot's address: the 24-bit multiply drops the top bit, and its 30-bit product is an offset the loads take next to the scalar base
+__device__ __forceinline__ const uint4* item_slot(const uint4* slots, uint32_t item) { return (const uint4*)((const char*)slots + __umul24(item, 64u)); }
+
 // COVERAGE_R8: ... and every coverage texture is single-channel 8-bit, linear (kernels.h material_coverage_r8).
 // COVERAGE: the scene holds triangles that are not statically opaque (coverage textures, cut-outs, partial coverage): a shadow ray that hits one samples its material's
 // coverage. Scenes without any (the common case; decided at upload) run the instantiation without that code: it is a fifth of the kernel's instructions and, though never
@@ -92,7 +112,6 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
     uint32_t shard = (blockIdx.x & 7u) * (TRACE_SHARDS / 8u) + ((blockIdx.x >> 3) % (TRACE_SHARDS / 8u));     // blocks of one XCD start on neighbouring shards
     bool exhausted = false;
 
-    bool active = false, finished = false;     // finished: traversal done, result still in registers
     bool is_shadow = MODE == TRACE_SHADOW;     // per lane in the fused mode
     uint32_t ray_index = 0;
     f3 o = {0, 0, 0}, d = {0, 0, 1}, inv = {0, 0, 0}, ood = {0, 0, 0};
@@ -103,40 +122,34 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
     uint32_t pay_k = HIPR_NO_TRIANGLE;
     uint32_t octant = 0;
     uint32_t gx = 0, gy = 0;                   // the current group
-    uint32_t item = 0;                         // slot of the item this lane works on next
-    bool item_is_leaf = false;
+    uint32_t item = ITEM_IDLE;                 // what this lane works on next (ITEM_*); ITEM_FINISHED: traversal done, result still in registers
     int sp = 0;
     uint32_t nodes = 0, tris = 0, shadow_nodes = 0, shadow_tris = 0;
     uint32_t diag_node_iterations = 0, diag_node_lanes = 0, diag_triangle_iterations = 0, diag_triangle_lanes = 0, diag_busy_lanes = 0, diag_refills = 0;   // lane 0 only
     uint32_t diag_pushes = 0, diag_pushes_deep = 0;
     uint32_t diag_records_closest = 0, diag_records_shadow = 0, diag_records_mixed = 0;      // lane 0 only: record iterations of a fused launch by the rays on the records
 
-    for (;;) {
-        // ---- retire finished lanes (converged: every lane of the wave is here) --------------------------------------
-        if (finished) {
-            if (is_shadow) {
-                if constexpr (MODE != TRACE_CLOSEST) {
-                    float4 acc = radiance[pay_k];
-                    acc.x += pay_x; acc.y += pay_y; acc.z += pay_z;
-                    radiance[pay_k] = acc;
-                }
-            } else if constexpr (MODE != TRACE_SHADOW) {
-                for (uint32_t li = 0; li < sc.light_count; ++li) {   // analytic area lights, LightSources.cu:31-70
-                    const HiprLight l = load_light_uniform(sc.lights, li);
-                    const uint32_t type = l.flags & HIPR_LIGHT_TYPE_MASK;
-                    float t = -1e30f;
-                    if (type == HIPR_LIGHT_SPHERE) { if (!(l.data[6] > 0.0f)) continue; t = ray_sphere(o, d, L3(l, 3), l.data[6]); }
-                    else if (type == HIPR_LIGHT_SPOT) { if (!(l.data[6] > 0.0f)) continue; t = ray_disk(o, d, L3(l, 3), L3(l, 7), l.data[6]); }
-                    else continue;
-                    if (t > tmin && t < tmax) { tmax = t; pay_x = 0; pay_y = 0; pay_z = __uint_as_float(HIPR_HIT_LIGHT | li); }
-                }
-                hits[ray_index] = make_float4(tmax, pay_x, pay_y, pay_z);
-            }
-            finished = false;
+    // The analytic lights are the same for every ray of the launch: they are counted once. A scene's only one (the common case) is fetched at the top of a round with
+    // the round's other loads, so that no retiring ray waits for it on its own (the scalar registers of the loop below have no room to hold it throughout: with it
+    // there the product instantiations spill). Scenes with more of them walk the list as before; scenes with none skip the loop.
+    uint32_t analytic_lights = 0, held_light_index = 0;
+    if constexpr (MODE != TRACE_SHADOW) {
+        for (uint32_t li = 0; li < sc.light_count; ++li) {
+            const HiprLight l = load_light_uniform(sc.lights, li);
+            if (!is_analytic_light(l.flags, l.data[6])) continue;
+            if (analytic_lights++ == 0) held_light_index = li;
         }
-        // ---- refill idle lanes from the wave's private range -------------------------------------------------------
-        const unsigned long long idle = wave_ballot(!active);
+    }
+
+    for (;;) {
+        // ---- one ROUND (converged: every lane of the wave is here): finished lanes retire their ray, idle lanes take a new one from the wave's private range.
+        // Every address the round reads is known at its start -- the radiance slot of a retiring shadow ray, the queue entries of the new rays -- so all its
+        // loads are issued together and waited for once; the retire's sums and stores and the rays' set-up follow.
+        const bool finished = item == ITEM_FINISHED;
+        const unsigned long long idle = wave_ballot(!item_active(item));
         if (INSTRUMENT && lane == 0 && idle && !exhausted) ++diag_refills;
+        bool refill = false;                       // this lane takes entry `idx` of the launch
+        uint32_t idx = 0;
         if (idle && !exhausted) {
             while (chunk_next >= chunk_end && !exhausted) {
                 const uint32_t shard_begin = uint32_t((unsigned long long)n * shard / TRACE_SHARDS);
@@ -157,61 +170,103 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
                 }
             }
             if (chunk_next < chunk_end) {
-                const uint32_t idx = chunk_next + __popcll(idle & lt);
-                if (!active && idx < chunk_end) {
-                    bool dead = false;
-                    float4 ro, rdv;
-                    if (MODE == TRACE_FUSED) is_shadow = idx >= n_closest;
-                    const uint32_t entry = SORTED ? sorted[idx] : idx;
-                    if (is_shadow) {
-                        if constexpr (MODE != TRACE_CLOSEST) {
-                            const uint32_t si = entry - n_closest;
-                            ray_index = si;
-                            ro = q.o_tmax[si]; rdv = q.d_slot[si];
-                            const float4 rr = q.radiance[si];
-                            pay_x = rr.x; pay_y = rr.y; pay_z = rr.z;
-                            pay_k = __float_as_uint(rdv.w);
-                            tmin = 0.0f; tmax = ro.w;
-                        }
-                    } else if constexpr (MODE != TRACE_SHADOW) {
-                        ray_index = entry;
-                        const uint2 meta = in.meta[entry];
-                        dead = meta.x == HIPR_DEAD_SLOT;
-                        pay_k = meta.y;
-                        ro = in.o_tmin[entry]; rdv = in.d_pdf[entry];
-                        tmin = ro.w; tmax = __builtin_inff();
-                        pay_x = pay_y = 0.0f; pay_z = __uint_as_float(HIPR_HIT_MISS);
-                    }
-                    if (dead) hits[entry] = make_float4(0, 0, 0, __uint_as_float(HIPR_HIT_MISS));
-                    else {
-                        o = mk3(ro.x, ro.y, ro.z); d = mk3(rdv.x, rdv.y, rdv.z);
-                        const f3 sd = {fabsf(d.x) > 1e-20f ? d.x : copysignf(1e-20f, d.x), fabsf(d.y) > 1e-20f ? d.y : copysignf(1e-20f, d.y),
-                                       fabsf(d.z) > 1e-20f ? d.z : copysignf(1e-20f, d.z)};
-                        inv = {1.0f / sd.x, 1.0f / sd.y, 1.0f / sd.z};
-                        ood = o * inv;
-                        octant = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
-                        sp = 0;
-                        gx = 1u << 24; gy = 1u << 8;       // the root as a group of its own (one inner child in position 0 of base 0), already taken:
-                        item = 0u; item_is_leaf = false;   // the ray starts on the root node
-                        if (tree.slot_count == 0) finished = true;
-                        else active = true;
-                    }
-                }
+                idx = chunk_next + __popcll(idle & lt);
+                refill = !item_active(item) && idx < chunk_end;
                 chunk_next = min(chunk_next + uint32_t(__popcll(idle)), chunk_end);
             }
         }
-        unsigned long long busy = wave_ballot(active);
+        // the loads: nothing below reads what they return before all of them are under way
+        float4 acc = make_float4(0, 0, 0, 0);      // (left undefined for the lanes that load nothing, these records cost the loop its registers: scratch in every instantiation)
+        if constexpr (MODE != TRACE_CLOSEST) if (finished && is_shadow) acc = radiance[pay_k];
+        bool new_is_shadow = MODE == TRACE_SHADOW;
+        uint32_t entry = 0;
+        uint2 meta = make_uint2(0u, HIPR_NO_TRIANGLE);
+        float4 ro = make_float4(0, 0, 0, 0), rdv = ro, rr = ro;
+        if (refill) {
+            if (MODE == TRACE_FUSED) new_is_shadow = idx >= n_closest;
+            entry = SORTED ? sorted[idx] : idx;
+            if (new_is_shadow) {
+                if constexpr (MODE != TRACE_CLOSEST) {
+                    const uint32_t si = entry - n_closest;
+                    ro = q.o_tmax[si]; rdv = q.d_slot[si]; rr = q.radiance[si];
+                }
+            } else if constexpr (MODE != TRACE_SHADOW) {    // a dead entry's origin and direction are loaded (the entry is one of the launch's) and not used
+                meta = in.meta[entry]; ro = in.o_tmin[entry]; rdv = in.d_pdf[entry];
+            }
+        }
+        // ... the scalar ones last: their wait passes under the vector loads'. (Issued first, the light's twelve registers are live across the address arithmetic above,
+        // where the fused kernel has none to spare: it reuses two of them there and waits for the light before it issues the new rays' loads.)
+        HiprLight held_light;       // read only where it is loaded: by the waves that retire a closest-hit ray in a scene with one analytic light
+        if constexpr (MODE != TRACE_SHADOW) if (analytic_lights == 1 && wave_any(finished && !is_shadow)) held_light = load_light_uniform(sc.lights, held_light_index);
+        // retire
+        if (finished) {
+            if (is_shadow) {
+                if constexpr (MODE != TRACE_CLOSEST) {
+                    acc.x += pay_x; acc.y += pay_y; acc.z += pay_z;
+                    radiance[pay_k] = acc;
+                }
+            } else if constexpr (MODE != TRACE_SHADOW) {    // analytic area lights, LightSources.cu:31-70, in the order of the scene's list
+                if (analytic_lights == 1) {
+                    const float t = analytic_light_distance(held_light, o, d);
+                    if (t > tmin && t < tmax) { tmax = t; pay_x = 0; pay_y = 0; pay_z = __uint_as_float(HIPR_HIT_LIGHT | held_light_index); }
+                } else if (analytic_lights > 1) {
+                    for (uint32_t li = 0; li < sc.light_count; ++li) {
+                        const HiprLight l = load_light_uniform(sc.lights, li);
+                        if (!is_analytic_light(l.flags, l.data[6])) continue;
+                        const float t = analytic_light_distance(l, o, d);
+                        if (t > tmin && t < tmax) { tmax = t; pay_x = 0; pay_y = 0; pay_z = __uint_as_float(HIPR_HIT_LIGHT | li); }
+                    }
+                }
+                hits[ray_index] = make_float4(tmax, pay_x, pay_y, pay_z);
+            }
+            item = ITEM_IDLE;
+        }
+        // the new rays
+        if (refill) {
+            is_shadow = new_is_shadow;
+            bool dead = false;
+            if (new_is_shadow) {
+                ray_index = entry - n_closest;
+                pay_x = rr.x; pay_y = rr.y; pay_z = rr.z;
+                pay_k = __float_as_uint(rdv.w);
+                tmin = 0.0f; tmax = ro.w;
+            } else {
+                ray_index = entry;
+                uint32_t path_slot = meta.x;
+                asm volatile("" : "+v"(path_slot));      // opaque here: the compiler otherwise moves the `dead` compare up to the loads, and with it a wait for this one
+                dead = path_slot == HIPR_DEAD_SLOT;
+                pay_k = meta.y;
+                tmin = ro.w; tmax = __builtin_inff();
+                pay_x = pay_y = 0.0f; pay_z = __uint_as_float(HIPR_HIT_MISS);
+            }
+            if (dead) hits[entry] = make_float4(0, 0, 0, __uint_as_float(HIPR_HIT_MISS));
+            else {
+                // the canonical form of the two loaded bounds, once: the node block's max / min then take them as they are (the same values: only a signalling NaN changes, to the
+                // quiet one those operations make of it anyway)
+                tmin = __builtin_canonicalizef(tmin); tmax = __builtin_canonicalizef(tmax);
+                o = mk3(ro.x, ro.y, ro.z); d = mk3(rdv.x, rdv.y, rdv.z);
+                const f3 sd = {fabsf(d.x) > 1e-20f ? d.x : copysignf(1e-20f, d.x), fabsf(d.y) > 1e-20f ? d.y : copysignf(1e-20f, d.y),
+                               fabsf(d.z) > 1e-20f ? d.z : copysignf(1e-20f, d.z)};
+                inv = {1.0f / sd.x, 1.0f / sd.y, 1.0f / sd.z};
+                ood = o * inv;
+                octant = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
+                sp = 0;
+                gx = 1u << 24; gy = 1u << 8;       // the root as a group of its own (one inner child in position 0 of base 0), already taken:
+                item = tree.slot_count == 0 ? ITEM_FINISHED : 0u;      // the ray starts on the root node
+            }
+        }
+        unsigned long long busy = wave_ballot(item_active(item));
         if (!busy) {
-            if (wave_ballot(finished)) continue;
+            if (wave_ballot(item == ITEM_FINISHED)) continue;
             if (exhausted) break;
             continue;
         }
 
         // ---- traverse. Every iteration runs ONE of the two blocks -- the one more lanes are waiting for.
         do {
-            const bool leaf_mode = active & item_is_leaf;
-            const bool node_mode = active & !item_is_leaf;
-            const unsigned long long lmask = wave_ballot(leaf_mode), nmask = wave_ballot(node_mode);
+            const bool leaf_mode = item_on_record(item);
+            const bool node_mode = item_on_node(item);
+            const unsigned long long lmask = wave_ballot(leaf_mode), nmask = busy & ~lmask;     // busy: the vote that let the wave into this iteration
             bool advance = false;       // this lane finished its item in this iteration and takes the next one
             const unsigned long long shadows = INSTRUMENT && MODE == TRACE_FUSED ? wave_ballot(leaf_mode && is_shadow) : 0ull;
             if (INSTRUMENT && lane == 0) {
@@ -225,7 +280,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
             }
             if (__popcll(lmask) * HIPR_WIDE8_LEAF_VOTE_DEN > __popcll(nmask) * HIPR_WIDE8_LEAF_VOTE_NUM) {
                 if (leaf_mode) {
-                    const uint4* rp = tree.slots + 4 * size_t(item);
+                    const uint4* rp = item_slot(tree.slots, item);
                     const uint4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3];
                     const f3 a = mk3(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z));
                     const f3 e1 = mk3(__uint_as_float(r0.w), __uint_as_float(r1.x), __uint_as_float(r1.y));
@@ -296,7 +351,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
                     }
                 }
             } else if (node_mode) {
-                const uint4* np = tree.slots + 4 * size_t(item);
+                const uint4* np = item_slot(tree.slots, item);
                 const uint4 w0 = np[0], w1 = np[1], w2 = np[2], w3 = np[3];
                 if (INSTRUMENT) { nodes += is_shadow ? 0u : 1u; shadow_nodes += is_shadow ? 1u : 0u; }
                 advance = true;
@@ -368,14 +423,13 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
                 }
                 const bool done = (gy & 0xFFu) == 0u;
                 const uint32_t p = uint32_t(__builtin_ctz(gy | 0x100u));      // the low byte is non-zero unless the ray is done
-                gy = done ? gy : (gy & (gy - 1u));
+                gy &= gy - 1u;                                                // (of a ray that is done this clears a bit nobody reads again)
                 const uint32_t position = (p ^ octant) & 7u;
-                item_is_leaf = !((gy >> (8u + position)) & 1u);
-                item = (gx & 0xFFFFFFu) + uint32_t(__popc((gx >> 24) & ((1u << position) - 1u)));
-                active = !done;
-                finished = done;
+                const uint32_t slot = (gx & 0xFFFFFFu) + uint32_t(__popc(__builtin_amdgcn_ubfe(gx, 24u, position)));      // base + the valid children in lower positions
+                const uint32_t record = ((gy >> position) & 0x100u) ^ 0x100u;                                            // the child is not an inner node
+                item = done ? ITEM_FINISHED : (slot | record << 23);          // 0x100 << 23: ITEM_RECORD
             }
-            busy = wave_ballot(active);
+            busy = wave_ballot(item_active(item));
         } while (busy && (exhausted || __popcll(busy) >= refill_below));
     }
 
