@@ -38,8 +38,8 @@
 #include <vector>
 
 extern "C" int hipr_internal_check_material_update(HiprContext* context, const HiprMaterialUpdate* materials, uint32_t material_count, const HiprInstanceMaterial* assignments,
-                                                   uint32_t assignment_count);   // hiprenderer.hip: the refusals of hipr_update_scene_materials on their own
-extern "C" int hipr_internal_check_pool_growth(HiprContext* context, const HiprPoolGrowth* growth);   // hiprenderer.hip: every refusal of hipr_append_scene_pools short of a failed allocation
+                                                   uint32_t assignment_count);   // scene.hip: the refusals of hipr_update_scene_materials on their own
+extern "C" int hipr_internal_check_pool_growth(HiprContext* context, const HiprPoolGrowth* growth);   // scene.hip: every refusal of hipr_append_scene_pools short of a failed allocation
 extern "C" void hipr_internal_set_last_error(const char* message);   // hiprenderer.hip: hipr_last_error() is per thread; a worker's message is handed to the caller's
 
 namespace {

@@ -167,6 +167,9 @@ HD void camera_ray(const HiprCameraState& cam, uint32_t x, uint32_t y, uint32_t 
     direction = normalize(mk3(r[0] * v.x + r[1] * v.y + r[2] * v.z, r[3] * v.x + r[4] * v.y + r[5] * v.z, r[6] * v.x + r[7] * v.y + r[8] * v.z));
 }
 
+// HIPR_SHADE_TU: named for its first user, set by every unit that includes this header for its types, device functions and kernel templates only (shade.hip,
+// scene.hip, the experiments and the host builds of the tests, which is why the name stays). The kernels that are no templates are then left out: hiprenderer.hip
+// compiles and launches them, and it alone.
 #ifndef HIPR_SHADE_TU
 // Camera rays of one wavefront's path slots into its queue entries [0, n_paths): the slots are dealt to the wavefronts in groups of 64, round robin
 // (wavefront `phase` of `wavefronts`).
@@ -246,7 +249,7 @@ HD void triangle_hit_values(const TriangleTest& r, f3 e2, float& t, float& u, fl
 // (1 - s, s - r, r); the other half is (a, c, d) with (1 - r, s, r - s). A box side or a wall costs one test instead of two.
 // Item layout (4 float4): {v0, e1.x} {e1.yz, e2.xy} {e2.z, instance, primitive A, flags} {triangle A, triangle B, primitive B, selectors};
 // selectors: 2 bits each, which corner weight of the half is the triangle's u (weight of its vertex 1) and v (vertex 2): u of A,
-// v of A, u of B, v of B. The host builds the items at upload (hiprenderer.hip build_trace_items); the oracle restates the pairing.
+// v of A, u of B, v of B. The host builds the items at upload (scene.hip build_trace_items); the oracle restates the pairing.
 constexpr uint32_t HIPR_ITEM_QUAD = 2u;   // next to HIPR_TRIANGLE_OPAQUE in the item's flags
 struct ItemTest { float det, un, vn, us, vs; f3 q; };
 HD bool item_inside(f3 v0, f3 e1, f3 e2, bool quad, f3 o, f3 d, ItemTest& r) {
@@ -1073,25 +1076,8 @@ HD void build_shade_triangle_record(const DeviceScene& sc, uint32_t t, float4* o
 //   quad 3..5: object-to-world transformed vertex normal i (not normalised: sum(w_i * M n_i) = M sum(w_i * n_i), so the
 //              interpolated normal is the one the per-hit transform gives), .w = bits(material index | instance id | mesh flags)
 //   quad 6   : uv0.xy, uv1.xy       quad 7: uv2.xy, bits(tint0), bits(tint1)
-// Per-vertex emission (rare) still goes through the instance.
+// Per-vertex emission (rare) still goes through the instance. The kernels that write the records, and the trace kernels' vertex + edges form, are triangle_records.h's.
 // ---------------------------------------------------------------------------------------------
-// What the trace kernels read per triangle: the vertex and the two edges the test works on (the edges rounded once, here, as
-// the oracle rounds them), ids and flags where the uploaded triangle has them.
-__global__ __launch_bounds__(256) void k_build_trace_triangles(const float4* __restrict__ triangles, uint32_t triangle_count, float4* __restrict__ out) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= triangle_count) return;
-    const float4 a = triangles[3 * size_t(t)], b = triangles[3 * size_t(t) + 1], c = triangles[3 * size_t(t) + 2];
-    const f3 v0 = mk3(a.x, a.y, a.z), e1 = mk3(a.w, b.x, b.y) - v0, e2 = mk3(b.z, b.w, c.x) - v0;
-    out[3 * size_t(t)] = make_float4(v0.x, v0.y, v0.z, e1.x);
-    out[3 * size_t(t) + 1] = make_float4(e1.y, e1.z, e2.x, e2.y);
-    out[3 * size_t(t) + 2] = make_float4(e2.z, c.y, c.z, c.w);
-}
-
-__global__ __launch_bounds__(256) void k_build_shade_triangles(DeviceScene sc, float4* out) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= sc.triangle_count) return;
-    build_shade_triangle_record(sc, t, out);
-}
 
 // ---------------------------------------------------------------------------------------------
 // K5c: the order in which the shade kernel takes the rays of a bounce. A wave of k_shade runs the surface code -- attributes, material, three RIS light

@@ -1,4 +1,4 @@
-// launch.h -- host-side launch interface between hiprenderer.hip and shade.hip.
+// launch.h -- host-side launch interface between hiprenderer.hip and shade.hip (context.h brings it to scene.hip with the context, which names its shade unit).
 #pragma once
 
 #include "kernels.h"

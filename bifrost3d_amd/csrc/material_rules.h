@@ -3,7 +3,7 @@
 //
 // The yardstick of a material edit on the device is BYTE EQUALITY with a fresh upload of the edited scene, so both sides run these statements: IEEE f32
 // arithmetic in a fixed order, floorf / fabsf exact on either side, and ONE division, float(value) / 255.0f, which is correctly rounded on the host and in the
-// device library's main unit (csrc/hiprenderer.hip: correctly rounded division, -ffp-contract=off). NEVER include this header in the fast-math shade unit
+// device library's scene unit (csrc/scene.hip, built with the traversal unit's flags: correctly rounded division, -ffp-contract=off). NEVER include this header in the fast-math shade unit
 // (csrc/shade.hip): its division there is a reciprocal and a product, and a texel at the threshold would flag a triangle differently.
 //
 // Plain C++ for the host's compiler, __host__ __device__ under hipcc; no HIP header is needed.

@@ -129,7 +129,7 @@ def main():
     p.add_argument("--out", default=str(ROOT / "profiles" / "device_build_vs_host.txt"))
     p.add_argument("--library", nargs="+", default=[], metavar="LABEL=PATH",
                    help="other builds of libhiprenderer.so whose hipr_build_bvh2 is timed as in (a) and appended, e.g. the cut between the two regimes: "
-                        "make -C bifrost3d_amd csrc/hiprenderer.o HIPFLAGS='<the Makefile's HIPFLAGS> -DHIPR_BUILD_SHORT_RANGE=32', link it as the Makefile links the product, "
+                        "make -C bifrost3d_amd csrc/scene.o HIPFLAGS='<the Makefile's HIPFLAGS> -DHIPR_BUILD_SHORT_RANGE=32', link it as the Makefile links the product, "
                         "and pass --library 32=<that library>")
     args = p.parse_args()
     lines = ["Output of tools/device_build_probe.py; anything after the line 'Reading' at the end is commentary written by hand.", "",

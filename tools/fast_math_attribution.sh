@@ -31,7 +31,7 @@ done
 wait
 for tag in "${!V[@]}"; do
     fast=$tmp/$tag.o; exact=csrc/shade_exact.o; case $tag in V_*) fast=csrc/shade.o; exact=$tmp/$tag.o;; esac
-    hipcc --offload-arch=gfx950 -shared -fPIC -o csrc/libhiprenderer_$tag.so csrc/hiprenderer.o $fast $exact csrc/camera_effects.o csrc/denoiser.o csrc/group.o -ldl -lpthread
+    hipcc --offload-arch=gfx950 -shared -fPIC -o csrc/libhiprenderer_$tag.so csrc/hiprenderer.o csrc/scene.o $fast $exact csrc/camera_effects.o csrc/denoiser.o csrc/group.o -ldl -lpthread
     echo built csrc/libhiprenderer_$tag.so
 done
 rm -rf $tmp
