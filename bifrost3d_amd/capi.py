@@ -125,6 +125,10 @@ class HiprWide8BuildResult(C.Structure):
     _fields_ = [("slot_count", c_u32), ("height", c_u32), ("grid_min", c_f * 3), ("grid_cell", c_f * 3), ("node_count", c_u32), ("leaf_count", c_u32), ("paired_leaves", c_u32)]
 
 
+class HiprWide4BuildResult(C.Structure):
+    _fields_ = [("node_count", c_u32), ("stack_entries", c_u32)]
+
+
 class HiprSceneRebuildResult(C.Structure):
     _fields_ = [("node_count", c_u32), ("deepest", c_u32), ("wide8", HiprWide8BuildResult), ("half_area", C.c_double)]
 
@@ -213,7 +217,7 @@ assert C.sizeof(HiprIndexSegment) == 8 and C.sizeof(HiprPoolGrowth) == 112
 # Every symbol include/hiprenderer_c.h declares; tests check the library exports all of them.
 C_ABI_SYMBOLS = (
     "hipr_create", "hipr_destroy", "hipr_last_error", "hipr_device_count", "hipr_set_stream",
-    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_build_bvh2", "hipr_group_build_bvh2", "hipr_debug_build_times", "hipr_build_wide8", "hipr_group_build_wide8", "hipr_debug_collapse_times", "hipr_rebuild_scene_trees", "hipr_group_rebuild_scene_trees", "hipr_edit_scene_instances", "hipr_group_edit_scene_instances", "hipr_append_scene_pools", "hipr_group_append_scene_pools", "hipr_debug_scene_buffer_bytes", "hipr_debug_append_times", "hipr_debug_rebuild_times", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
+    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_build_bvh2", "hipr_group_build_bvh2", "hipr_debug_build_times", "hipr_build_wide8", "hipr_group_build_wide8", "hipr_debug_collapse_times", "hipr_build_wide4", "hipr_group_build_wide4", "hipr_debug_collapse4_times", "hipr_rebuild_scene_trees", "hipr_group_rebuild_scene_trees", "hipr_edit_scene_instances", "hipr_group_edit_scene_instances", "hipr_append_scene_pools", "hipr_group_append_scene_pools", "hipr_debug_scene_buffer_bytes", "hipr_debug_append_times", "hipr_debug_rebuild_times", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
     "hipr_set_frame", "hipr_owned_pixel_count",
     "hipr_render_pass", "hipr_set_samples_per_pass", "hipr_trace_pass", "hipr_accumulate_samples", "hipr_read_accumulation", "hipr_scatter_tiles", "hipr_synchronize", "hipr_get_counters",
     "hipr_device_malloc", "hipr_device_free", "hipr_device_memset", "hipr_copy_to_host", "hipr_present_flipped",
@@ -268,6 +272,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.hipr_build_wide8.argtypes = [vp, C.POINTER(HiprBvhNode), c_u32, C.POINTER(HiprTriangle), C.POINTER(c_u32), c_u32, vp, c_u32, C.POINTER(HiprWide8BuildResult)]
     lib.hipr_group_build_wide8.argtypes = [vp, C.POINTER(HiprBvhNode), c_u32, C.POINTER(HiprTriangle), C.POINTER(c_u32), c_u32, vp, c_u32, C.POINTER(HiprWide8BuildResult)]
     lib.hipr_debug_collapse_times.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.hipr_build_wide4.argtypes = [vp, C.POINTER(HiprBvhNode), c_u32, c_u32, vp, c_u32, C.POINTER(HiprWide4BuildResult)]
+    lib.hipr_group_build_wide4.argtypes = [vp, C.POINTER(HiprBvhNode), c_u32, c_u32, vp, c_u32, C.POINTER(HiprWide4BuildResult)]
+    lib.hipr_debug_collapse4_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.hipr_rebuild_scene_trees.argtypes = [vp, c_u32, vp, c_u32, vp, vp, c_u32, C.POINTER(HiprSceneRebuildResult)]
     lib.hipr_group_rebuild_scene_trees.argtypes = [vp, c_u32, vp, c_u32, vp, vp, c_u32, C.POINTER(HiprSceneRebuildResult)]
     lib.hipr_edit_scene_instances.argtypes = [vp, C.POINTER(HiprInstanceEdit), c_u32, c_u32, vp, c_u32, vp, c_u32, vp, c_u32, C.POINTER(HiprSceneEditResult)]

@@ -263,6 +263,13 @@ struct CollapseScratch : Scratch<CollapseBuffers> {
     double validate_ms = 0.0, upload_ms = 0.0, kernel_ms = 0.0, readback_ms = 0.0;      // of the last collapse
 };
 
+// The device scratch of hipr_build_wide4 (wide4_build.h): the input (64 B per BVH2 node and its place in the level lists), a word of binary_need per node, and per wide
+// node -- at most one per BVH2 node -- 20 B of frontier and layout words and the node twice, in frontier order and in place.
+struct Collapse4Buffers { DeviceBuffer nodes, level_nodes, need, wide_root, wide_budget, made, wide_size, wide_stack, wide_at, out, status; };
+struct Collapse4Scratch : Scratch<Collapse4Buffers> {
+    double validate_ms = 0.0, upload_ms = 0.0, kernel_ms = 0.0, readback_ms = 0.0;      // of the last collapse
+};
+
 // What hipr_rebuild_scene_trees needs beside the two builds' scratch (scene_rebuild.h): 9 B per triangle and a word per instance and BVH2 node. The
 // flat triangle array itself is BuildScratch::triangles, where hipr_build_bvh2 keeps its input.
 struct RebuildBuffers {
@@ -362,6 +369,7 @@ struct Context {
     DeviceBuffer debug_a, debug_b, debug_c;
     BuildScratch build;                 // hipr_build_bvh2; nothing of the resident scene
     CollapseScratch collapse;           // hipr_build_wide8; likewise
+    Collapse4Scratch collapse4;         // hipr_build_wide4; likewise
     RebuildScratch rebuild;             // hipr_rebuild_scene_trees, which also runs over the two above
 
     hipEvent_t next_event() {

@@ -356,6 +356,12 @@ int hipr_group_build_wide8(HiprGroup* g, const HiprBvhNode* nodes, uint32_t node
     return hipr_build_wide8(g->members[0].context, nodes, node_count, triangles, order, triangle_count, out_slots, slot_capacity, out);
 }
 
+// The collapse of hipr_build_wide4 on member 0, likewise.
+int hipr_group_build_wide4(HiprGroup* g, const HiprBvhNode* nodes, uint32_t node_count, uint32_t triangle_count, HiprWideNode* out_nodes, uint32_t node_capacity, HiprWide4BuildResult* out) {
+    if (!g || g->members.empty()) return HIPR_ERROR_INVALID_ARGUMENT;
+    return hipr_build_wide4(g->members[0].context, nodes, node_count, triangle_count, out_nodes, node_capacity, out);
+}
+
 // hipr_rebuild_scene_trees on every member: the same kernels over the same arrays give the same trees, so member 0's arrays are the ones handed out and the
 // others rebuild without a read-back. A member that refuses leaves its scene as it was; the members then disagree, and the caller uploads.
 int hipr_group_rebuild_scene_trees(HiprGroup* g, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_order, HiprSlot8* out_slots, uint32_t slot_capacity,

@@ -12,6 +12,7 @@
 #include "material_update.h"
 #include "bvh2_build.h"
 #include "wide8_build.h"
+#include "wide4_build.h"
 #include "scene_rebuild.h"
 #include "instance_edit.h"
 #include "pool_growth.h"
@@ -1382,6 +1383,98 @@ int hipr_build_wide8(HiprContext* c, const HiprBvhNode* nodes, uint32_t node_cou
 int hipr_debug_collapse_times(HiprContext* c, double* out4_ms) {
     if (!c || !out4_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_collapse_times: null argument");
     out4_ms[0] = c->collapse.validate_ms; out4_ms[1] = c->collapse.upload_ms; out4_ms[2] = c->collapse.kernel_ms; out4_ms[3] = c->collapse.readback_ms;
+    return HIPR_OK;
+}
+
+// The compressed 4-wide tree of host/BvhBuilder.cpp's WideCollapse collapsed from a BVH2 by the kernels of wide4_build.h. Nothing of the resident scene is read or
+// written; the outputs are written only once the whole collapse has succeeded.
+int hipr_build_wide4(HiprContext* c, const HiprBvhNode* nodes, uint32_t node_count, uint32_t triangle_count, HiprWideNode* out_nodes, uint32_t node_capacity, HiprWide4BuildResult* out) {
+    const char* who = "hipr_build_wide4";
+    if (int st = check_context(c)) return st;
+    const auto t_validate = std::chrono::steady_clock::now();
+    if (!nodes || !node_count || !out_nodes || !out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null argument or no nodes", who);
+    if (node_count > BUILD_MAX_TRIANGLES) return fail(HIPR_ERROR_UNSUPPORTED, "%s: %u nodes, a leaf reference holds %u", who, node_count, BUILD_MAX_TRIANGLES);
+    W8Input input;
+    char reason[256] = "";
+    if (w8_check_input(nodes, node_count, nullptr, triangle_count, input, reason, sizeof(reason)) == W8_INPUT_INVALID) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: %s", who, reason);
+    const uint32_t reachable = uint32_t(input.level_nodes.size()), bvh_levels = uint32_t(input.level_first.size()) - 1u;
+    Collapse4Scratch& b = c->collapse4;
+    const ScratchGuard guard{b};
+    hipStream_t stream = c->stream;
+    c->break_chain(stream);
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t N = node_count, capacity = reachable;      // every wide node is rooted at a distinct reachable BVH2 node
+    if (b.need.resize(N * 4) | b.wide_root.resize(capacity * 4) | b.wide_budget.resize(capacity * 4) | b.made.resize(capacity * sizeof(HiprWideNode)) | b.wide_size.resize(capacity * 4) |
+        b.wide_stack.resize(capacity * 4) | b.wide_at.resize(capacity * 4) | b.status.resize(W4_STATUS_WORDS * 4))
+        return HIPR_ERROR_OUT_OF_MEMORY;
+    if (int st = b.nodes.upload(nodes, N * sizeof(HiprBvhNode), stream)) return st;
+    if (int st = b.level_nodes.upload(input.level_nodes.data(), size_t(reachable) * 4, stream)) return st;
+    HIP_TRY(hipMemsetAsync(b.status.ptr, 0, W4_STATUS_WORDS * 4, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const auto t1 = std::chrono::steady_clock::now();
+
+    W4State S = {};
+    S.nodes = b.nodes.as<HiprBvhNode>(); S.node_count = node_count; S.level_nodes = b.level_nodes.as<uint32_t>(); S.need = b.need.as<uint32_t>();
+    S.wide_capacity = uint32_t(capacity); S.wide_root = b.wide_root.as<uint32_t>(); S.wide_budget = b.wide_budget.as<uint32_t>(); S.made = b.made.as<HiprWideNode>();
+    S.wide_size = b.wide_size.as<uint32_t>(); S.wide_stack = b.wide_stack.as<uint32_t>(); S.wide_at = b.wide_at.as<uint32_t>(); S.status = b.status.as<uint32_t>();
+    const dim3 block(W8_BLOCK);
+    auto blocks_for = [](uint32_t threads) { return dim3((threads + W8_BLOCK - 1) / W8_BLOCK); };
+    // 2: binary_need, deepest level first, and the finite check; the host chooses the root's budget
+    for (uint32_t l = bvh_levels; l-- > 0;) {
+        const uint32_t first = input.level_first[l], count = input.level_first[l + 1] - first;
+        hipLaunchKernelGGL(k_w4_need, blocks_for(count), block, 0, stream, S, first, count);
+    }
+    uint32_t root_need = 0, not_finite = 0;
+    HIP_TRY(hipMemcpyAsync(&root_need, S.need, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&not_finite, S.status + W4_STATUS_NOT_FINITE, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (not_finite) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: a child box is not finite", who);
+    if (root_need == 0 || root_need > W8_MAX_LEVELS) return fail(HIPR_ERROR_HIP, "%s: the root needs %u entries on %u levels", who, root_need, bvh_levels);
+    const uint32_t root_entry[2] = {0u, root_need <= W4_SMALL_BUDGET ? W4_SMALL_BUDGET : W4_LARGE_BUDGET};
+    HIP_TRY(hipMemcpyAsync(S.wide_root, &root_entry[0], 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(S.wide_budget, &root_entry[1], 4, hipMemcpyHostToDevice, stream));
+    // 3: the wide nodes, level by level
+    std::vector<uint32_t> wide_first, wide_count;
+    uint32_t status[W4_STATUS_WORDS] = {};
+    for (uint32_t level = 0, first = 0, count = 1; count; ++level) {
+        if (level >= W4_MAX_WIDE_LEVELS || size_t(first) + count > capacity) return fail(HIPR_ERROR_HIP, "%s: the collapse left its bounds at wide level %u (%u nodes from %u, room for %zu)", who, level, count, first, capacity);
+        hipLaunchKernelGGL(k_w4_collapse, blocks_for(count), block, 0, stream, S, first, count, level);
+        HIP_TRY(hipMemcpyAsync(status, S.status, (W4_STATUS_LEVELS + level + 2) * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (status[W4_STATUS_OVERFLOW]) return fail(HIPR_ERROR_HIP, "%s: more wide nodes than the %u BVH2 nodes reached", who, reachable);
+        wide_first.push_back(first); wide_count.push_back(count);
+        first += count;
+        count = status[W4_STATUS_LEVELS + level + 1];
+    }
+    const uint32_t wide_total = wide_first.back() + wide_count.back(), wide_levels = uint32_t(wide_first.size());
+    if (wide_total > node_capacity) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: the tree needs %u nodes, room for %u", who, wide_total, node_capacity);
+    if (b.out.resize(size_t(wide_total) * sizeof(HiprWideNode))) return HIPR_ERROR_OUT_OF_MEMORY;
+    S.out = b.out.as<HiprWideNode>();
+    // 4: sizes and stack needs, bottom-up; 5: positions and the nodes in place, top-down
+    for (uint32_t l = wide_levels; l-- > 0;) hipLaunchKernelGGL(k_w4_size, blocks_for(wide_count[l]), block, 0, stream, S, wide_first[l], wide_count[l]);
+    HIP_TRY(hipMemsetAsync(S.wide_at, 0, 4, stream));
+    for (uint32_t l = 0; l < wide_levels; ++l) hipLaunchKernelGGL(k_w4_place_emit, blocks_for(wide_count[l]), block, 0, stream, S, wide_first[l], wide_count[l]);
+    uint32_t root_words[2] = {0u, 0u};
+    HIP_TRY(hipMemcpyAsync(&root_words[0], S.wide_size, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&root_words[1], S.wide_stack, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (root_words[0] != wide_total) return fail(HIPR_ERROR_HIP, "%s: %u nodes below the root, %u made", who, root_words[0], wide_total);
+    const auto t2 = std::chrono::steady_clock::now();
+    HIP_TRY(hipMemcpyAsync(out_nodes, S.out, size_t(wide_total) * sizeof(HiprWideNode), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    out->node_count = wide_total; out->stack_entries = root_words[1];
+    const auto t3 = std::chrono::steady_clock::now();
+    b.validate_ms = ms(t_validate, t0); b.upload_ms = ms(t0, t1); b.kernel_ms = ms(t1, t2); b.readback_ms = ms(t2, t3);
+    if (std::getenv("HIPR_BVH_TIMING"))
+        fprintf(stderr, "[hipr] %s: %u BVH2 nodes on %u levels, need %u, %u wide nodes on %u levels, %u stack entries: index walk %.3f ms, allocation + upload %.3f ms, kernels %.3f ms, read-back %.3f ms\n", who,
+                node_count, bvh_levels, root_need, wide_total, wide_levels, root_words[1], b.validate_ms, b.upload_ms, b.kernel_ms, b.readback_ms);
+    return HIPR_OK;
+}
+
+int hipr_debug_collapse4_times(HiprContext* c, double* out4_ms) {
+    if (!c || !out4_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_collapse4_times: null argument");
+    out4_ms[0] = c->collapse4.validate_ms; out4_ms[1] = c->collapse4.upload_ms; out4_ms[2] = c->collapse4.kernel_ms; out4_ms[3] = c->collapse4.readback_ms;
     return HIPR_OK;
 }
 

@@ -80,6 +80,14 @@ def load_host_library() -> C.CDLL:
     lib.hiprh_bvh_wide8_counts.argtypes = [vp, C.POINTER(C.c_uint)]; lib.hiprh_bvh_wide8_counts.restype = None
     lib.hiprh_wide8_build_on_device.argtypes = [vp, vp, C.c_uint, vp, vp, C.c_uint, C.POINTER(C.c_int)]
     lib.hiprh_wide8_build_on_device.restype = vp
+    lib.hiprh_wide4_build_on_device.argtypes = [vp, vp, C.c_uint, C.c_uint, C.POINTER(C.c_int)]
+    lib.hiprh_wide4_build_on_device.restype = vp
+    lib.hiprh_wide4_collapse.argtypes = [vp, C.c_uint, C.c_uint, C.POINTER(C.c_uint)]
+    lib.hiprh_wide4_collapse.restype = vp
+    lib.hiprh_wide4_quantise_children.argtypes = [vp, vp, C.c_uint, vp]; lib.hiprh_wide4_quantise_children.restype = None
+    lib.hiprh_scene_wide4_collapse_counts.argtypes = [vp, C.POINTER(C.c_uint)]
+    lib.hiprh_scene_set_test_wide4_source.argtypes = [vp, C.c_int]
+    lib.hiprh_scene_use_device_wide4.argtypes = [vp, vp]
     lib.hiprh_pmjbn_samples.argtypes = [C.POINTER(C.c_float), C.c_uint, C.c_uint]
     lib.hiprh_bvh_destroy.argtypes = [vp]
     lib.hiprh_renderer_bench.argtypes = [C.c_char_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_double)]
@@ -118,7 +126,7 @@ class Scene:
     def __init__(self, name: str, diffuse_only: bool = False, param0: int = 0, param1: int = 0, environment: bool = False, coat: bool = False, spot: bool = False, textured: bool = False,
                  device_builder=None):
         """`device_builder`: a renderer.Context whose device builds the BVH2 of this scene (hipr_build_bvh2) and collapses it to the 8-wide tree (hipr_build_wide8, unless
-        HIPR_DEVICE_COLLAPSE=0) -- the scene is rebuilt through it at once, and so is every later rebuild; where the device declines a stage, the host builds the same
+        HIPR_DEVICE_COLLAPSE=0) and, with HIPR_DEVICE_COLLAPSE4=1, to the 4-wide tree (hipr_build_wide4) -- the scene is rebuilt through it at once, and so is every later rebuild; where the device declines a stage, the host builds the same
         tree and build_counts() / collapse_counts() say so."""
         self.lib = load_host_library()
         if name.startswith("file:"):    # a model file set up the way SimpleViewer sets up its command-line scene
@@ -152,6 +160,22 @@ class Scene:
         out = (C.c_uint * 3)()
         self.lib.hiprh_scene_build_counts(self.handle, out)
         return dict(device_builds=int(out[0]), declined_builds=int(out[1]), longest_median_range=int(out[2]))
+
+    def wide4_collapse_counts(self) -> dict:
+        """Tree builds, adoptions included, whose 4-wide tree the device collapsed, and those where it was asked and the host collapsed instead."""
+        out = (C.c_uint * 2)()
+        self.lib.hiprh_scene_wide4_collapse_counts(self.handle, out)
+        return dict(device_collapses=int(out[0]), declined_collapses=int(out[1]))
+
+    def use_device_wide4(self, context) -> None:
+        """Installs (None: removes) the context's hipr_build_wide4 as the 4-wide collapse of this scene's later builds and adoptions, whatever HIPR_DEVICE_COLLAPSE4 says.
+        Nothing is rebuilt here. Context.close() takes it out again, with the other sources."""
+        if context is not None and not context.handle:
+            raise capi.HiprError("use_device_wide4: the context is closed")
+        if context is not None:
+            context.remember_built_scene(self)
+        if self.lib.hiprh_scene_use_device_wide4(self.handle, context.handle if context is not None else None) < 0:
+            raise capi.HiprError("hiprh_scene_use_device_wide4 failed")
 
     def collapse_counts(self) -> dict:
         """Builds whose 8-wide tree the device collapsed, and builds where it was asked and the host collapsed instead."""

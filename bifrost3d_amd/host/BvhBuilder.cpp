@@ -412,19 +412,27 @@ static void quantise_children(const Box* boxes, size_t count, HiprWideNode& w) {
 // Collapse to compressed 4-wide nodes: a node adopts the children of its largest inner child until it has four, then the
 // child boxes are quantised to 8 bits per bound on the node's own grid, rounding outwards.
 // ---------------------------------------------------------------------------------------------
+// The BVH2 a collapse reads: a vector's, or a caller's array (collapse_wide4_on_host), without a copy.
+struct NodeSpan {
+    const HiprBvhNode* first; size_t count;
+    size_t size() const { return count; }
+    const HiprBvhNode& operator[](size_t i) const { return first[i]; }
+};
 struct WideCollapse {
-    const std::vector<HiprBvhNode>& nodes;
+    const NodeSpan nodes;
     std::vector<HiprWideNode> wide;
     std::vector<uint32_t> binary_need;   // stack entries the BVH2 subtree of a node needs when nothing below it is widened
     std::vector<uint32_t> subtree_size;  // BVH2 nodes in the subtree of a node
     const uint32_t* need = nullptr;      // = binary_need.data() of the collapse that computed it (shared with the subtree collapses)
 
     // Subtrees collapsed as tasks of their own (the top collapse of a parallel run): BVH2 subtrees of at most `subtree_cutoff` nodes.
-    struct Task { uint32_t node_index, budget; std::vector<HiprWideNode> wide; uint32_t stack_need = 0; };
+    struct Task { uint32_t node_index, budget; std::vector<HiprWideNode> wide; uint32_t stack_need = 0, did_not_fit = 0; };
     std::vector<Task> tasks;
     uint32_t subtree_cutoff = 0;
+    uint32_t did_not_fit = 0;            // nodes that stopped adopting because one more child would not have fitted the budget (what the tests of the budget ask for)
     static bool is_task(int32_t ref) { return ref >= SUBTREE_MARK && ref != int32_t(HIPR_WIDE_EMPTY); }
-    explicit WideCollapse(const std::vector<HiprBvhNode>& n, const uint32_t* shared_need = nullptr) : nodes(n), need(shared_need) {}
+    explicit WideCollapse(const std::vector<HiprBvhNode>& n) : nodes{n.data(), n.size()} {}
+    explicit WideCollapse(NodeSpan n, const uint32_t* shared_need = nullptr) : nodes(n), need(shared_need) {}
 
     // Nodes are stored parent before children: one sweep from the last node to the first sees every child done.
     uint32_t compute_binary_need() {
@@ -472,7 +480,7 @@ struct WideCollapse {
             bool fits = held + std::max(need_of(inner.child[0]), need_of(inner.child[1])) <= budget;
             for (size_t i = 0; i < children.size() && fits; ++i)
                 if (int(i) != widest) fits = held + need_of(children[i].ref) <= budget;
-            if (!fits) break;
+            if (!fits) { ++did_not_fit; break; }
             children[widest] = child_of(inner, 0);
             children.insert(children.begin() + widest + 1, child_of(inner, 1));
         }
@@ -539,6 +547,7 @@ struct WideCollapse {
                 sub.wide.reserve(subtree_size[task.node_index] / 2 + 1);
                 sub.collapse(task.node_index, task.budget, task.stack_need);
                 task.wide = std::move(sub.wide);
+                task.did_not_fit = sub.did_not_fit;
             }
         };
         Failure failure;
@@ -547,6 +556,7 @@ struct WideCollapse {
         failure.guard(worker);
         for (std::thread& w : workers) w.join();
         failure.rethrow();
+        for (const Task& task : tasks) did_not_fit += task.did_not_fit;
 
         std::vector<HiprWideNode> top = std::move(wide);
         std::vector<uint32_t> top_at(top.size()), task_at(tasks.size());
@@ -654,6 +664,55 @@ static bool wide8_from_source(const Wide8Source& source, Wide8SourceReport* repo
 
 BvhBuildResult build_bvh(const std::vector<HiprTriangle>& triangles, uint32_t max_depth, const Bvh2Source& source, Bvh2SourceReport* report, const Wide8Source& wide8_source,
                          Wide8SourceReport* wide8_report) {
+    return build_bvh(triangles, max_depth, source, report, wide8_source, wide8_report, Wide4Source(), nullptr);
+}
+
+// The default follows profiles/wide4_collapse_vs_host.txt: not measured yet, so the device's 4-wide collapse is opt-in.
+static constexpr bool DEVICE_COLLAPSE4_DEFAULT = false;
+bool device_collapse4_wanted() {
+    const char* v = std::getenv("HIPR_DEVICE_COLLAPSE4");
+    return v ? std::atoi(v) != 0 : DEVICE_COLLAPSE4_DEFAULT;
+}
+
+// The 4-wide collapse from the caller's source. false: the host's WideCollapse serves.
+static bool wide4_from_source(const Wide4Source& source, Wide4SourceReport* report, const std::vector<HiprBvhNode>& nodes, uint32_t triangle_count, std::vector<HiprWideNode>& wide, uint32_t& stack_entries) {
+    if (!source || nodes.empty()) return false;
+    const auto t_start = std::chrono::steady_clock::now();
+    // every wide node is rooted at a distinct BVH2 node; the pages of this room are touched only where the source writes
+    const uint32_t capacity = uint32_t(nodes.size());
+    struct Room { HiprWideNode* nodes; ~Room() { std::free(nodes); } } room = {static_cast<HiprWideNode*>(std::malloc(size_t(capacity) * sizeof(HiprWideNode)))};
+    HiprWide4BuildResult built = {};
+    const int status = room.nodes ? source.build(source.context, nodes.data(), uint32_t(nodes.size()), triangle_count, room.nodes, capacity, &built) : HIPR_ERROR_OUT_OF_MEMORY;
+    const bool used = status == 0 && built.node_count >= 1 && built.node_count <= capacity;
+    if (used) { wide.assign(room.nodes, room.nodes + built.node_count); stack_entries = built.stack_entries; }
+    const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+    if (report) { report->asked = true; report->status = status; report->used = used; report->seconds = seconds; }
+    if (std::getenv("HIPR_BVH_TIMING")) fprintf(stderr, "[hipr] build_bvh: 4-wide source %s (status %d) after %.3f s\n", used ? "used" : "not used, the host collapses", status, seconds);
+    return used;
+}
+
+void quantise_wide4_children(const float* boxes_kx6, uint32_t count, HiprWideNode& out) {
+    Box boxes[4];
+    count = std::min(count, 4u);
+    for (uint32_t k = 0; k < count; ++k)
+        for (int a = 0; a < 3; ++a) { boxes[k].lo[a] = boxes_kx6[6 * k + a]; boxes[k].hi[a] = boxes_kx6[6 * k + 3 + a]; }
+    out = {};
+    quantise_children(boxes, count, out);
+}
+
+std::vector<HiprWideNode> collapse_wide4_on_host(const HiprBvhNode* nodes, size_t node_count, unsigned threads, uint32_t& stack_entries, uint32_t* did_not_fit, uint32_t* budget_out) {
+    stack_entries = 0;
+    if (!nodes || !node_count) return {};
+    WideCollapse collapse(NodeSpan{nodes, node_count});
+    const uint32_t budget = collapse.compute_binary_need() <= 32u ? 32u : 0xFFFFu;
+    collapse.run(budget, std::max(threads, 1u), stack_entries);
+    if (did_not_fit) *did_not_fit = collapse.did_not_fit;
+    if (budget_out) *budget_out = budget;
+    return std::move(collapse.wide);
+}
+
+BvhBuildResult build_bvh(const std::vector<HiprTriangle>& triangles, uint32_t max_depth, const Bvh2Source& source, Bvh2SourceReport* report, const Wide8Source& wide8_source,
+                         Wide8SourceReport* wide8_report, const Wide4Source& wide4_source, Wide4SourceReport* wide4_report) {
     BvhBuildResult result;
     const uint32_t n = uint32_t(triangles.size());
     result.max_depth = 0;
@@ -698,12 +757,14 @@ BvhBuildResult build_bvh(const std::vector<HiprTriangle>& triangles, uint32_t ma
     const auto t_built = std::chrono::steady_clock::now();
 
     result.nodes = std::move(b.nodes);
-    WideCollapse collapse(result.nodes);
-    // Keep the worst case within the 32 entry LDS stack of the traversal kernels whenever the BVH2 itself allows it; deeper
-    // trees are collapsed freely and traversed by the kernels that back the LDS stack with scratch memory.
-    const uint32_t budget = collapse.compute_binary_need() <= 32u ? 32u : 0xFFFFu;
-    collapse.run(budget, b.threads, result.wide_stack_entries);
-    result.wide_nodes = std::move(collapse.wide);
+    if (!wide4_from_source(wide4_source, wide4_report, result.nodes, n, result.wide_nodes, result.wide_stack_entries)) {
+        WideCollapse collapse(result.nodes);
+        // Keep the worst case within the 32 entry LDS stack of the traversal kernels whenever the BVH2 itself allows it; deeper
+        // trees are collapsed freely and traversed by the kernels that back the LDS stack with scratch memory.
+        const uint32_t budget = collapse.compute_binary_need() <= 32u ? 32u : 0xFFFFu;
+        collapse.run(budget, b.threads, result.wide_stack_entries);
+        result.wide_nodes = std::move(collapse.wide);
+    }
     result.max_depth = b.deepest + 1;   // stack entries needed is bounded by the node depth; keep one spare
     const auto t_wide = std::chrono::steady_clock::now();
     if (!wide8_from_source(wide8_source, wide8_report, result.nodes, triangles, result.order, result.wide8))

@@ -57,8 +57,26 @@ struct Wide8SourceReport {
     double seconds = 0.0;        // ... and how long it took
 };
 
+// The 4-wide collapse supplied by the caller in place of the host's WideCollapse: hipr_build_wide4's signature behind a context pointer (csrc/wide4_build.h collapses to
+// the host's tree byte for byte on the device). Returns HIPR_OK, or the status of a refusal or an error, with the outputs untouched.
+struct Wide4Source {
+    int (*build)(void* context, const HiprBvhNode* nodes, uint32_t node_count, uint32_t triangle_count, HiprWideNode* out_nodes, uint32_t node_capacity, HiprWide4BuildResult* out) = nullptr;
+    void* context = nullptr;
+    explicit operator bool() const { return build != nullptr; }
+};
+// What became of it in one build_bvh. A source that declines or fails is always followed by the host's collapse, silently: the tree is the same either way.
+struct Wide4SourceReport {
+    bool asked = false;          // the source was called
+    bool used = false;           // ... and its tree is the result's
+    int status = 0;              // what it returned
+    double seconds = 0.0;        // ... and how long it took
+};
+
 // Whether a consumer that installs a Bvh2Source installs the Wide8Source with it: HIPR_DEVICE_COLLAPSE (0: the host collapses), else DEVICE_COLLAPSE_DEFAULT.
 bool device_collapse_wanted();
+
+// Whether a consumer that installs a Bvh2Source installs the Wide4Source with it: HIPR_DEVICE_COLLAPSE4 (0: the host collapses, 1: the device), else DEVICE_COLLAPSE4_DEFAULT.
+bool device_collapse4_wanted();
 
 // `max_depth`: the deepest leaf the builder may produce (root = 1). 62 fits the 64 entry LDS stack.
 BvhBuildResult build_bvh(const std::vector<HiprTriangle>& world_triangles, uint32_t max_depth = 62);
@@ -67,6 +85,15 @@ BvhBuildResult build_bvh(const std::vector<HiprTriangle>& world_triangles, uint3
 // ... and the 8-wide collapse from `wide8_source` when one is installed.
 BvhBuildResult build_bvh(const std::vector<HiprTriangle>& world_triangles, uint32_t max_depth, const Bvh2Source& source, Bvh2SourceReport* report, const Wide8Source& wide8_source,
                          Wide8SourceReport* wide8_report);
+// ... and the 4-wide collapse from `wide4_source` when one is installed.
+BvhBuildResult build_bvh(const std::vector<HiprTriangle>& world_triangles, uint32_t max_depth, const Bvh2Source& source, Bvh2SourceReport* report, const Wide8Source& wide8_source,
+                         Wide8SourceReport* wide8_report, const Wide4Source& wide4_source, Wide4SourceReport* wide4_report);
+// The host's 4-wide collapse alone over a caller's BVH2 (node 0 the root, parents before children, as every BVH2 of this library is), on `threads` threads, with the
+// root's budget chosen as build_bvh chooses it: the result does not depend on `threads`. `did_not_fit` (may be null): nodes that stopped adopting because one more child
+// would not have fitted the budget; `budget` (may be null): the root's.
+std::vector<HiprWideNode> collapse_wide4_on_host(const HiprBvhNode* nodes, size_t node_count, unsigned threads, uint32_t& stack_entries, uint32_t* did_not_fit, uint32_t* budget);
+// The quantisation of one 4-wide node's child boxes (tests of csrc/wide4_build.h's restatement): boxes = lo xyz, hi xyz per child, count <= 4; `out` is zeroed first.
+void quantise_wide4_children(const float* boxes_kx6, uint32_t count, HiprWideNode& out);
 
 // Transform-only update: refits every box of `bvh` (BVH2 child boxes and the wide nodes' quantised child boxes) to `triangles`, which are
 // the build's triangles in leaf order with new positions; topology and triangle order are kept. Returns bvh_child_area() of the result, or a negative value when

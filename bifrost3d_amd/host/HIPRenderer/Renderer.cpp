@@ -304,6 +304,14 @@ struct Renderer::Implementation {
         return HIPR_ERROR_NOT_READY;
     }
 
+    // hipr_group_build_wide4 as their 4-wide collapse (SceneBuilder::set_wide4_source), by the same rule.
+    static int build_wide4_on_a_live_group(void* implementation, const HiprBvhNode* nodes, uint32_t node_count, uint32_t triangle_count, HiprWideNode* out_nodes, uint32_t node_capacity,
+                                           HiprWide4BuildResult* out) {
+        for (CameraState& c : static_cast<Implementation*>(implementation)->per_camera_state)
+            if (c.context) return hipr_group_build_wide4(c.context, nodes, node_count, triangle_count, out_nodes, node_capacity, out);
+        return HIPR_ERROR_NOT_READY;
+    }
+
     void rebuild_scene() {
         retire_scene();
         scene.reset(new SceneBuilder());
@@ -314,6 +322,8 @@ struct Renderer::Implementation {
             scene->set_bvh2_source(Bvh2Source{build_bvh2_on_a_live_group, this});
             // ... and the 8-wide collapse with it (csrc/wide8_build.h, likewise byte for byte) unless HIPR_DEVICE_COLLAPSE=0 keeps it on the host.
             if (device_collapse_wanted()) scene->set_wide8_source(Wide8Source{build_wide8_on_a_live_group, this});
+            // ... and the 4-wide collapse (csrc/wide4_build.h, byte for byte as well) where HIPR_DEVICE_COLLAPSE4 or its default asks for it.
+            if (device_collapse4_wanted()) scene->set_wide4_source(Wide4Source{build_wide4_on_a_live_group, this});
         }
         flatten_bifrost_scene(*scene, scene_mesh_index);
         for (CameraState& c : per_camera_state) c.scene_uploaded = false;

@@ -271,7 +271,9 @@ void SceneBuilder::finalize(uint32_t bvh_max_depth) {
 // The trees over the triangles in flatten order, the triangles in the trees' order and the description: what finalize() does after its flatten, and what
 // adopt_rebuilt_trees() does with sources that hand back the trees it was given.
 void SceneBuilder::build_trees_over(const std::vector<HiprTriangle>& world, const Bvh2Source& bvh2_source, Bvh2SourceReport& report, const Wide8Source& wide8_source, Wide8SourceReport& wide8_report) {
-    m_bvh = build_bvh(world, m_bvh_max_depth_limit, bvh2_source, &report, wide8_source, &wide8_report);
+    Wide4SourceReport wide4_report;
+    m_bvh = build_bvh(world, m_bvh_max_depth_limit, bvh2_source, &report, wide8_source, &wide8_report, m_wide4_source, &wide4_report);
+    if (wide4_report.used) ++m_wide4_collapse_counts.device_collapses; else if (wide4_report.asked) ++m_wide4_collapse_counts.declined_collapses;
     m_built_bvh_area = bvh_child_area(m_bvh);
     m_triangles.resize(world.size());
     for (size_t k = 0; k < world.size(); ++k) m_triangles[k] = world[m_bvh.order[k]];

@@ -99,6 +99,12 @@ public:
     void set_wide8_source(const Wide8Source& source) { m_wide8_source = source; }
     struct CollapseCounts { unsigned device_collapses = 0, declined_collapses = 0; };
     CollapseCounts collapse_counts() const { return m_collapse_counts; }
+    // The same for the 4-wide collapse (hipr_build_wide4 behind a context: the same nodes, collapsed on the device), which finalize() / rebuild() AND both adoptions
+    // below ask -- the adoptions are handed a BVH2 and an 8-wide tree, and the 4-wide collapse is what is left to do. A source that declines or fails is followed by the
+    // host's collapse, silently. Wide4Source() removes it. wide4_collapse_counts(): tree builds (adoptions included) whose 4-wide tree the source made, and those where
+    // it was asked and the host collapsed.
+    void set_wide4_source(const Wide4Source& source) { m_wide4_source = source; }
+    CollapseCounts wide4_collapse_counts() const { return m_wide4_collapse_counts; }
     // The trees a device rebuild of the resident scene made (hipr_rebuild_scene_trees: the same trees, built from the triangles the device holds) taken over in place of
     // a rebuild(): everything staged is applied to the builder's own triangles WITHOUT a refit and without a flatten, they are brought into flatten order through the
     // old order and into the new one through `order` (order[k] = the flatten position of the triangle at place k: BvhBuildResult::order), the BVH2 (`nodes`,
@@ -168,7 +174,7 @@ private:
     // them with the second and third corner exchanged, so that the world-space corners wind the way the reference's transformed geometric normal points
     // (rtTransformNormal through the inverse transpose, ORS/MonteCarlo.cu:147) and every consumer of the triple order sees the same triangle.
     uint32_t index_offset_for(uint32_t mesh, const float* object_to_world);
-    void build_trees_over(const std::vector<HiprTriangle>& world, const Bvh2Source& bvh2_source, Bvh2SourceReport& report, const Wide8Source& wide8_source, Wide8SourceReport& wide8_report);
+    void build_trees_over(const std::vector<HiprTriangle>& world, const Bvh2Source& bvh2_source, Bvh2SourceReport& report, const Wide8Source& wide8_source, Wide8SourceReport& wide8_report);      // the 4-wide collapse from m_wide4_source, counted
     void move_triangles(const std::vector<bool>& moved);
     void flatten_instance(uint32_t instance, std::vector<HiprTriangle>& world);
     bool trees_fit(uint32_t triangle_count, const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, const HiprSlot8* slots, const HiprWide8BuildResult& wide8) const;
@@ -205,6 +211,8 @@ private:
     BvhBuildResult m_bvh;
     Bvh2Source m_bvh2_source;
     Wide8Source m_wide8_source;
+    Wide4Source m_wide4_source;
+    CollapseCounts m_wide4_collapse_counts;
     BuildCounts m_build_counts;
     CollapseCounts m_collapse_counts;
     double m_built_bvh_area = 0.0;

@@ -486,8 +486,10 @@ static int build_bvh2_on_context(void* context, const HiprTriangle* triangles, u
                                  uint32_t* out_order, uint32_t* out_deepest);
 static int build_wide8_on_context(void* context, const HiprBvhNode* nodes, uint32_t node_count, const HiprTriangle* triangles, const uint32_t* order, uint32_t triangle_count, HiprSlot8* out_slots,
                                   uint32_t slot_capacity, HiprWide8BuildResult* out);
-// Installs hipr_build_bvh2 of `context` (NULL: removes it) as the BVH2 stage of the scene's builds and hipr_build_wide8 as their 8-wide collapse (unless
-// device_collapse_wanted() says the host collapses), and, with a context, rebuilds the scene through them. A decline
+static int build_wide4_on_context(void* context, const HiprBvhNode* nodes, uint32_t node_count, uint32_t triangle_count, HiprWideNode* out_nodes, uint32_t node_capacity, HiprWide4BuildResult* out);
+// Installs hipr_build_bvh2 of `context` (NULL: removes it) as the BVH2 stage of the scene's builds, hipr_build_wide8 as their 8-wide collapse (unless
+// device_collapse_wanted() says the host collapses) and hipr_build_wide4 as their 4-wide collapse (where device_collapse4_wanted() says so; the adoptions ask
+// it too), and, with a context, rebuilds the scene through them. A decline
 // or a device error is silent here: the host's stage builds the same tree. Returns 1 when the device built the BVH2, 0 when the host did, -1 on error.
 int hiprh_scene_use_device_builder(void* scene, void* context) {
     if (!scene) return -1;
@@ -495,6 +497,7 @@ int hiprh_scene_use_device_builder(void* scene, void* context) {
     try {
         sb->set_bvh2_source(context ? Bvh2Source{build_bvh2_on_context, context} : Bvh2Source());
         sb->set_wide8_source(context && device_collapse_wanted() ? Wide8Source{build_wide8_on_context, context} : Wide8Source());
+        sb->set_wide4_source(context && device_collapse4_wanted() ? Wide4Source{build_wide4_on_context, context} : Wide4Source());
         if (!context) return 0;
         const unsigned before = sb->build_counts().device_builds;
         sb->rebuild();
@@ -514,6 +517,37 @@ int hiprh_scene_collapse_counts(void* scene, unsigned* out2) {
     if (!scene || !out2) return -1;
     const SceneBuilder* sb = static_cast<SceneBuilder*>(scene);
     out2[0] = sb->collapse_counts().device_collapses; out2[1] = sb->collapse_counts().declined_collapses;
+    return 0;
+}
+
+// The same for the 4-wide tree, adoptions included (SceneBuilder::wide4_collapse_counts).
+int hiprh_scene_wide4_collapse_counts(void* scene, unsigned* out2) {
+    if (!scene || !out2) return -1;
+    const SceneBuilder* sb = static_cast<SceneBuilder*>(scene);
+    out2[0] = sb->wide4_collapse_counts().device_collapses; out2[1] = sb->wide4_collapse_counts().declined_collapses;
+    return 0;
+}
+// Tests of the source wiring without a device: a Wide4Source that hands back the host's own collapse (mode 1), one that declines with its outputs untouched (mode 2);
+// mode 0 removes the source. Nothing is rebuilt here.
+static int host_collapse_as_wide4_source(void*, const HiprBvhNode* nodes, uint32_t node_count, uint32_t, HiprWideNode* out_nodes, uint32_t node_capacity, HiprWide4BuildResult* out) {
+    uint32_t stack_entries = 0;
+    const std::vector<HiprWideNode> wide = collapse_wide4_on_host(nodes, node_count, 1u, stack_entries, nullptr, nullptr);
+    if (wide.size() > node_capacity) return HIPR_ERROR_INVALID_ARGUMENT;
+    std::copy(wide.begin(), wide.end(), out_nodes);
+    out->node_count = uint32_t(wide.size()); out->stack_entries = stack_entries;
+    return HIPR_OK;
+}
+static int declining_wide4_source(void*, const HiprBvhNode*, uint32_t, uint32_t, HiprWideNode*, uint32_t, HiprWide4BuildResult*) { return HIPR_ERROR_UNSUPPORTED; }
+int hiprh_scene_set_test_wide4_source(void* scene, int mode) {
+    if (!scene || mode < 0 || mode > 2) return -1;
+    static_cast<SceneBuilder*>(scene)->set_wide4_source(mode == 1 ? Wide4Source{host_collapse_as_wide4_source, nullptr} : (mode == 2 ? Wide4Source{declining_wide4_source, nullptr} : Wide4Source()));
+    return 0;
+}
+// hipr_build_wide4 of `context` (NULL: removes it) as the 4-wide collapse of the scene's later builds and adoptions, whatever device_collapse4_wanted() says
+// (tools/wide4_collapse_probe.py measures both ways; tests install it). Nothing is rebuilt here.
+int hiprh_scene_use_device_wide4(void* scene, void* context) {
+    if (!scene) return -1;
+    static_cast<SceneBuilder*>(scene)->set_wide4_source(context ? Wide4Source{build_wide4_on_context, context} : Wide4Source());
     return 0;
 }
 
@@ -634,6 +668,47 @@ void* hiprh_wide8_build_on_device(void* context, const HiprBvhNode* nodes, unsig
         w.node_count = built.node_count; w.leaf_count = built.leaf_count; w.paired_leaves = built.paired_leaves;
         return h;
     } catch (const std::exception& e) { fprintf(stderr, "hiprh_wide8_build_on_device: %s\n", e.what()); delete h; return nullptr; }
+}
+// hipr_build_wide4 as a Wide4Source.
+static int build_wide4_on_context(void* context, const HiprBvhNode* nodes, uint32_t node_count, uint32_t triangle_count, HiprWideNode* out_nodes, uint32_t node_capacity, HiprWide4BuildResult* out) {
+    return hipr_build_wide4(static_cast<HiprContext*>(context), nodes, node_count, triangle_count, out_nodes, node_capacity, out);
+}
+// A handle whose 4-wide tree `context` collapsed on the device (hipr_build_wide4) from the caller's BVH2; the handle's other trees are empty. NULL when the device
+// refuses or fails -- this entry does not fall back: the status is in *out_status and the message in hipr_last_error().
+void* hiprh_wide4_build_on_device(void* context, const HiprBvhNode* nodes, unsigned node_count, unsigned triangle_count, int* out_status) {
+    BvhHandle* h = nullptr;
+    if (out_status) *out_status = HIPR_ERROR_INVALID_ARGUMENT;
+    if (!context) return nullptr;
+    try {
+        std::vector<HiprWideNode> wide(std::max(node_count, 1u));
+        HiprWide4BuildResult built = {};
+        const int status = hipr_build_wide4(static_cast<HiprContext*>(context), nodes, node_count, triangle_count, wide.data(), uint32_t(wide.size()), &built);
+        if (out_status) *out_status = status;
+        if (status != HIPR_OK) return nullptr;
+        h = new BvhHandle();
+        wide.resize(built.node_count);
+        h->result.wide_nodes = std::move(wide);
+        h->result.wide_stack_entries = built.stack_entries;
+        return h;
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_wide4_build_on_device: %s\n", e.what()); delete h; return nullptr; }
+}
+// A handle whose 4-wide tree the HOST's WideCollapse made from the caller's BVH2 (node 0 the root, parents before children) on `threads` threads, the root's budget
+// chosen as build_bvh chooses it; the handle's other trees are empty. out2 (may be NULL): nodes that stopped adopting because one more child did not fit, the budget.
+void* hiprh_wide4_collapse(const HiprBvhNode* nodes, unsigned node_count, unsigned threads, unsigned* out2) {
+    BvhHandle* h = nullptr;
+    if (!nodes || !node_count) return nullptr;
+    try {
+        h = new BvhHandle();
+        uint32_t did_not_fit = 0, budget = 0;
+        h->result.wide_nodes = collapse_wide4_on_host(nodes, node_count, threads, h->result.wide_stack_entries, &did_not_fit, &budget);
+        if (out2) { out2[0] = did_not_fit; out2[1] = budget; }
+        return h;
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_wide4_collapse: %s\n", e.what()); delete h; return nullptr; }
+}
+// quantise_children of host/BvhBuilder.cpp over `groups` child-box groups (tests of csrc/wide4_build.h's exponent search): boxes = 4 x (lo xyz, hi xyz) floats per
+// group, counts = children per group (1 .. 4).
+void hiprh_wide4_quantise_children(const float* boxes, const unsigned* counts, unsigned groups, HiprWideNode* out) {
+    for (unsigned g = 0; g < groups; ++g) HIPRenderer::quantise_wide4_children(boxes + 24 * size_t(g), counts[g], out[g]);
 }
 // The handle's 8-wide tree: slots, height, grid (min xyz, cell xyz) and counters (nodes, leaf records, records of two triangles).
 const HiprSlot8* hiprh_bvh_wide8_slots(void* h) { return static_cast<BvhHandle*>(h)->result.wide8.slots.data(); }

@@ -150,6 +150,26 @@ class Context:
         return status, slots[:r.slot_count], dict(slot_count=r.slot_count, height=r.height, grid_min=np.array(r.grid_min[:], np.float32), grid_cell=np.array(r.grid_cell[:], np.float32),
                                                   node_count=r.node_count, leaf_count=r.leaf_count, paired_leaves=r.paired_leaves)
 
+    def build_wide4(self, nodes: np.ndarray, triangle_count: int, wide: np.ndarray | None = None, result: np.ndarray | None = None, group=None):
+        """hipr_build_wide4: the host's compressed 4-wide tree over the BVH2 `nodes` ((n, 16) uint32 words of HiprBvhNode) whose leaves reference `triangle_count`
+        triangles, collapsed on the device. Returns (status, wide nodes (node_count, 16) uint32, result): `result` a dict of node_count and stack_entries. `wide`
+        ((capacity, 16) uint32) and `result` (2 uint32 words of HiprWide4BuildResult) may be the caller's; on a status other than HIPR_OK both are returned whole as the
+        call left them. `group`: a HiprGroup handle, for hipr_group_build_wide4."""
+        nodes = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 16)
+        wide = np.zeros((max(len(nodes), 1), 16), np.uint32) if wide is None else wide
+        raw = np.zeros(2, np.uint32) if result is None else result
+        call, handle = (self.lib.hipr_group_build_wide4, group) if group is not None else (self.lib.hipr_build_wide4, self.handle)
+        status = call(handle, C.cast(nodes.ctypes.data, C.POINTER(capi.HiprBvhNode)), len(nodes), triangle_count, wide.ctypes.data, len(wide), C.cast(raw.ctypes.data, C.POINTER(capi.HiprWide4BuildResult)))
+        if status != capi.HIPR_OK:
+            return status, wide, raw
+        return status, wide[:int(raw[0])], dict(node_count=int(raw[0]), stack_entries=int(raw[1]))
+
+    def collapse4_times(self) -> dict:
+        """Milliseconds of the last build_wide4: the walk over the indices, allocation + upload, kernels, read-back."""
+        out = (C.c_double * 4)()
+        self._check(self.lib.hipr_debug_collapse4_times(self.handle, out), "hipr_debug_collapse4_times")
+        return dict(validate=out[0], upload=out[1], kernels=out[2], readback=out[3])
+
     def rebuild_scene_trees(self, max_depth: int = 62, read_back: bool = True, group=None) -> dict:
         """hipr_rebuild_scene_trees: the trees of the resident scene rebuilt on the device from the triangles it holds (after a refit_scene_transforms that moved a model
         far, or reported needs_rebuild). Returns a dict of status, node_count, deepest, wide8 (as build_wide8's result), half_area and -- `read_back` -- nodes

@@ -414,6 +414,20 @@ typedef struct HiprWide8BuildResult {
 } HiprWide8BuildResult;
 int hipr_build_wide8(HiprContext* context, const HiprBvhNode* nodes, uint32_t node_count, const HiprTriangle* triangles, const uint32_t* order /* may be NULL */,
                      uint32_t triangle_count, HiprSlot8* out_slots, uint32_t slot_capacity, HiprWide8BuildResult* out);
+/* The compressed 4-wide tree of a BVH2 (HiprWideNode) collapsed on the device (the reference asks OptiX for a "Trbvh" build, which runs on the GPU,
+ * OR/Renderer.cpp:161-182,471-476): byte for byte the nodes, node count and stack entries of the host's collapse (host/BvhBuilder.cpp; csrc/wide4_build.h), which
+ * are what HiprSceneDesc::wide_nodes, wide_node_count and wide_stack_entries take. The collapse reads no triangle: `triangle_count` bounds the leaf ranges. All
+ * pointers are host pointers; a `node_capacity` of `node_count` always suffices, because every wide node is rooted at a distinct BVH2 node. The call runs on the
+ * context's stream, owns its device scratch (about 220 B per BVH2 node; kept with the context up to 128 MiB, freed when the call returns beyond that), leaves the
+ * resident scene untouched and needs none. Checked on the host, by one pass over the indices, before the device is touched:
+ *   HIPR_ERROR_INVALID_ARGUMENT   a null pointer or no nodes; a child index or a leaf range out of bounds; a node referenced twice; more than 64 levels of nodes.
+ *   HIPR_ERROR_UNSUPPORTED        more nodes than a leaf reference addresses (2^28), as hipr_build_wide8.
+ * Found on the device, before a node is written:
+ *   HIPR_ERROR_INVALID_ARGUMENT   a child box that is not finite (the first pass reads every box anyway); `node_capacity` below the nodes the tree needs.
+ * Every refusal leaves `out_nodes` and `out` untouched. */
+typedef struct HiprWide4BuildResult { uint32_t node_count, stack_entries; } HiprWide4BuildResult;
+int hipr_build_wide4(HiprContext* context, const HiprBvhNode* nodes, uint32_t node_count, uint32_t triangle_count, HiprWideNode* out_nodes, uint32_t node_capacity,
+                     HiprWide4BuildResult* out);
 /* The trees of the RESIDENT scene rebuilt on the device, in place, from the triangles it holds (the reference asks OptiX for a "Trbvh" build, which runs on the GPU
  * over the geometry the device holds, OR/Renderer.cpp:161-182,471-476; a moved node marks the acceleration dirty and the next launch rebuilds it on the device,
  * OR/Renderer.cpp:472,1010-1041): what a model that was dragged far asks for -- hipr_refit_scene_transforms reports child_half_area past 1.5 x uploaded_half_area, or
@@ -619,6 +633,8 @@ int hipr_group_build_bvh2(HiprGroup* group, const HiprTriangle* triangles, uint3
                           uint32_t* out_node_count, uint32_t* out_order, uint32_t* out_deepest);   /* builds on member 0 */
 int hipr_group_build_wide8(HiprGroup* group, const HiprBvhNode* nodes, uint32_t node_count, const HiprTriangle* triangles, const uint32_t* order, uint32_t triangle_count,
                            HiprSlot8* out_slots, uint32_t slot_capacity, HiprWide8BuildResult* out);   /* collapses on member 0 */
+int hipr_group_build_wide4(HiprGroup* group, const HiprBvhNode* nodes, uint32_t node_count, uint32_t triangle_count, HiprWideNode* out_nodes, uint32_t node_capacity,
+                           HiprWide4BuildResult* out);   /* collapses on member 0 */
 int hipr_group_rebuild_scene_trees(HiprGroup* group, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity, uint32_t* out_order, HiprSlot8* out_slots,
                                    uint32_t slot_capacity, HiprSceneRebuildResult* out);   /* every member rebuilds; member 0's arrays are handed out; their results must agree */
 int hipr_group_edit_scene_instances(HiprGroup* group, const HiprInstanceEdit* edits, uint32_t edit_count, uint32_t max_depth, HiprBvhNode* out_nodes, uint32_t node_capacity,
@@ -791,6 +807,9 @@ int hipr_debug_append_times(HiprContext* context, double* out3_ms);
 int hipr_debug_build_times(HiprContext* context, double* out4_ms);
 /* The same for the context's last successful hipr_build_wide8: the walk over the indices, allocation + upload, kernels (with the few words read per level), read-back. */
 int hipr_debug_collapse_times(HiprContext* context, double* out4_ms);
+/* ... and for the context's last successful hipr_build_wide4: the walk over the indices, allocation + upload, kernels (with the few words read per level), read-back
+ * (tools/wide4_collapse_probe.py). */
+int hipr_debug_collapse4_times(HiprContext* context, double* out4_ms);
 /* The same for the context's last successful hipr_rebuild_scene_trees: the flatten order, the BVH2 build, the hand-over and the collapse with its slots copied to the
  * host, the new resident arrays with what is derived from them, the read-back of the outputs (tools/device_rebuild_probe.py). */
 int hipr_debug_rebuild_times(HiprContext* context, double* out5_ms);
