@@ -158,6 +158,19 @@ class HiprPoolGrowth(C.Structure):
                 ("index_count", c_u32), ("segment_count", c_u32), ("material_count", c_u32), ("texture_count", c_u32)]
 
 
+class HiprEnvironmentBuild(C.Structure):
+    _fields_ = [("environment_map_ID", c_i32), ("row_sines", C.POINTER(c_f)), ("pdf_height", c_u32), ("srgb_decode", C.POINTER(c_f)), ("draw_points", C.POINTER(c_f)), ("sample_count", c_u32)]
+
+
+class HiprLightingResult(C.Structure):
+    _fields_ = [("pdf_width", c_u32), ("pdf_height", c_u32), ("sample_count", c_u32), ("importance_sampling_disabled", c_u32), ("light_count", c_u32), ("switches", c_u32)]
+
+
+ENVIRONMENT_KEEP, ENVIRONMENT_REMOVE, ENVIRONMENT_BUILD = 0, 1, 2
+SWITCH_TEXTURES, SWITCH_ENVIRONMENT = 1, 2
+LIGHT_NONE, LIGHT_SPHERE, LIGHT_DIRECTIONAL, LIGHT_ENVIRONMENT, LIGHT_PRESAMPLED_ENVIRONMENT, LIGHT_SPOT, LIGHT_TYPE_MASK = 0, 1, 2, 3, 4, 5, 7
+
+
 class HiprRefitResult(C.Structure):
     _fields_ = [("needs_rebuild", c_i32), ("child_half_area", C.c_double), ("uploaded_half_area", C.c_double), ("grid_min", c_f * 3), ("grid_cell", c_f * 3)]
 
@@ -196,6 +209,8 @@ SCENE_BUFFER_NODES = 7      # the BVH2; not among SCENE_BUFFERS, which lists wha
 TEXEL_R8, TEXEL_RGBA8, TEXEL_R32F, TEXEL_RGBA32F = 1, 4, 17, 20
 # the pools hipr_append_scene_pools grows; not among SCENE_BUFFERS either: tests of the growth keep a tuple of their own
 SCENE_BUFFER_INDICES, SCENE_BUFFER_GEOMETRY, SCENE_BUFFER_TEXCOORDS, SCENE_BUFFER_TINTS, SCENE_BUFFER_EMISSIONS, SCENE_BUFFER_TEXTURES, SCENE_BUFFER_TEXELS = 8, 9, 10, 11, 12, 13, 14
+# what hipr_update_scene_lighting writes: the lights, the environment's PDF image and its samples
+SCENE_BUFFER_LIGHTS, SCENE_BUFFER_ENVIRONMENT_PDF, SCENE_BUFFER_ENVIRONMENT_SAMPLES = 15, 16, 17
 SCENE_BUFFERS = (SCENE_BUFFER_TRIANGLES, SCENE_BUFFER_WIDE8_SLOTS, SCENE_BUFFER_TRACE_TRIANGLES, SCENE_BUFFER_SHADE_TRIANGLES, SCENE_BUFFER_TRIANGLE_CLASS, SCENE_BUFFER_MATERIALS, SCENE_BUFFER_INSTANCES)
 TRACE_BVH2, TRACE_WIDE_PERSISTENT, TRACE_EXHAUSTIVE, TRACE_WIDE8_PERSISTENT = 0, 1, 2, 3
 SHADING_DEFAULT, SHADING_DIFFUSE, SHADING_TRANSMISSIVE = 0, 1, 2
@@ -213,11 +228,12 @@ assert C.sizeof(HiprMaterial) == 64 and C.sizeof(HiprLight) == 48 and C.sizeof(H
 assert C.sizeof(HiprTexture) == 24 and C.sizeof(HiprCameraState) == 180 and C.sizeof(HiprTriangle) == 48 and C.sizeof(HiprBvhNode) == 64 and C.sizeof(HiprInstance) == 80
 assert C.sizeof(HiprInstanceEdit) == 88 and C.sizeof(HiprSceneEditResult) == 72
 assert C.sizeof(HiprIndexSegment) == 8 and C.sizeof(HiprPoolGrowth) == 112
+assert C.sizeof(HiprEnvironmentBuild) == 48 and C.sizeof(HiprLightingResult) == 24 and C.sizeof(HiprLightSample) == 32
 
 # Every symbol include/hiprenderer_c.h declares; tests check the library exports all of them.
 C_ABI_SYMBOLS = (
     "hipr_create", "hipr_destroy", "hipr_last_error", "hipr_device_count", "hipr_set_stream",
-    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_build_bvh2", "hipr_group_build_bvh2", "hipr_debug_build_times", "hipr_build_wide8", "hipr_group_build_wide8", "hipr_debug_collapse_times", "hipr_build_wide4", "hipr_group_build_wide4", "hipr_debug_collapse4_times", "hipr_rebuild_scene_trees", "hipr_group_rebuild_scene_trees", "hipr_edit_scene_instances", "hipr_group_edit_scene_instances", "hipr_append_scene_pools", "hipr_group_append_scene_pools", "hipr_debug_scene_buffer_bytes", "hipr_debug_append_times", "hipr_debug_rebuild_times", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
+    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_build_bvh2", "hipr_group_build_bvh2", "hipr_debug_build_times", "hipr_build_wide8", "hipr_group_build_wide8", "hipr_debug_collapse_times", "hipr_build_wide4", "hipr_group_build_wide4", "hipr_debug_collapse4_times", "hipr_rebuild_scene_trees", "hipr_group_rebuild_scene_trees", "hipr_edit_scene_instances", "hipr_group_edit_scene_instances", "hipr_append_scene_pools", "hipr_group_append_scene_pools", "hipr_update_scene_lighting", "hipr_group_update_scene_lighting", "hipr_debug_lighting_times", "hipr_debug_scene_buffer_bytes", "hipr_debug_append_times", "hipr_debug_rebuild_times", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
     "hipr_set_frame", "hipr_owned_pixel_count",
     "hipr_render_pass", "hipr_set_samples_per_pass", "hipr_trace_pass", "hipr_accumulate_samples", "hipr_read_accumulation", "hipr_scatter_tiles", "hipr_synchronize", "hipr_get_counters",
     "hipr_device_malloc", "hipr_device_free", "hipr_device_memset", "hipr_copy_to_host", "hipr_present_flipped",
@@ -281,6 +297,10 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.hipr_group_edit_scene_instances.argtypes = [vp, C.POINTER(HiprInstanceEdit), c_u32, c_u32, vp, c_u32, vp, c_u32, vp, c_u32, C.POINTER(HiprSceneEditResult)]
     lib.hipr_append_scene_pools.argtypes = [vp, C.POINTER(HiprPoolGrowth)]
     lib.hipr_group_append_scene_pools.argtypes = [vp, C.POINTER(HiprPoolGrowth)]
+    lighting = [C.POINTER(HiprLight), c_u32, C.c_int, C.POINTER(HiprEnvironmentBuild), C.POINTER(c_f), c_u64, C.POINTER(HiprLightSample), c_u32, C.POINTER(HiprLightingResult)]
+    lib.hipr_update_scene_lighting.argtypes = [vp] + lighting
+    lib.hipr_group_update_scene_lighting.argtypes = [vp] + lighting
+    lib.hipr_debug_lighting_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.hipr_debug_scene_buffer_bytes.argtypes = [vp, C.c_int, C.POINTER(c_u64)]
     lib.hipr_debug_append_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.hipr_debug_rebuild_times.argtypes = [vp, C.POINTER(C.c_double)]

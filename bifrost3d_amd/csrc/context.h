@@ -98,6 +98,8 @@ constexpr int COUNT_PAIRS = 3, COUNT_LINES = 3;
 constexpr int HOST_COUNT_WORDS = 8 + COUNT_LINES * COUNT_PAIR_STRIDE;   // pinned: 2 x {paths, shadow rays} read back, [4..8) spare, then the image of the counters at the start of a pass
 
 // What the argument checks of a description derive on their way (preflight_scene).
+struct LightingScratch;      // below, with the other scratches
+
 struct Preflight {
     uint32_t wide_stack_need = 0;       // worst-case stack need of the 4-wide tree: derived, not taken from the caller
     uint32_t wide8_height = 0;          // 0: the description brings no 8-wide tree
@@ -186,6 +188,10 @@ struct ResidentScene {
     int install_rebuilt_trees(const RebuiltTrees& built, hipStream_t stream);
     // The device work of hipr_append_scene_pools, which has checked the description against the host copies (hipr_internal_check_pool_growth): the pools grown at their tails.
     int append_pools(const HiprPoolGrowth& growth, hipStream_t stream);
+    // The device work of hipr_update_scene_lighting, which has checked its arguments against the host copies (hipr_internal_check_lighting_update): the light list
+    // replaced, the environment kept, removed or rebuilt from the resident texels (environment_build.h).
+    int update_lighting(const HiprLight* new_lights, uint32_t light_count, int environment_action, const HiprEnvironmentBuild* build, float* out_per_pixel_PDF, HiprLightSample* out_samples,
+                        LightingScratch& scratch, hipStream_t stream, HiprLightingResult* out);
     double append_ms[3] = {0.0, 0.0, 0.0};      // of the last append_pools: the allocations (host clock), the device-to-device copies of the resident parts, the tails and the mirror segments (events)
     Event append_events[3];             // made by the first append_pools
 
@@ -280,6 +286,14 @@ struct RebuildScratch : Scratch<RebuildBuffers> {
     double flatten_ms = 0.0, bvh2_ms = 0.0, collapse_ms = 0.0, install_ms = 0.0, readback_ms = 0.0;      // of the last rebuild
 };
 
+// The device scratch of hipr_update_scene_lighting's environment build (environment_build.h): the three tables, then per PDF texel the importance, its blurred
+// copy and the conditional sums (a word more per row) -- about three PDF images -- and a few words per row.
+struct LightingBuffers { DeviceBuffer row_sines, srgb_decode, draw_points, importance, blurred, conditional, marginal_raw, marginal, totals, integral; };
+struct LightingScratch : Scratch<LightingBuffers> {
+    double upload_ms = 0.0, kernel_ms = 0.0, finish_ms = 0.0, readback_ms = 0.0;      // of the last lighting update
+    Event events[4];                    // around the kernels before and after the integral is read; made by the first build
+};
+
 // The context; HiprContext, the C-ABI's opaque type, is this and nothing else.
 struct Context {
     int device = 0;
@@ -371,6 +385,7 @@ struct Context {
     CollapseScratch collapse;           // hipr_build_wide8; likewise
     Collapse4Scratch collapse4;         // hipr_build_wide4; likewise
     RebuildScratch rebuild;             // hipr_rebuild_scene_trees, which also runs over the two above
+    LightingScratch lighting;           // hipr_update_scene_lighting's environment build
 
     hipEvent_t next_event() {
         if (events_used == event_pool.size()) {

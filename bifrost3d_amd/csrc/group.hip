@@ -40,6 +40,9 @@
 extern "C" int hipr_internal_check_material_update(HiprContext* context, const HiprMaterialUpdate* materials, uint32_t material_count, const HiprInstanceMaterial* assignments,
                                                    uint32_t assignment_count);   // scene.hip: the refusals of hipr_update_scene_materials on their own
 extern "C" int hipr_internal_check_pool_growth(HiprContext* context, const HiprPoolGrowth* growth);   // scene.hip: every refusal of hipr_append_scene_pools short of a failed allocation
+extern "C" int hipr_internal_check_lighting_update(HiprContext* context, const HiprLight* lights, uint32_t light_count, int environment_action, const HiprEnvironmentBuild* build,
+                                                   const float* out_per_pixel_PDF, uint64_t pdf_capacity, const HiprLightSample* out_samples, uint32_t sample_capacity,
+                                                   const HiprLightingResult* out);   // scene.hip: every refusal of hipr_update_scene_lighting short of a failed allocation
 extern "C" void hipr_internal_set_last_error(const char* message);   // hiprenderer.hip: hipr_last_error() is per thread; a worker's message is handed to the caller's
 
 namespace {
@@ -409,6 +412,29 @@ int hipr_group_append_scene_pools(HiprGroup* g, const HiprPoolGrowth* growth) {
     for (Member& m : g->members)
         if (int s = hipr_internal_check_pool_growth(m.context, growth)) return s;
     return for_each_member(g, [&](Member& m, uint32_t) { return hipr_append_scene_pools(m.context, growth); });
+}
+
+// hipr_update_scene_lighting on every member: every member checks before any member writes; the same kernels over the same texels give the same environment, so
+// member 0's arrays are the ones handed out and the others build without a read-back of the PDF image.
+int hipr_group_update_scene_lighting(HiprGroup* g, const HiprLight* lights, uint32_t light_count, int environment_action, const HiprEnvironmentBuild* build, float* out_per_pixel_PDF,
+                                     uint64_t pdf_capacity, HiprLightSample* out_samples, uint32_t sample_capacity, HiprLightingResult* out) {
+    if (!g || !out || g->members.empty()) return HIPR_ERROR_INVALID_ARGUMENT;
+    for (Member& m : g->members)
+        if (int s = hipr_internal_check_lighting_update(m.context, lights, light_count, environment_action, build, out_per_pixel_PDF, pdf_capacity, out_samples, sample_capacity, out)) return s;
+    std::vector<HiprLightingResult> results(g->members.size());
+    const int status = for_each_member(g, [&](Member& m, uint32_t index) {
+        return index == 0 ? hipr_update_scene_lighting(m.context, lights, light_count, environment_action, build, out_per_pixel_PDF, pdf_capacity, out_samples, sample_capacity, &results[0])
+                          : hipr_update_scene_lighting(m.context, lights, light_count, environment_action, build, nullptr, 0, nullptr, 0, &results[index]);
+    });
+    if (status) return status;
+    for (const HiprLightingResult& r : results)
+        if (std::memcmp(&r, &results[0], sizeof(r))) {
+            hipr_internal_set_last_error("hipr_group_update_scene_lighting: the members' environments disagree");
+            fprintf(stderr, "hiprenderer: hipr_group_update_scene_lighting: the members' environments disagree\n");
+            return HIPR_ERROR_HIP;
+        }
+    *out = results[0];
+    return HIPR_OK;
 }
 
 int hipr_group_update_scene_materials(HiprGroup* g, const HiprMaterialUpdate* materials, uint32_t material_count, const HiprInstanceMaterial* assignments, uint32_t assignment_count) {

@@ -16,6 +16,7 @@
 #include "scene_rebuild.h"
 #include "instance_edit.h"
 #include "pool_growth.h"
+#include "environment_build.h"
 
 #include <hip/hip_runtime.h>
 
@@ -762,6 +763,148 @@ int ResidentScene::append_pools(const HiprPoolGrowth& g, hipStream_t st) {
     uploaded_mesh_attributes |= (g.texcoord_vertices ? HIPR_MESH_TEXCOORDS : 0u) | (g.tint_vertices ? HIPR_MESH_TINTS : 0u) | (g.emission_vertices ? HIPR_MESH_EMISSIVE : 0u);
     uploaded_texel_bytes += g.texel_bytes;
     derive_switches_from_pools();
+    ready = was_ready;
+    awaits_rebuild = awaited_rebuild;
+    return HIPR_OK;
+}
+
+// The device work of hipr_update_scene_lighting (environment_build.h). The scratch and every new buffer -- the lights', the environment's PDF image and samples --
+// are allocated BEFORE the scene is touched: a failed allocation leaves the scene as found. The kernels write scratch and the new buffers only; the resident ones
+// are exchanged for them at the end, when nothing can fail any more. Then, as the other writers: the new pointers and counts in `args`, the host copies, the
+// switches -- and the state the call found, ready or awaiting a rebuild: no triangle, tree or pool has changed.
+int ResidentScene::update_lighting(const HiprLight* new_lights, uint32_t light_count, int action, const HiprEnvironmentBuild* build, float* out_per_pixel_PDF, HiprLightSample* out_samples,
+                                   LightingScratch& x, hipStream_t st, HiprLightingResult* out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool builds = action == HIPR_ENVIRONMENT_BUILD;
+    DeviceBuffer fresh_lights, fresh_PDF, fresh_samples;
+    EnvTexture texture = {};
+    uint32_t width = 0, height = 0, samples = 0;
+    bool blurs = false;
+    int r = fresh_lights.resize((size_t(light_count) + 1) * sizeof(HiprLight));
+    if (builds) {
+        const HiprTexture& t = uploaded_textures[size_t(build->environment_map_ID)];
+        texture = {t.width, t.height, t.format, t.wrap_u, t.wrap_v, t.filter, texels.as<uint8_t>() + t.texel_offset, nullptr};
+        width = t.width; height = build->pdf_height; samples = build->sample_count;
+        blurs = (t.filter & 1u) != 0 || height != t.height;      // compute_distribution's filter_pixels
+        const size_t texel_count = size_t(width) * height;
+        r |= fresh_PDF.resize(texel_count * sizeof(float));
+        r |= fresh_samples.resize(size_t(samples) * sizeof(HiprLightSample));
+        r |= x.row_sines.resize(size_t(height) * sizeof(float));
+        r |= x.srgb_decode.resize(256 * sizeof(float));
+        r |= x.draw_points.resize(size_t(samples) * 2 * sizeof(float));
+        r |= x.importance.resize(texel_count * sizeof(float));
+        if (blurs) r |= x.blurred.resize(texel_count * sizeof(float));
+        r |= x.conditional.resize(size_t(width + 1) * height * sizeof(float));
+        r |= x.marginal_raw.resize((size_t(height) + 1) * sizeof(float));
+        r |= x.marginal.resize((size_t(height) + 1) * sizeof(float));
+        r |= x.totals.resize(size_t(height) * sizeof(float));
+        r |= x.integral.resize(sizeof(float));
+        for (Event& e : x.events)
+            if (!e) e = make_event(hipEventDefault);
+    }
+    if (r) {
+        (void)hipGetLastError();      // the failed allocation's error is answered here: it must not meet the next call's check
+        return HIPR_ERROR_OUT_OF_MEMORY;      // the new buffers go with this frame
+    }
+    const bool was_ready = ready, awaited_rebuild = awaits_rebuild;
+    begin_write();
+    const bool timed = x.events[0] && x.events[1] && x.events[2] && x.events[3];
+    bool disabled = false;
+    float kernel_ms[2] = {0.0f, 0.0f};
+    double finish_ms = 0.0, readback_ms = 0.0;
+    auto t1 = t0;
+    std::vector<HiprLightSample> finished;
+    if (builds) {
+        HIP_TRY(hipMemcpyAsync(x.row_sines.ptr, build->row_sines, size_t(height) * sizeof(float), hipMemcpyHostToDevice, st));
+        if (build->srgb_decode) { HIP_TRY(hipMemcpyAsync(x.srgb_decode.ptr, build->srgb_decode, 256 * sizeof(float), hipMemcpyHostToDevice, st)); texture.srgb_decode = x.srgb_decode.as<float>(); }
+        HIP_TRY(hipMemcpyAsync(x.draw_points.ptr, build->draw_points, size_t(samples) * 2 * sizeof(float), hipMemcpyHostToDevice, st));
+        t1 = std::chrono::steady_clock::now();
+        const size_t texel_count = size_t(width) * height;
+        const uint32_t texel_blocks = uint32_t((texel_count + ENV_BLOCK - 1) / ENV_BLOCK);
+        if (timed) HIP_TRY(hipEventRecord(x.events[0], st));
+        hipLaunchKernelGGL(k_env_importance, dim3(texel_blocks), dim3(ENV_BLOCK), 0, st, texture, height, x.row_sines.as<float>(), x.importance.as<float>());
+        if (blurs) hipLaunchKernelGGL(k_env_blur, dim3(texel_blocks), dim3(ENV_BLOCK), 0, st, x.importance.as<float>(), width, height, x.blurred.as<float>());
+        const float* function = blurs ? x.blurred.as<float>() : x.importance.as<float>();
+        hipLaunchKernelGGL(k_env_row_sums, dim3((height + ENV_BAND_ROWS - 1) / ENV_BAND_ROWS), dim3(ENV_BLOCK), 0, st, function, width, height, x.conditional.as<float>());
+        hipLaunchKernelGGL(k_env_marginal, dim3(1), dim3(64), 0, st, x.conditional.as<float>(), width, height, x.marginal_raw.as<float>(), x.totals.as<float>(), x.integral.as<float>());
+        HIP_TRY(hipGetLastError());
+        if (timed) HIP_TRY(hipEventRecord(x.events[1], st));
+        float integral = 0.0f;
+        HIP_TRY(hipMemcpyAsync(&integral, x.integral.ptr, sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));      // the tables are read by now as well; the branch below is presample_environment's, taken where it takes it
+        if (timed) HIP_TRY(hipEventElapsedTime(&kernel_ms[0], x.events[0], x.events[1]));
+        disabled = integral < 0.00001f;
+        if (disabled) {
+            width = height = samples = 1;
+            finished.assign(1, HiprLightSample{{0, 0, 0}, 0.0f, {0, 1, 0}, 0.0f});      // LightSample::none()
+            HIP_TRY(hipMemsetAsync(fresh_PDF.ptr, 0, sizeof(float), st));
+        } else {
+            const float PDF_scale = float(int(width) * int(height)) * (1.0f / (2.0f * 3.14159265358979323846f * 3.14159265358979323846f));
+            const size_t entries = size_t(width + 1) * height;
+            if (timed) HIP_TRY(hipEventRecord(x.events[2], st));
+            hipLaunchKernelGGL(k_env_normalise, dim3(uint32_t((entries + ENV_BLOCK - 1) / ENV_BLOCK)), dim3(ENV_BLOCK), 0, st, x.marginal_raw.as<float>(), x.totals.as<float>(), width, height,
+                               x.marginal.as<float>(), x.conditional.as<float>());
+            hipLaunchKernelGGL(k_env_pdf_image, dim3(texel_blocks), dim3(ENV_BLOCK), 0, st, x.marginal.as<float>(), x.conditional.as<float>(), width, height, PDF_scale, fresh_PDF.as<float>());
+            hipLaunchKernelGGL(k_env_draws, dim3((samples + ENV_BLOCK - 1) / ENV_BLOCK), dim3(ENV_BLOCK), 0, st, texture, x.marginal.as<float>(), x.conditional.as<float>(), height,
+                               x.draw_points.as<float>(), samples, fresh_samples.as<HiprLightSample>());
+            HIP_TRY(hipGetLastError());
+            if (timed) HIP_TRY(hipEventRecord(x.events[3], st));
+            finished.resize(samples);
+            const auto r0 = std::chrono::steady_clock::now();
+            HIP_TRY(hipMemcpyAsync(finished.data(), fresh_samples.ptr, size_t(samples) * sizeof(HiprLightSample), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (timed) HIP_TRY(hipEventElapsedTime(&kernel_ms[1], x.events[2], x.events[3]));
+            const auto r1 = std::chrono::steady_clock::now();
+            for (HiprLightSample& s : finished) finish_environment_sample(s);
+            finish_ms = ms(r1, std::chrono::steady_clock::now());
+            readback_ms = ms(r0, r1);
+        }
+        const auto r2 = std::chrono::steady_clock::now();
+        HIP_TRY(hipMemcpyAsync(fresh_samples.ptr, finished.data(), finished.size() * sizeof(HiprLightSample), hipMemcpyHostToDevice, st));
+        if (out_per_pixel_PDF) HIP_TRY(hipMemcpyAsync(out_per_pixel_PDF, fresh_PDF.ptr, size_t(width) * height * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (out_samples) std::memcpy(out_samples, finished.data(), finished.size() * sizeof(HiprLightSample));
+        readback_ms += ms(r2, std::chrono::steady_clock::now());
+    }
+    // the new list, with the environment's light last when the environment that is resident from here on takes part in next event estimation
+    const uint32_t resident_samples = builds ? samples : (action == HIPR_ENVIRONMENT_KEEP && uploaded_environment ? args.env_sample_count : 0u);
+    std::vector<HiprLight> list(new_lights, new_lights + light_count);
+    if (resident_samples > 1) {      // next_event_estimation_possible (SceneBuilder::set_environment)
+        HiprLight light = {};
+        light.flags = HIPR_LIGHT_PRESAMPLED_ENVIRONMENT;
+        list.push_back(light);
+    }
+    const auto l0 = std::chrono::steady_clock::now();
+    if (!list.empty()) HIP_TRY(hipMemcpyAsync(fresh_lights.ptr, list.data(), list.size() * sizeof(HiprLight), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));      // `list` is read; nothing is queued any more: the resident buffers change hands
+    const double lights_ms = ms(l0, std::chrono::steady_clock::now());
+    std::swap(lights, fresh_lights);      // the old buffers go with this frame
+    args.lights = lights.as<HiprLight>();
+    args.light_count = uint32_t(list.size());
+    if (builds) {
+        std::swap(environment_PDF, fresh_PDF);
+        std::swap(environment_samples, fresh_samples);
+        args.env_map_ID = build->environment_map_ID;
+        args.env_per_pixel_PDF = environment_PDF.as<float>();
+        args.env_samples = environment_samples.as<float4>();
+        args.env_pdf_width = width; args.env_pdf_height = height; args.env_sample_count = samples;
+        uploaded_environment = true;
+    } else if (action == HIPR_ENVIRONMENT_REMOVE) {
+        args.env_map_ID = 0;
+        args.env_per_pixel_PDF = nullptr;
+        args.env_samples = nullptr;
+        args.env_pdf_width = args.env_pdf_height = args.env_sample_count = 0u;
+        uploaded_environment = false;
+    }
+    uploaded_light_types.resize(list.size());
+    for (size_t l = 0; l < list.size(); ++l) uploaded_light_types[l] = list[l].flags & HIPR_LIGHT_TYPE_MASK;
+    derive_switches_from_pools();
+    x.upload_ms = ms(t0, t1) + lights_ms; x.kernel_ms = double(kernel_ms[0]) + double(kernel_ms[1]); x.finish_ms = finish_ms; x.readback_ms = readback_ms;
+    *out = {};
+    out->pdf_width = args.env_pdf_width; out->pdf_height = args.env_pdf_height; out->sample_count = args.env_sample_count;
+    out->importance_sampling_disabled = disabled ? 1u : 0u;
+    out->light_count = args.light_count;
+    out->switches = (has_textures ? HIPR_SWITCH_TEXTURES : 0u) | (has_environment ? HIPR_SWITCH_ENVIRONMENT : 0u);
     ready = was_ready;
     awaits_rebuild = awaited_rebuild;
     return HIPR_OK;
@@ -1562,6 +1705,63 @@ int hipr_debug_append_times(HiprContext* c, double* out3_ms) {
     return HIPR_OK;
 }
 
+// Not part of the public header: every refusal of hipr_update_scene_lighting that is not a failed allocation, and nothing else -- no HIP call, the device and the
+// books stay as they are. The group asks every member before any member writes.
+int hipr_internal_check_lighting_update(HiprContext* c, const HiprLight* lights, uint32_t light_count, int action, const HiprEnvironmentBuild* b, const float* out_per_pixel_PDF, uint64_t pdf_capacity,
+                                        const HiprLightSample* out_samples, uint32_t sample_capacity, const HiprLightingResult* out) {
+    const char* who = "hipr_update_scene_lighting";
+    if (int st = check_context(c)) return st;
+    const ResidentScene& r = c->scene;
+    if (!r.ready && !r.awaits_rebuild) return fail(HIPR_ERROR_NOT_READY, "%s: no scene uploaded, or one a failed call left behind", who);
+    if (!out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null result", who);
+    if (light_count && !lights) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null array with a non-zero count", who);
+    if (light_count == 0xFFFFFFFFu) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: the list with the environment's light does not fit 32 bits", who);
+    for (uint32_t l = 0; l < light_count; ++l)
+        if ((lights[l].flags & HIPR_LIGHT_TYPE_MASK) == HIPR_LIGHT_PRESAMPLED_ENVIRONMENT)
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: light %u is the environment's; the call appends it by itself", who, l);
+    if (action != HIPR_ENVIRONMENT_KEEP && action != HIPR_ENVIRONMENT_REMOVE && action != HIPR_ENVIRONMENT_BUILD) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: unknown environment action %d", who, action);
+    if ((action == HIPR_ENVIRONMENT_BUILD) != (b != nullptr)) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: HIPR_ENVIRONMENT_BUILD comes with a description, the other actions without", who);
+    if (!b) return HIPR_OK;
+    if (b->environment_map_ID <= 0 || size_t(b->environment_map_ID) >= r.uploaded_textures.size())
+        return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: environment map %d of %zu resident textures (hipr_append_scene_pools brings a new one)", who, b->environment_map_ID, r.uploaded_textures.size());
+    const HiprTexture& t = r.uploaded_textures[size_t(b->environment_map_ID)];
+    if (b->pdf_height != std::max(t.height, ENV_MINIMUM_PDF_HEIGHT)) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: pdf_height is %u, a texture of %u rows takes %u", who, b->pdf_height, t.height, std::max(t.height, ENV_MINIMUM_PDF_HEIGHT));
+    if (!b->row_sines || !b->draw_points) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null array with a non-zero count", who);
+    if (t.is_sRGB && !b->srgb_decode) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: texture %d is sRGB and needs srgb_decode", who, b->environment_map_ID);
+    if (!t.is_sRGB && b->srgb_decode) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: texture %d is linear; srgb_decode must be null", who, b->environment_map_ID);
+    if (b->sample_count < 2u || (b->sample_count & (b->sample_count - 1u))) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: %u samples; a power of two >= 2 is needed", who, b->sample_count);
+    for (size_t k = 0; k < size_t(b->sample_count) * 2; ++k)
+        if (!(b->draw_points[k] >= 0.0f && b->draw_points[k] < 1.0f)) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: draw point %zu lies outside [0, 1)", who, k / 2);
+    for (uint32_t y = 0; y < b->pdf_height; ++y)
+        if (!std::isfinite(b->row_sines[y])) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: row_sines[%u] is not finite", who, y);
+    for (uint32_t k = 0; b->srgb_decode && k < 256u; ++k)
+        if (!std::isfinite(b->srgb_decode[k])) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: srgb_decode[%u] is not finite", who, k);
+    const uint64_t texel_count = uint64_t(t.width) * b->pdf_height;
+    if ((out_per_pixel_PDF && pdf_capacity < texel_count) || (out_samples && sample_capacity < b->sample_count))
+        return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: the outputs need room for %llu PDF texels and %u samples", who, (unsigned long long)texel_count, b->sample_count);
+    if (t.format != HIPR_TEXEL_RGBA8 && t.format != HIPR_TEXEL_RGBA32F) return fail(HIPR_ERROR_UNSUPPORTED, "%s: only environments with 4 channels are supported (OptiXRenderer/Renderer.cpp:1141-1158)", who);
+    if (t.is_sRGB && t.format == HIPR_TEXEL_RGBA32F) return fail(HIPR_ERROR_UNSUPPORTED, "%s: an sRGB texture of floats is decoded by pow per texel, which a table of bytes cannot serve; upload the scene instead", who);
+    if (texel_count > (1ull << 30)) return fail(HIPR_ERROR_UNSUPPORTED, "%s: a PDF image of %llu texels is more than the kernels index", who, (unsigned long long)texel_count);
+    return HIPR_OK;
+}
+
+// The lights and the environment of the resident scene replaced on the device (environment_build.h): the arguments checked on the host, then ResidentScene::update_lighting.
+int hipr_update_scene_lighting(HiprContext* c, const HiprLight* lights, uint32_t light_count, int action, const HiprEnvironmentBuild* b, float* out_per_pixel_PDF, uint64_t pdf_capacity,
+                               HiprLightSample* out_samples, uint32_t sample_capacity, HiprLightingResult* out) {
+    if (int st = hipr_internal_check_lighting_update(c, lights, light_count, action, b, out_per_pixel_PDF, pdf_capacity, out_samples, sample_capacity, out)) return st;
+    if (int finish_status = finish_all(c)) return finish_status;      // no pending pass may go on over buffers that are about to change hands
+    c->break_chain(c->stream);
+    ScratchGuard<LightingScratch> guard(c->lighting);
+    return c->scene.update_lighting(lights, light_count, action, b, out_per_pixel_PDF, out_samples, c->lighting, c->stream, out);
+}
+
+int hipr_debug_lighting_times(HiprContext* c, double* out4_ms) {
+    if (!c || !out4_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_lighting_times: null argument");
+    const LightingScratch& x = c->lighting;
+    out4_ms[0] = x.upload_ms; out4_ms[1] = x.kernel_ms; out4_ms[2] = x.finish_ms; out4_ms[3] = x.readback_ms;
+    return HIPR_OK;
+}
+
 int hipr_debug_rebuild_times(HiprContext* c, double* out5_ms) {
     if (!c || !out5_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_rebuild_times: null argument");
     const RebuildScratch& x = c->rebuild;
@@ -1588,6 +1788,9 @@ static bool scene_buffer(const ResidentScene& r, int which, const void*& from, u
     else if (which == HIPR_SCENE_BUFFER_EMISSIONS) attribute(r.emissions, HIPR_MESH_EMISSIVE, 12);
     else if (which == HIPR_SCENE_BUFFER_TEXTURES) { from = r.textures.ptr; bytes = uint64_t(r.uploaded_textures.size()) * sizeof(HiprTexture); }
     else if (which == HIPR_SCENE_BUFFER_TEXELS) { from = r.texels.ptr; bytes = r.uploaded_texel_bytes; }
+    else if (which == HIPR_SCENE_BUFFER_LIGHTS) { from = r.lights.ptr; bytes = uint64_t(r.args.light_count) * sizeof(HiprLight); }
+    else if (which == HIPR_SCENE_BUFFER_ENVIRONMENT_PDF) { from = r.environment_PDF.ptr; bytes = r.uploaded_environment ? uint64_t(r.args.env_pdf_width) * r.args.env_pdf_height * sizeof(float) : 0u; }
+    else if (which == HIPR_SCENE_BUFFER_ENVIRONMENT_SAMPLES) { from = r.environment_samples.ptr; bytes = r.uploaded_environment ? uint64_t(r.args.env_sample_count) * sizeof(HiprLightSample) : 0u; }
     else return false;
     return true;
 }

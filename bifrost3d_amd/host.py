@@ -45,6 +45,13 @@ def load_host_library() -> C.CDLL:
     lib.hiprh_scene_add_mesh.argtypes = [vp, fp, fp, fp, up, fp, C.c_uint, up, C.c_uint]
     lib.hiprh_scene_add_material.argtypes = [vp, C.POINTER(capi.HiprMaterial)]
     lib.hiprh_scene_add_texture.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.POINTER(C.c_ubyte), C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.hiprh_scene_add_environment.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.POINTER(C.c_ubyte), C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint]
+    lib.hiprh_scene_add_light.argtypes = [vp, C.POINTER(capi.HiprLight)]
+    lib.hiprh_scene_set_lights.argtypes = [vp, C.POINTER(capi.HiprLight), C.c_uint]
+    lib.hiprh_scene_lights.argtypes = [vp, C.POINTER(C.c_uint)]
+    lib.hiprh_scene_lights.restype = C.POINTER(capi.HiprLight)
+    lib.hiprh_scene_staged_environment_build.argtypes = [vp, C.c_uint, C.c_uint, C.POINTER(capi.HiprEnvironmentBuild)]
+    lib.hiprh_scene_adopt_lighting.argtypes = [vp, C.POINTER(capi.HiprLight), C.c_uint, C.c_int, C.c_uint, C.POINTER(capi.HiprLightingResult), C.POINTER(C.c_float), C.POINTER(capi.HiprLightSample)]
     lib.hiprh_scene_staged_growth.argtypes = [vp, C.POINTER(capi.HiprPoolGrowth), C.POINTER(capi.HiprInstanceEdit), C.c_uint]
     lib.hiprh_scene_materials.argtypes = [vp, C.POINTER(C.c_uint)]
     lib.hiprh_scene_materials.restype = C.POINTER(capi.HiprMaterial)
@@ -331,6 +338,58 @@ class Scene:
         if index < 0:
             raise capi.HiprError("hiprh_scene_add_texture failed")
         return int(index)
+
+    def add_environment(self, pixels: np.ndarray, width: int, height: int, texel_format: int, is_sRGB: bool = False, repeat=(True, False), linear=(True, True), sample_count: int = 1024) -> int:
+        """The scene given an environment from raw pixels through the HOST path: InfiniteAreaLight + presample_environment over the image, SceneBuilder::add_texture +
+        set_environment. `pixels` are the width x height texels of `texel_format` (capi.TEXEL_RGBA8 or TEXEL_RGBA32F); `linear` = (magnification, minification).
+        Returns the texture index; rebuild() before the description is read."""
+        pixels = np.ascontiguousarray(pixels).view(np.uint8).reshape(-1)
+        index = self.lib.hiprh_scene_add_environment(self.handle, width, height, texel_format, int(is_sRGB), pixels.ctypes.data_as(C.POINTER(C.c_ubyte)), pixels.nbytes, int(repeat[0]), int(repeat[1]),
+                                                     int(linear[0]), int(linear[1]), sample_count)
+        if index < 0:
+            raise capi.HiprError("hiprh_scene_add_environment failed")
+        return int(index)
+
+    def add_light(self, light: capi.HiprLight) -> None:
+        """SceneBuilder::add_light (the host path): rebuild() before the description is read."""
+        if self.lib.hiprh_scene_add_light(self.handle, C.byref(light)) != 1:
+            raise capi.HiprError("hiprh_scene_add_light failed")
+
+    def lights(self) -> list:
+        """Copies of the builder's lights, the presampled environment's (last) included."""
+        count = C.c_uint()
+        pointer = self.lib.hiprh_scene_lights(self.handle, C.byref(count))
+        return [capi.HiprLight.from_buffer_copy(bytes(pointer[k])) for k in range(count.value)]
+
+    def set_lights(self, lights) -> bool:
+        """SceneBuilder::set_lights: the light list of a built scene replaced in place, any count and types, the environment's light kept last."""
+        lights = list(lights)
+        status = self.lib.hiprh_scene_set_lights(self.handle, (capi.HiprLight * max(len(lights), 1))(*lights), len(lights))
+        if status < 0:
+            raise capi.HiprError("hiprh_scene_set_lights failed")
+        return status == 1
+
+    def staged_environment_build(self, texture_index: int, sample_count: int):
+        """SceneBuilder::staged_environment_build: the capi.HiprEnvironmentBuild Context.update_scene_lighting takes to build the environment of `texture_index` on the
+        device, or None for a texture the scene does not hold. Its pointers hold until the next call of this method."""
+        build = capi.HiprEnvironmentBuild()
+        status = self.lib.hiprh_scene_staged_environment_build(self.handle, texture_index, sample_count, C.byref(build))
+        if status < 0:
+            raise capi.HiprError("hiprh_scene_staged_environment_build failed")
+        return build if status == 1 else None
+
+    def adopt_lighting(self, lights, action: int, texture_index: int = 0, updated: dict | None = None) -> bool:
+        """SceneBuilder::adopt_lighting: the outcome of Context.update_scene_lighting (`updated`, its dict) taken over without a rebuild."""
+        lights = list(lights)
+        result = updated["result"] if updated else capi.HiprLightingResult()
+        pdf = updated["per_pixel_PDF"] if updated and action == capi.ENVIRONMENT_BUILD else None
+        samples = updated["samples"] if updated and action == capi.ENVIRONMENT_BUILD else None
+        status = self.lib.hiprh_scene_adopt_lighting(self.handle, (capi.HiprLight * max(len(lights), 1))(*lights), len(lights), action, texture_index, C.byref(result),
+                                                     pdf.ctypes.data_as(C.POINTER(C.c_float)) if pdf is not None else None,
+                                                     C.cast(samples.ctypes.data, C.POINTER(capi.HiprLightSample)) if samples is not None else None)
+        if status < 0:
+            raise capi.HiprError("hiprh_scene_adopt_lighting failed")
+        return status == 1
 
     def staged_scene_growth(self):
         """SceneBuilder::staged_scene_growth: (capi.HiprPoolGrowth, ctypes array of capi.HiprInstanceEdit) for everything since the last build or adoption -- what

@@ -222,7 +222,7 @@ struct Renderer::Implementation {
     HiprSceneState scene_state = {{0, 0, 0}, 3};                     // next_event_sample_count = 3, OR/Renderer.cpp:479
     std::unique_ptr<SceneBuilder> scene;
     std::map<unsigned int, uint32_t> scene_mesh_index;      // Bifrost mesh ID -> the scene builder's mesh
-    Renderer::SceneUpdateCounts scene_updates = {0, 0, 0, 0, 0, 0};
+    Renderer::SceneUpdateCounts scene_updates = {0, 0, 0, 0, 0, 0, 0};
     Renderer::SceneBuildCounts retired_builds = {0, 0};      // of the scene builders that are gone
     Renderer::SceneCollapseCounts retired_collapses = {0, 0};
     Renderer::SceneRebuildCounts scene_rebuilds = {0, 0};
@@ -517,6 +517,60 @@ struct Renderer::Implementation {
         return true;
     }
 
+    // The lighting tick on the device (HIPR_DEVICE_LIGHTING=1, opt-in; hipr_update_scene_lighting; OR/Renderer.cpp:852-1008: the reference rewrites its light buffer
+    // in place, :1136-1196: it presamples its environment without touching geometry): light sources created or destroyed, and a scene's environment map set to a
+    // texture the resident pools hold. Every camera with an uploaded scene takes the new light list and, for a new map, builds the PDF image and the samples from its
+    // resident texels (csrc/environment_build.h) -- the first with outputs, which the scene builder adopts without a rebuild. A camera that waits for its upload takes
+    // the whole description later. false: the caller takes the full path -- a new scene -- which is also what any refusal or error ends in. A map whose texture is
+    // new in the tick is not taken here: the tick takes the full path.
+    static bool device_lighting_wanted() {
+        const char* wanted = std::getenv("HIPR_DEVICE_LIGHTING");
+        return wanted && std::atoi(wanted) != 0;
+    }
+    bool update_lighting_on_the_device(TextureID environment_map) {
+        if (!scene || scene->has_staged_transforms() || scene->has_staged_edits()) return false;
+        CameraState* first = nullptr;
+        for (CameraState& c : per_camera_state) {
+            if (!c.context || !c.scene_uploaded) continue;      // uploads the description later, with everything in it
+            if (c.geometry_update_pending) return false;
+            if (!first) first = &c;
+        }
+        if (!first) return false;
+        const std::vector<HiprLight> lights = collect_lights();
+        int action = HIPR_ENVIRONMENT_KEEP;
+        uint32_t texture_index = 0;
+        SceneBuilder::StagedEnvironmentBuild staged;
+        std::vector<float> per_pixel_PDF;
+        std::vector<HiprLightSample> samples;
+        if (environment_map != TextureID::invalid_UID()) {
+            const ImageID image = Textures::get_image_ID(environment_map);
+            if (channel_count(Images::get_pixel_format(image)) != 4) return false;      // the full path says so and goes without the map
+            texture_index = environment_map.get_index();
+            if (!scene->staged_environment_build(texture_index, 8192, staged)) return false;      // presample_environment's default count
+            action = HIPR_ENVIRONMENT_BUILD;
+            per_pixel_PDF.resize(size_t(Images::get_width(image)) * staged.build.pdf_height);
+            samples.resize(staged.build.sample_count);
+        }
+        const HiprEnvironmentBuild* build = action == HIPR_ENVIRONMENT_BUILD ? &staged.build : nullptr;
+        for (CameraState& c : per_camera_state) c.drop_batch();
+        HiprLightingResult result = {};
+        if (hipr_group_update_scene_lighting(first->context, lights.data(), uint32_t(lights.size()), action, build, build ? per_pixel_PDF.data() : nullptr, per_pixel_PDF.size(),
+                                             build ? samples.data() : nullptr, uint32_t(samples.size()), &result) != HIPR_OK)
+            return false;
+        per_pixel_PDF.resize(size_t(result.pdf_width) * result.pdf_height);
+        samples.resize(result.sample_count);
+        if (!scene->adopt_lighting(lights, action, texture_index, result, action == HIPR_ENVIRONMENT_BUILD ? std::move(per_pixel_PDF) : std::vector<float>(),
+                                   action == HIPR_ENVIRONMENT_BUILD ? std::move(samples) : std::vector<HiprLightSample>()))
+            return false;
+        for (CameraState& c : per_camera_state) {
+            if (&c == first || !c.context || !c.scene_uploaded) continue;
+            HiprLightingResult same = {};
+            if (hipr_group_update_scene_lighting(c.context, lights.data(), uint32_t(lights.size()), action, build, nullptr, 0, nullptr, 0, &same) != HIPR_OK) c.scene_uploaded = false;
+        }
+        ++scene_updates.lighting_updates;
+        return true;
+    }
+
     // ---- handle_updates -----------------------------------------------------------------------------------------------
     void handle_updates() {
         bool should_reset_accumulations = false, scene_dirty = false, models_edited = false;
@@ -575,9 +629,13 @@ struct Renderer::Implementation {
             else materials_dirty = true;
         }
         // Lights (:852-1008): created or destroyed lights change the light count (a new scene description); updated ones are replaced in place.
-        bool lights_moved = false;
+        // HIPR_DEVICE_LIGHTING=1: a changed light count and an environment map set are dirt the resident scene can take (update_lighting_on_the_device), where
+        // lighting is the tick's only dirt; unset, they make a new scene as they always did.
+        const bool lighting_may_stay = scene && device_lighting_wanted();
+        bool lights_recounted = false, lights_moved = false;
+        TextureID environment_map_set = TextureID::invalid_UID();
         for (LightSourceID light_ID : LightSources::get_changed_lights()) {
-            if (LightSources::get_changes(light_ID).any_set(LightSources::Change::Created, LightSources::Change::Destroyed)) scene_dirty = true;
+            if (LightSources::get_changes(light_ID).any_set(LightSources::Change::Created, LightSources::Change::Destroyed)) (lighting_may_stay ? lights_recounted : scene_dirty) = true;
             else lights_moved = true;
             should_reset_accumulations = true;
         }
@@ -617,7 +675,8 @@ struct Renderer::Implementation {
                 continue;
             }
             if (changes.any_set(SceneRoots::Change::EnvironmentMap, SceneRoots::Change::Created) && SceneRoots::get_environment_map(scene_ID) != TextureID::invalid_UID()) {
-                scene_dirty = true;
+                if (lighting_may_stay && environment_map_set == TextureID::invalid_UID()) environment_map_set = SceneRoots::get_environment_map(scene_ID);
+                else scene_dirty = true;
                 should_reset_accumulations = true;
             }
             if (changes.any_set(SceneRoots::Change::EnvironmentTint, SceneRoots::Change::Created)) {
@@ -630,6 +689,13 @@ struct Renderer::Implementation {
         // Material edits are applied to the resident scene when they are the tick's only dirt; with anything else in the tick, or when the device path declines,
         // they make a new scene as they always did.
         if (materials_dirty) scene_dirty = true;
+        // Lighting edits likewise: with any other dirt in the tick -- a moved model, a material, a model, a pool that grows (the map's own texture included) -- or when
+        // the device path declines, they make a new scene.
+        if (lights_recounted || environment_map_set != TextureID::invalid_UID()) {
+            const bool only_dirt = !scene_dirty && !models_edited && !pools_grow && moved_models.empty() && changed_materials.empty() && material_assignments.empty();
+            if (only_dirt && update_lighting_on_the_device(environment_map_set)) lights_moved = false;      // the new list carries the moved lights as well
+            else scene_dirty = true;
+        }
         // Created and destroyed models likewise: with any other dirt in the tick they make a new scene.
         // (With pools that may grow, a material created in a free slot of the pool is the material edit below, and the models follow it.)
         if (models_edited && (!moved_models.empty() || lights_moved || (!changed_materials.empty() && !(pools_may_grow && pools_grow && only_created_materials)) || !material_assignments.empty())) scene_dirty = true;

@@ -2,6 +2,7 @@
 #include "SceneBuilder.h"
 
 #include "../csrc/material_rules.h"      // the flag rules, shared with the kernels that apply a material edit on the device
+#include "RNG.h"                         // the draw points of staged_environment_build
 
 #include <chrono>
 #include <cstdio>
@@ -642,6 +643,85 @@ bool SceneBuilder::replace_lights(const std::vector<HiprLight>& lights) {
     if (lights.size() + environment_lights != m_lights.size()) return false;
     std::copy(lights.begin(), lights.end(), m_lights.begin());      // the presampled environment light, if any, stays last
     return true;
+}
+
+bool SceneBuilder::set_lights(const std::vector<HiprLight>& lights) {
+    if (!m_built) return false;
+    for (const HiprLight& light : lights)
+        if ((light.flags & HIPR_LIGHT_TYPE_MASK) == HIPR_LIGHT_PRESAMPLED_ENVIRONMENT) return false;
+    m_lights = lights;
+    if (m_has_environment && m_environment_samples.size() > 1) {      // set_environment's rule: the environment's light stays last
+        HiprLight light = {};
+        light.flags = HIPR_LIGHT_PRESAMPLED_ENVIRONMENT;
+        m_lights.push_back(light);
+    }
+    m_desc.lights = m_lights.data(); m_desc.light_count = uint32_t(m_lights.size());
+    m_built_pools.lights = m_lights.size();      // the device follows: a growth staged afterwards is the device's to apply again
+    return true;
+}
+
+bool SceneBuilder::staged_environment_build(uint32_t texture_index, uint32_t sample_count, StagedEnvironmentBuild& staged) const {
+    staged = {};
+    if (texture_index == 0 || texture_index >= m_textures.size()) return false;
+    const HiprTexture& t = m_textures[texture_index];
+    const int height = int(std::max(t.height, 128u));      // InfiniteAreaLight::MINIMUM_PDF_HEIGHT
+    staged.row_sines.resize(size_t(height));
+    for (int y = 0; y < height; ++y) staged.row_sines[size_t(y)] = std::sin(PI<float>() * (y + 0.5f) / float(height));      // compute_distribution's sin_theta
+    if (t.is_sRGB) {
+        staged.srgb_decode.resize(256);
+        const float unorm8 = 1.0f / 255.0f;
+        for (int b = 0; b < 256; ++b) {      // get_pixel's sRGB_to_linear of the byte's value (Color.h:356-361)
+            const float v = (unsigned char)b * unorm8;
+            staged.srgb_decode[size_t(b)] = v < 0.04045f ? v * 0.0773993808f : std::pow(v * 0.9478672986f + 0.0521327014f, 2.4f);
+        }
+    }
+    // presample_environment's points in the order it visits them
+    unsigned int count = 1;
+    while (count < sample_count) count *= 2;
+    count = std::max(2u, count);
+    if (m_draw_points.size() != size_t(count) * 2) {      // the points depend on the count alone and cost tens of milliseconds at 8192: made once per count, kept
+        const int exponent = int(std::log2(float(count)));
+        std::vector<Vector2f> points(count);
+        RNG::fill_progressive_multijittered_bluenoise_samples(points.data(), points.data() + count);
+        m_draw_points.resize(size_t(count) * 2);
+        for (unsigned int i = 0; i < count; ++i) {
+            const unsigned int adjusted = RNG::reverse_bits(i) >> (32 - exponent);
+            m_draw_points[2 * size_t(i)] = points[adjusted].x;
+            m_draw_points[2 * size_t(i) + 1] = points[adjusted].y;
+        }
+    }
+    staged.draw_points = m_draw_points;
+    staged.build.environment_map_ID = int32_t(texture_index);
+    staged.build.row_sines = staged.row_sines.data();
+    staged.build.pdf_height = uint32_t(height);
+    staged.build.srgb_decode = t.is_sRGB ? staged.srgb_decode.data() : nullptr;
+    staged.build.draw_points = staged.draw_points.data();
+    staged.build.sample_count = count;
+    return true;
+}
+
+bool SceneBuilder::adopt_lighting(const std::vector<HiprLight>& lights, int environment_action, uint32_t texture_index, const HiprLightingResult& result, std::vector<float> per_pixel_PDF,
+                                  std::vector<HiprLightSample> samples) {
+    if (!m_built) return false;
+    for (const HiprLight& light : lights)
+        if ((light.flags & HIPR_LIGHT_TYPE_MASK) == HIPR_LIGHT_PRESAMPLED_ENVIRONMENT) return false;
+    if (environment_action == HIPR_ENVIRONMENT_BUILD) {
+        if (texture_index == 0 || texture_index >= m_textures.size() || result.sample_count == 0 || samples.size() != result.sample_count ||
+            per_pixel_PDF.size() != size_t(result.pdf_width) * result.pdf_height)
+            return false;
+        m_environment_PDF = std::move(per_pixel_PDF);
+        m_environment_samples = std::move(samples);
+        m_environment = {int32_t(texture_index), result.pdf_width, result.pdf_height, m_environment_PDF.data(), m_environment_samples.data(), uint32_t(m_environment_samples.size())};
+        m_has_environment = true;
+    } else if (environment_action == HIPR_ENVIRONMENT_REMOVE) {
+        m_environment_PDF.clear();
+        m_environment_samples.clear();
+        m_environment = {};
+        m_has_environment = false;
+    } else if (environment_action != HIPR_ENVIRONMENT_KEEP) return false;
+    m_environment_set_since = false;
+    m_desc.environment = m_has_environment ? &m_environment : nullptr;
+    return set_lights(lights);
 }
 
 HiprCameraState make_camera_state(const CameraDescription& camera, float aspect_ratio, uint32_t accumulations, float path_regularization_PDF_scale) {

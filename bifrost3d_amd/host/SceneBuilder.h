@@ -158,6 +158,28 @@ public:
     const std::vector<HiprInstance>& instances() const { return m_instances; }
     // The lights of a finalized scene replaced one for one (moved or re-coloured lights; the count must match).
     bool replace_lights(const std::vector<HiprLight>& lights);
+    // Lighting edits of a BUILT scene without a rebuild (what hipr_update_scene_lighting does to the resident scene; the reference rewrites its light buffer in
+    // place and presamples its environment without touching geometry, OR/Renderer.cpp:852-1008, :1136-1196). No triangle, tree or pool follows a light or the
+    // environment's data, so desc() is brought along in place and is then, in every array and scalar, what add_light / set_environment and rebuild() leave.
+    // set_lights: the light list replaced by `lights`, any count and any types, with the presampled environment's light -- which `lights` must not carry -- kept
+    // last. False, with nothing touched, before the scene is built or for a list that carries that light.
+    bool set_lights(const std::vector<HiprLight>& lights);
+    // What hipr_update_scene_lighting takes to build the environment of texture `texture_index` on the device: the three tables the host path evaluates through
+    // libm -- the sine of every PDF row (compute_distribution), the linear value of every sRGB byte (get_pixel), the progressive multi-jittered draw points in the
+    // order presample_environment visits them -- owned by `staged`, whose `build` points into it: they hold as long as `staged` lives. `sample_count` is rounded
+    // up to a power of two, at least 2, as presample_environment does. The points depend on the count alone and are the expensive table (61 ms at 8192): the builder
+    // keeps those of the last count asked for. False for a texture the builder does not hold.
+    struct StagedEnvironmentBuild {
+        HiprEnvironmentBuild build = {};
+        std::vector<float> row_sines, srgb_decode, draw_points;
+    };
+    bool staged_environment_build(uint32_t texture_index, uint32_t sample_count, StagedEnvironmentBuild& staged) const;
+    // The outcome of a hipr_update_scene_lighting taken over: `lights` as set_lights takes them; `environment_action` HIPR_ENVIRONMENT_KEEP, _REMOVE (the builder
+    // drops its environment), or _BUILD with the texture, the extents `result` reports and the PDF texels and samples the call handed out, which become the
+    // builder's as set_environment would take them. False, with nothing touched, where set_lights refuses, for an unknown action, or for arrays whose sizes are
+    // not the ones `result` reports.
+    bool adopt_lighting(const std::vector<HiprLight>& lights, int environment_action, uint32_t texture_index, const HiprLightingResult& result, std::vector<float> per_pixel_PDF,
+                        std::vector<HiprLightSample> samples);
 
     const HiprSceneDesc& desc() const { assert(!m_staged && "apply_staged_transforms() first: the instances lead the triangles and the trees"); return m_desc; }
     const HiprSceneState& state() const { return m_state; }
@@ -217,6 +239,7 @@ private:
     CollapseCounts m_collapse_counts;
     double m_built_bvh_area = 0.0;
     uint32_t m_bvh_max_depth_limit = 62;
+    mutable std::vector<float> m_draw_points;      // staged_environment_build: the draw points of the last sample count asked for
     std::vector<float> m_environment_PDF;
     std::vector<HiprLightSample> m_environment_samples;
     HiprEnvironment m_environment = {};

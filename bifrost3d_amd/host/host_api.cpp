@@ -474,6 +474,77 @@ int hiprh_scene_staged_growth(void* scene, HiprPoolGrowth* out_growth, HiprInsta
         return int(edits.size());
     } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_staged_growth: %s\n", e.what()); return -1; }
 }
+// A scene given an environment from raw pixels through the HOST path, the way add_procedural_environment does: the image and the texture in the Bifrost managers,
+// InfiniteAreaLight + presample_environment over them, SceneBuilder::add_texture + set_environment. `format` HIPR_TEXEL_RGBA8 or HIPR_TEXEL_RGBA32F. The caller
+// rebuilds (hiprh_scene_rebuild) before it reads the description. Returns the texture index, -1 on error.
+int hiprh_scene_add_environment(void* scene, unsigned width, unsigned height, unsigned format, int is_sRGB, const unsigned char* pixels, unsigned long long byte_count, int repeat_u, int repeat_v,
+                                int linear_magnification, int linear_minification, unsigned sample_count) {
+    if (!scene || !pixels || !width || !height || (format != HIPR_TEXEL_RGBA8 && format != HIPR_TEXEL_RGBA32F)) return -1;
+    if (byte_count != (format == HIPR_TEXEL_RGBA8 ? 4ull : 16ull) * width * height) return -1;
+    try {
+        using namespace Bifrost;
+        const Assets::ImageID image = Assets::Images::create2D("environment", format == HIPR_TEXEL_RGBA8 ? Assets::PixelFormat::RGBA32 : Assets::PixelFormat::RGBA_Float, is_sRGB != 0, width, height,
+                                                               pixels, size_t(byte_count));
+        const Assets::TextureID texture = Assets::Textures::create2D(image, linear_magnification ? Assets::MagnificationFilter::Linear : Assets::MagnificationFilter::None,
+                                                                     linear_minification ? Assets::MinificationFilter::Linear : Assets::MinificationFilter::None,
+                                                                     repeat_u ? Assets::WrapMode::Repeat : Assets::WrapMode::Clamp, repeat_v ? Assets::WrapMode::Repeat : Assets::WrapMode::Clamp);
+        const Assets::InfiniteAreaLight light(texture);
+        PresampledEnvironment presampled = presample_environment(light, sample_count);
+        ImageData data;
+        data.width = width; data.height = height; data.format = uint8_t(format); data.is_sRGB = is_sRGB != 0;
+        data.pixels.assign(pixels, pixels + byte_count);
+        SceneBuilder* sb = static_cast<SceneBuilder*>(scene);
+        const uint32_t texture_index = sb->add_texture(data, repeat_u != 0, repeat_v != 0, linear_magnification != 0, linear_minification != 0);
+        sb->set_environment(texture_index, presampled.pdf_width, presampled.pdf_height, std::move(presampled.per_pixel_PDF), std::move(presampled.samples));
+        Assets::Textures::destroy(texture);
+        Assets::Images::destroy(image);
+        return int(texture_index);
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_add_environment: %s\n", e.what()); return -1; }
+}
+// SceneBuilder::add_light (the host path: the caller rebuilds) and SceneBuilder::set_lights (a built scene's list replaced in place). 1 / 0 = done / refused, -1 on error.
+int hiprh_scene_add_light(void* scene, const HiprLight* light) {
+    if (!scene || !light) return -1;
+    try { static_cast<SceneBuilder*>(scene)->add_light(*light); return 1; }
+    catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_add_light: %s\n", e.what()); return -1; }
+}
+int hiprh_scene_set_lights(void* scene, const HiprLight* lights, unsigned count) {
+    if (!scene || (count && !lights)) return -1;
+    try { return static_cast<SceneBuilder*>(scene)->set_lights(std::vector<HiprLight>(lights, lights + count)) ? 1 : 0; }
+    catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_set_lights: %s\n", e.what()); return -1; }
+}
+const HiprLight* hiprh_scene_lights(void* scene, unsigned* out_count) {
+    if (!scene || !out_count) return nullptr;
+    const std::vector<HiprLight>& lights = static_cast<SceneBuilder*>(scene)->lights();
+    *out_count = unsigned(lights.size());
+    return lights.data();
+}
+// SceneBuilder::staged_environment_build: what hipr_update_scene_lighting takes to build the environment of `texture_index`. The pointers of `out_build` hold until the
+// next call of this function on the calling thread. 1 / 0 = staged / not a texture of the scene, -1 on error.
+int hiprh_scene_staged_environment_build(void* scene, unsigned texture_index, unsigned sample_count, HiprEnvironmentBuild* out_build) {
+    if (!scene || !out_build) return -1;
+    try {
+        static thread_local SceneBuilder::StagedEnvironmentBuild staged;
+        if (!static_cast<const SceneBuilder*>(scene)->staged_environment_build(texture_index, sample_count, staged)) return 0;
+        *out_build = staged.build;
+        return 1;
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_staged_environment_build: %s\n", e.what()); return -1; }
+}
+// SceneBuilder::adopt_lighting: the outcome of a hipr_update_scene_lighting taken over. `per_pixel_PDF` and `samples` are read for HIPR_ENVIRONMENT_BUILD only, with the
+// extents `result` reports. 1 / 0 = adopted / refused, -1 on error.
+int hiprh_scene_adopt_lighting(void* scene, const HiprLight* lights, unsigned count, int environment_action, unsigned texture_index, const HiprLightingResult* result, const float* per_pixel_PDF,
+                               const HiprLightSample* samples) {
+    if (!scene || !result || (count && !lights)) return -1;
+    try {
+        std::vector<float> pdf;
+        std::vector<HiprLightSample> drawn;
+        if (environment_action == HIPR_ENVIRONMENT_BUILD) {
+            if (!per_pixel_PDF || !samples) return -1;
+            pdf.assign(per_pixel_PDF, per_pixel_PDF + size_t(result->pdf_width) * result->pdf_height);
+            drawn.assign(samples, samples + result->sample_count);
+        }
+        return static_cast<SceneBuilder*>(scene)->adopt_lighting(std::vector<HiprLight>(lights, lights + count), environment_action, texture_index, *result, std::move(pdf), std::move(drawn)) ? 1 : 0;
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_adopt_lighting: %s\n", e.what()); return -1; }
+}
 // out[0] = calls of hiprh_scene_adopt_trees that adopted, out[1] = calls that refused.
 int hiprh_scene_rebuild_counts(void* scene, unsigned* out2) {
     if (!scene || !out2) return -1;

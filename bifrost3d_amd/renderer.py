@@ -240,6 +240,41 @@ class Context:
             self._resident_counts = (counts[0], counts[1], counts[2] + growth.material_count)
         return status
 
+    def update_scene_lighting(self, lights=(), action: int = capi.ENVIRONMENT_KEEP, build=None, read_back: bool = True, group=None, capacities=None) -> dict:
+        """hipr_update_scene_lighting: the lights of the resident scene replaced by `lights` (capi.HiprLight, WITHOUT the environment's) and the environment kept,
+        removed or -- `build`, a capi.HiprEnvironmentBuild (Scene.staged_environment_build makes it) -- rebuilt on the device from the resident texels. Returns a dict of
+        status and, when it is HIPR_OK, result (capi.HiprLightingResult), pdf_width, pdf_height, sample_count, disabled, light_count, switches and -- a build with
+        `read_back` -- per_pixel_PDF (float32) and samples ((n, 8) float32) as Scene.adopt_lighting takes them. `capacities`: (PDF floats, samples) of the read-back
+        arrays. `group`: a HiprGroup handle, for hipr_group_update_scene_lighting."""
+        lights = list(lights) if lights is not None else None
+        array = (capi.HiprLight * max(len(lights), 1))(*lights) if lights is not None else None
+        pdf = samples = None
+        if build is not None and read_back:
+            texture = self.read_scene_buffer(capi.SCENE_BUFFER_TEXTURES)
+            width = int(texture[build.environment_map_ID][0]) if 0 < build.environment_map_ID < len(texture) else 1
+            pdf_room, sample_room = capacities or (width * build.pdf_height, build.sample_count)
+            pdf, samples = np.zeros(max(pdf_room, 1), np.float32), np.zeros((max(sample_room, 1), 8), np.float32)
+        result = capi.HiprLightingResult()
+        call, handle = (self.lib.hipr_group_update_scene_lighting, group) if group is not None else (self.lib.hipr_update_scene_lighting, self.handle)
+        status = call(handle, array, len(lights) if lights is not None else 1, action, C.byref(build) if build is not None else None,
+                      pdf.ctypes.data_as(C.POINTER(C.c_float)) if pdf is not None else None, (capacities[0] if capacities else len(pdf)) if pdf is not None else 0,
+                      C.cast(samples.ctypes.data, C.POINTER(capi.HiprLightSample)) if samples is not None else None, (capacities[1] if capacities else len(samples)) if samples is not None else 0,
+                      C.byref(result))
+        if status != capi.HIPR_OK:
+            return dict(status=status)
+        out = dict(status=status, result=result, pdf_width=result.pdf_width, pdf_height=result.pdf_height, sample_count=result.sample_count, disabled=bool(result.importance_sampling_disabled),
+                   light_count=result.light_count, switches=result.switches)
+        if pdf is not None:
+            out["per_pixel_PDF"] = np.ascontiguousarray(pdf[:result.pdf_width * result.pdf_height])
+            out["samples"] = np.ascontiguousarray(samples[:result.sample_count])
+        return out
+
+    def lighting_times(self) -> dict:
+        """Milliseconds of the last update_scene_lighting: allocations + uploads, kernels, the host's finish of the samples, read-back."""
+        out = (C.c_double * 4)()
+        self._check(self.lib.hipr_debug_lighting_times(self.handle, out), "hipr_debug_lighting_times")
+        return dict(upload=out[0], kernels=out[1], finish=out[2], readback=out[3])
+
     def append_times(self) -> dict:
         """Milliseconds of the last append_scene_pools: the new allocations, the device-to-device copies of the resident parts, the tails with the mirror segments."""
         out = (C.c_double * 3)()
@@ -264,7 +299,8 @@ class Context:
         the device's count says (hipr_debug_scene_buffer_bytes): _INDICES -> (words,) uint32, _GEOMETRY -> (vertices, 4), _TEXCOORDS -> (vertices, 2), _TINTS -> (vertices,),
         _EMISSIONS -> (vertices, 3), _TEXTURES -> (textures, 6), all uint32 words, _TEXELS -> (bytes,) uint8; a pool the device does not hold has no rows."""
         pools = {capi.SCENE_BUFFER_INDICES: (1, np.uint32), capi.SCENE_BUFFER_GEOMETRY: (4, np.uint32), capi.SCENE_BUFFER_TEXCOORDS: (2, np.uint32), capi.SCENE_BUFFER_TINTS: (1, np.uint32),
-                 capi.SCENE_BUFFER_EMISSIONS: (3, np.uint32), capi.SCENE_BUFFER_TEXTURES: (6, np.uint32), capi.SCENE_BUFFER_TEXELS: (1, np.uint8)}
+                 capi.SCENE_BUFFER_EMISSIONS: (3, np.uint32), capi.SCENE_BUFFER_TEXTURES: (6, np.uint32), capi.SCENE_BUFFER_TEXELS: (1, np.uint8),
+                 capi.SCENE_BUFFER_LIGHTS: (12, np.uint32), capi.SCENE_BUFFER_ENVIRONMENT_PDF: (1, np.uint32), capi.SCENE_BUFFER_ENVIRONMENT_SAMPLES: (8, np.uint32)}
         if which in pools:
             width, dtype = pools[which]
             size = capi.c_u64()

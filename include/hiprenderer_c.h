@@ -548,6 +548,53 @@ typedef struct HiprPoolGrowth {
     uint32_t index_count, segment_count, material_count, texture_count;
 } HiprPoolGrowth;
 int hipr_append_scene_pools(HiprContext* context, const HiprPoolGrowth* growth);
+/* The lights and the environment of the RESIDENT scene replaced on the device (the reference rewrites its light buffer in place, OR/Renderer.cpp:852-1008, and builds
+ * its presampled environment without touching geometry, :1136-1196, OR/PresampledEnvironmentMap.cpp:19-101): a lamp added, removed or changed in kind, the sky set,
+ * swapped or taken away move no triangle, no tree, no material and no texel, so no flatten on the host and no upload of any pool is needed. `lights` is the NEW light
+ * list, any count and any types, WITHOUT the environment's light. `environment_action`: HIPR_ENVIRONMENT_KEEP leaves the resident environment, _REMOVE takes it away
+ * (the environment is the constant tint again), _BUILD makes the per-texel PDF image and the presampled light samples of `build->environment_map_ID` -- a texture the
+ * RESIDENT pool holds: hipr_append_scene_pools brings a new one first -- by kernels (csrc/environment_build.h) over the resident texels. The three arrays of
+ * `build` carry what the host path evaluates through libm, so that the device evaluates no transcendental: the sine of every PDF row, the linear value of every
+ * sRGB byte, the progressive multi-jittered draw points; what is left for the device is + - x /, comparisons and conversions in correctly rounded f32. The
+ * direction and the solid angle PDF of each sample are finished on the host inside the call (std::sin / std::cos; sample_count x 32 bytes read back and uploaded).
+ * The light of type HIPR_LIGHT_PRESAMPLED_ENVIRONMENT is appended last by the call itself, exactly when the environment resident afterwards has more than one sample
+ * (SceneBuilder::set_environment's rule). An image whose integral is below 1e-5 gives presample_environment's disabled form: one PDF texel of 0, one sample with a
+ * zero PDF, no light appended. Afterwards the light buffer, the environment's PDF and sample buffers, the environment fields and the light count the kernels take, and
+ * the kernel instantiations picked from the pools are, byte for byte, what SceneBuilder::add_light, InfiniteAreaLight + presample_environment + set_environment,
+ * rebuild() and hipr_upload_scene on a fresh context leave. `out_per_pixel_PDF` (`pdf_capacity` floats) and `out_samples` (`sample_capacity` records) receive what
+ * a BUILD made, for the host's description to follow; `out` the extents as resident. The call accepts the states hipr_append_scene_pools accepts (ready, or awaiting a
+ * rebuild after a refit) and leaves the state it found. Checked on the host before the device is touched, each leaving the scene as found:
+ *   HIPR_ERROR_NOT_READY          no scene, or a scene a failed call left behind;
+ *   HIPR_ERROR_INVALID_ARGUMENT   a null `out`; a null array with a non-zero count; a light of type HIPR_LIGHT_PRESAMPLED_ENVIRONMENT in `lights`; an action outside the
+ *                                 enum; _BUILD without `build`, or `build` with another action; a texture index of 0 or outside the resident pool; `pdf_height` other
+ *                                 than max(texture height, 128); no `srgb_decode` for an sRGB texture, or one for a linear texture; a sample count that is no power of
+ *                                 two >= 2; a draw point outside [0, 1); a table value that is not finite; an output with less room than the build can need;
+ *   HIPR_ERROR_UNSUPPORTED        a texture that is neither RGBA8 nor RGBA32F (as at upload); an sRGB texture of floats (a table of bytes cannot serve it); a PDF image
+ *                                 of more than 2^30 texels.
+ * Scratch (about three PDF images; kept with the context up to 128 MiB, freed when the call returns beyond that) and every new buffer are allocated before anything
+ * resident is written: a failed allocation is HIPR_ERROR_OUT_OF_MEMORY and leaves the scene as found. A HIP failure after that leaves no scene, as with the other
+ * writers. */
+typedef struct HiprEnvironmentBuild {
+    int32_t  environment_map_ID;   /* a texture of the RESIDENT pool, RGBA8 or RGBA32F */
+    const float* row_sines;        /* pdf_height values: sin(pi (y + 0.5) / pdf_height) as the caller's libm gives them */
+    uint32_t pdf_height;           /* must be max(texture height, 128) */
+    const float* srgb_decode;      /* 256 values, linear value of byte b; NULL for a texture that is not sRGB */
+    const float* draw_points;      /* 2 x sample_count, in the order the samples are stored (the caller has applied the bit reversal) */
+    uint32_t sample_count;         /* a power of two >= 2 */
+} HiprEnvironmentBuild;
+enum { HIPR_ENVIRONMENT_KEEP = 0, HIPR_ENVIRONMENT_REMOVE = 1, HIPR_ENVIRONMENT_BUILD = 2 };
+typedef struct HiprLightingResult {
+    uint32_t pdf_width, pdf_height, sample_count;      /* the environment as resident afterwards; zeros without one */
+    uint32_t importance_sampling_disabled;             /* 1: this call's build met an image integral below 1e-5 and left the disabled form */
+    uint32_t light_count;                              /* as resident afterwards, the environment's light included */
+    uint32_t switches;                                 /* the kernel instantiations derived from the pools afterwards: HIPR_SWITCH_* */
+} HiprLightingResult;
+enum { HIPR_SWITCH_TEXTURES = 1, HIPR_SWITCH_ENVIRONMENT = 2 };
+int hipr_update_scene_lighting(HiprContext* context, const HiprLight* lights, uint32_t light_count,   /* WITHOUT the environment's light */
+                               int environment_action, const HiprEnvironmentBuild* build,
+                               float* out_per_pixel_PDF /* may be NULL */, uint64_t pdf_capacity,
+                               HiprLightSample* out_samples /* may be NULL */, uint32_t sample_capacity,
+                               HiprLightingResult* out);
 int hipr_set_scene_state(HiprContext* context, const HiprSceneState* state);
 
 /* Entry points, numbered like OR/Types.h:33-44. set_backend() of the host renderer maps Backend values onto them
@@ -641,6 +688,9 @@ int hipr_group_edit_scene_instances(HiprGroup* group, const HiprInstanceEdit* ed
                                     uint32_t* out_order, uint32_t order_capacity, HiprSlot8* out_slots, uint32_t slot_capacity,
                                     HiprSceneEditResult* out);   /* every member edits; member 0's arrays are handed out; their results must agree */
 int hipr_group_append_scene_pools(HiprGroup* group, const HiprPoolGrowth* growth);   /* every member checks before any member writes */
+int hipr_group_update_scene_lighting(HiprGroup* group, const HiprLight* lights, uint32_t light_count, int environment_action, const HiprEnvironmentBuild* build,
+                                     float* out_per_pixel_PDF, uint64_t pdf_capacity, HiprLightSample* out_samples, uint32_t sample_capacity,
+                                     HiprLightingResult* out);   /* every member checks before any member writes; member 0's arrays are handed out; their results must agree */
 int hipr_group_update_scene_materials(HiprGroup* group, const HiprMaterialUpdate* materials, uint32_t material_count,
                                       const HiprInstanceMaterial* assignments, uint32_t assignment_count);   /* every member checks before any member writes */
 int hipr_group_set_scene_state(HiprGroup* group, const HiprSceneState* state);
@@ -795,7 +845,10 @@ int hipr_debug_classify_hits(HiprContext* context, const float* hits_n4, uint32_
 enum { HIPR_SCENE_BUFFER_TRIANGLES = 0, HIPR_SCENE_BUFFER_WIDE8_SLOTS = 1, HIPR_SCENE_BUFFER_TRACE_TRIANGLES = 2, HIPR_SCENE_BUFFER_SHADE_TRIANGLES = 3,
        HIPR_SCENE_BUFFER_TRIANGLE_CLASS = 4, HIPR_SCENE_BUFFER_MATERIALS = 5, HIPR_SCENE_BUFFER_INSTANCES = 6, HIPR_SCENE_BUFFER_NODES = 7 /* the BVH2 */,
        HIPR_SCENE_BUFFER_INDICES = 8, HIPR_SCENE_BUFFER_GEOMETRY = 9, HIPR_SCENE_BUFFER_TEXCOORDS = 10, HIPR_SCENE_BUFFER_TINTS = 11, HIPR_SCENE_BUFFER_EMISSIONS = 12,
-       HIPR_SCENE_BUFFER_TEXTURES = 13, HIPR_SCENE_BUFFER_TEXELS = 14 };
+       HIPR_SCENE_BUFFER_TEXTURES = 13, HIPR_SCENE_BUFFER_TEXELS = 14,
+       /* what hipr_update_scene_lighting writes: HiprLight[light_count], the environment's pdf_width x pdf_height floats and its HiprLightSample[sample_count]
+          (no environment: zero bytes) */
+       HIPR_SCENE_BUFFER_LIGHTS = 15, HIPR_SCENE_BUFFER_ENVIRONMENT_PDF = 16, HIPR_SCENE_BUFFER_ENVIRONMENT_SAMPLES = 17 };
 int hipr_debug_read_scene_buffer(HiprContext* context, int which, void* out, uint64_t capacity_bytes);
 int hipr_debug_scene_buffer_bytes(HiprContext* context, int which, uint64_t* out_bytes);
 /* Milliseconds of the context's last successful hipr_append_scene_pools that did any work: the new allocations (the host's clock), the device-to-device copies of
@@ -813,6 +866,9 @@ int hipr_debug_collapse4_times(HiprContext* context, double* out4_ms);
 /* The same for the context's last successful hipr_rebuild_scene_trees: the flatten order, the BVH2 build, the hand-over and the collapse with its slots copied to the
  * host, the new resident arrays with what is derived from them, the read-back of the outputs (tools/device_rebuild_probe.py). */
 int hipr_debug_rebuild_times(HiprContext* context, double* out5_ms);
+/* ... and for the context's last successful hipr_update_scene_lighting: the allocations with the uploads of the tables and the lights queued (the host's clock), the
+ * kernels (between events on the stream: no synchronise is added for them), the host's finish of the samples, the read-back with the samples' upload. */
+int hipr_debug_lighting_times(HiprContext* context, double* out4_ms);
 
 #ifdef __cplusplus
 }
