@@ -339,10 +339,10 @@ HD void shade_path(const DeviceScene& sc, const HiprCameraState& cam, int entry,
 struct ShadeInputs {
     uint32_t entry;        // the queue entry (HIPR_DEAD_SLOT: none)
     uint2 meta;            // slot, last accepted triangle
-    float4 o, d, t, hit;   // origin + tmin (fetched with the geometry, and only where it is used: shade_fetch_origin), direction + pdf, throughput + bounces, (t, u, v, id)
+    float4 o, d, t, hit;   // origin + tmin and direction + pdf (fetched with the geometry, by the kind of hit: shade_fetch_by_kind), throughput + bounces, (t, u, v, id)
 };
 
-// `i`: the queue entry, or HIPR_DEAD_SLOT for none (past the end of the queue).
+// `i`: the queue entry, or HIPR_DEAD_SLOT for none (past the end of the queue). The first stage: what is read whatever the ray hit.
 HD ShadeInputs shade_fetch_inputs(const PathState& in, const float4* hits, uint32_t i) {
     ShadeInputs r;
     r.entry = i;
@@ -350,7 +350,7 @@ HD ShadeInputs shade_fetch_inputs(const PathState& in, const float4* hits, uint3
     r.o = r.d = r.t = make_float4(0, 0, 0, 0);
     r.hit = make_float4(0, 0, 0, __uint_as_float(HIPR_HIT_MISS));
     if (i != HIPR_DEAD_SLOT) {
-        r.meta = in.meta[i]; r.d = in.d_pdf[i]; r.hit = hits[i];
+        r.meta = in.meta[i]; r.hit = hits[i];
         r.t = in.thr_bounces ? in.thr_bounces[i] : make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(0u));      // camera rays (bounce 0): k_generate leaves these 16 B unwritten
     }
     return r;
@@ -372,12 +372,31 @@ HD bool shade_hits_triangle(const ShadeInputs& in) {
     const uint32_t id = __float_as_uint(in.hit.w);
     return in.meta.x != HIPR_DEAD_SLOT && id != HIPR_HIT_MISS && !(id & HIPR_HIT_LIGHT);
 }
-// The ray's origin, one stage behind the other inputs: known to be needed once the hit id is there. Misses and light hits use it (environment lookup, light
-// evaluation), surface hits do not -- in the listing's order whole batches skip the 16 B (profiles/r04_ab_shade_queue_bytes.txt).
+// The second stage, one behind the other inputs: once the hit id is there, an entry fetches what its kind of hit reads in shade_path and nothing else
+// (profiles/ab_shade_ray_kinds.txt; a byte of queue traffic has a measured price, profiles/r04_ab_shade_queue_bytes.txt):
+//   surface hit   direction + pdf; its origin only where the hit is rejected, on the spot (shade_path origin_of_entry)
+//   light hit     direction + pdf and origin + tmin (light_evaluate_intersection)
+//   miss          direction + pdf only under an environment map (`environment_lookup`: TEXTURES >= 2 && sc.env_map_ID; a constant sky is the tint whatever the
+//                 direction), and its path's radiance[slot] into r.o, the four registers the origin would have taken: all a miss does is add to that value,
+//                 and k_shade adds to the copy fetched here, a batch ahead, instead of waiting for the load inside the batch
+//   dead slot     nothing
+//   AOV entries   origin and direction of every live entry (the depth entry reads both for a miss as well)
+// Why radiance[slot] may be read a batch before it is added to: a queue holds a path at most once, so during the kernel the one lane that shades the entry is the
+// only reader or writer of radiance[slot] (every other add of k_shade goes to the slot of ITS entry); the trace kernel's shadow sums into the same array are other
+// launches on the same stream, before or after this one; the wavefront that co-runs on the other stream owns other slots.
 template <bool AOV>
-HD void shade_fetch_origin(const PathState& in, ShadeInputs& r) {
-    if (r.entry != HIPR_DEAD_SLOT && r.meta.x != HIPR_DEAD_SLOT && (AOV || !shade_hits_triangle(r))) r.o = in.o_tmin[r.entry];
+HD void shade_fetch_by_kind(const PathState& in, const float4* radiance, bool environment_lookup, ShadeInputs& r) {
+    if (r.meta.x == HIPR_DEAD_SLOT) return;      // past the end of the queue (shade_fetch_inputs), or a dead slot in it
+    const uint32_t id = __float_as_uint(r.hit.w);
+    const bool miss = id == HIPR_HIT_MISS, light = !miss && (id & HIPR_HIT_LIGHT) != 0u;
+    if (AOV || !miss || environment_lookup) r.d = in.d_pdf[r.entry];
+    // one load into r.o, from the array the kind names
+    const float4* o = !AOV && miss ? radiance + r.meta.x : in.o_tmin + r.entry;
+    if (AOV || miss || light) r.o = *o;
 }
+// Is r.o the path's radiance (shade_fetch_by_kind) and not an origin?
+template <bool AOV>
+HD bool shade_holds_radiance(const ShadeInputs& r) { return !AOV && r.meta.x != HIPR_DEAD_SLOT && __float_as_uint(r.hit.w) == HIPR_HIT_MISS; }
 HD ShadeGeometry shade_fetch_geometry(const DeviceScene& sc, const ShadeInputs& in) {
     ShadeGeometry g;
     g.ta = g.tb = g.tc = g.s0 = g.s1 = g.s2 = g.s3 = g.s4 = g.s5 = make_float4(0, 0, 0, 0);
@@ -453,8 +472,9 @@ __global__ __launch_bounds__(SHADE_BLOCK, shade_waves_per_simd(PART)) void k_sha
     sc.tables.alpha = s_alpha;
     if (lights_in_lds) sc.lights = s_lights;
 #endif
+    const bool environment_lookup = TEXTURES >= 2 && sc.env_map_ID != 0;      // a miss reads its direction (shade_path's miss program)
     ShadeGeometry geo = shade_fetch_geometry(sc, cur);
-    shade_fetch_origin<AOV>(in, cur);
+    shade_fetch_by_kind<AOV>(in, radiance, environment_lookup, cur);
     HiprMaterial mat = shade_fetch_material(sc, cur, geo);
 #if HIPR_SHADE_ONE_BARRIER
     if (threadIdx.x < 2) s_arrivals[threadIdx.x] = 0ull;
@@ -495,14 +515,16 @@ __global__ __launch_bounds__(SHADE_BLOCK, shade_waves_per_simd(PART)) void k_sha
                                           __float_as_uint(cur.t.w), cur.meta.y, pixel_hash, accumulation, cur.hit, geo, mat, nee_kept_a_sample, so);
             if (PART == SHADE_PART_NEE && so.nee_reached) nee_flags[cur.entry] = so.nee_valid ? 1 : 0;
             if (so.add_radiance.x != 0.0f || so.add_radiance.y != 0.0f || so.add_radiance.z != 0.0f) {
-                float4 acc = radiance[slot];
+                // a miss adds to the value fetched with its inputs (shade_fetch_by_kind: nothing else touches radiance[slot] during the kernel); every other
+                // kind -- a light hit, the rare emitting surface, the AOV entries -- reads it here
+                float4 acc = shade_holds_radiance<AOV>(cur) ? cur.o : radiance[slot];
                 acc.x += so.add_radiance.x; acc.y += so.add_radiance.y; acc.z += so.add_radiance.z;
                 radiance[slot] = acc;
             }
         }
         // the hit id of the next batch has arrived by now: request its triangle and shading record
         geo = shade_fetch_geometry(sc, next);
-        shade_fetch_origin<AOV>(in, next);
+        shade_fetch_by_kind<AOV>(in, radiance, environment_lookup, next);
 
 #if HIPR_SHADE_ONE_BARRIER
         // ---- compaction: ballot + prefix popcount in the wave; the waves of the block take their places in the block's stretch of both queues in the

@@ -177,7 +177,14 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
         }
         // the loads: nothing below reads what they return before all of them are under way
         float4 acc = make_float4(0, 0, 0, 0);      // (left undefined for the lanes that load nothing, these records cost the loop its registers: scratch in every instantiation)
-        if constexpr (MODE != TRACE_CLOSEST) if (finished && is_shadow) acc = radiance[pay_k];
+        // A shadow ray that ended fully shadowed carries exactly +0 in every component (the transmittance code sets it), and x + (+0) = x for every x but -0, which a
+        // radiance slot never holds: k_generate starts it at +0, and under round to nearest a sum of two floats is -0 only where both are -0. Such a ray neither loads nor
+        // stores its slot -- 32 scattered bytes that changed nothing. In the instantiations without the coverage code and without instrumentation only: the others pay for
+        // the compare with 4 to 8 B more scratch (profiles/ab_shade_ray_kinds.txt, resource lines) and keep the unconditional sum.
+        constexpr bool SKIP_ZERO_SUMS = !COVERAGE && !INSTRUMENT;
+        bool adds_nothing = false;
+        if constexpr (SKIP_ZERO_SUMS) adds_nothing = pay_x == 0.0f && pay_y == 0.0f && pay_z == 0.0f;
+        if constexpr (MODE != TRACE_CLOSEST) if (finished && is_shadow && !adds_nothing) acc = radiance[pay_k];
         bool new_is_shadow = MODE == TRACE_SHADOW;
         uint32_t entry = 0;
         uint2 meta = make_uint2(0u, HIPR_NO_TRIANGLE);
@@ -203,7 +210,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
             if (is_shadow) {
                 if constexpr (MODE != TRACE_CLOSEST) {
                     acc.x += pay_x; acc.y += pay_y; acc.z += pay_z;
-                    radiance[pay_k] = acc;
+                    if (!adds_nothing) radiance[pay_k] = acc;
                 }
             } else if constexpr (MODE != TRACE_SHADOW) {    // analytic area lights, LightSources.cu:31-70, in the order of the scene's list
                 if (analytic_lights == 1) {
