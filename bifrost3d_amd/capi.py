@@ -171,6 +171,34 @@ SWITCH_TEXTURES, SWITCH_ENVIRONMENT = 1, 2
 LIGHT_NONE, LIGHT_SPHERE, LIGHT_DIRECTIONAL, LIGHT_ENVIRONMENT, LIGHT_PRESAMPLED_ENVIRONMENT, LIGHT_SPOT, LIGHT_TYPE_MASK = 0, 1, 2, 3, 4, 5, 7
 
 
+class HiprTexelEdit(C.Structure):
+    _fields_ = [("texture_index", c_u32), ("x", c_u32), ("y", c_u32), ("width", c_u32), ("height", c_u32), ("texels", C.c_void_p), ("row_pitch_bytes", c_u64)]
+
+
+class HiprTexelUpdateResult(C.Structure):
+    _fields_ = [("candidate_triangles", c_u32), ("changed_triangles", c_u32), ("all_triangles_opaque", c_u32), ("environment_stale", c_u32)]
+
+
+def texel_edits(edits):
+    """(texture index, x, y, pixels) tuples -- `pixels` a C-contiguous array of (height, width[, channels]) texels in the texture's resident format, or
+    (texture index, x, y, width, height, pixels, row pitch in bytes) with the rows of `pixels` a pitch apart -- as the HiprTexelEdit array of hipr_update_scene_texels
+    (one spare element: never a null array). Returns (array, keep-alive): the array points into the arrays of keep-alive."""
+    import numpy as np
+    edits = list(edits)
+    array, keep = (HiprTexelEdit * max(len(edits), 1))(), []
+    for k, edit in enumerate(edits):
+        if len(edit) == 4:
+            texture, x, y, pixels = edit
+            pixels = np.ascontiguousarray(pixels)
+            height, width, pitch = pixels.shape[0], pixels.shape[1], pixels.strides[0]
+        else:
+            texture, x, y, width, height, pixels, pitch = edit
+            pixels = np.ascontiguousarray(pixels) if pixels is not None else None
+        keep.append(pixels)
+        array[k] = HiprTexelEdit(int(texture), int(x), int(y), int(width), int(height), pixels.ctypes.data if pixels is not None else None, int(pitch))
+    return array, keep
+
+
 class HiprRefitResult(C.Structure):
     _fields_ = [("needs_rebuild", c_i32), ("child_half_area", C.c_double), ("uploaded_half_area", C.c_double), ("grid_min", c_f * 3), ("grid_cell", c_f * 3)]
 
@@ -229,11 +257,12 @@ assert C.sizeof(HiprTexture) == 24 and C.sizeof(HiprCameraState) == 180 and C.si
 assert C.sizeof(HiprInstanceEdit) == 88 and C.sizeof(HiprSceneEditResult) == 72
 assert C.sizeof(HiprIndexSegment) == 8 and C.sizeof(HiprPoolGrowth) == 112
 assert C.sizeof(HiprEnvironmentBuild) == 48 and C.sizeof(HiprLightingResult) == 24 and C.sizeof(HiprLightSample) == 32
+assert C.sizeof(HiprTexelEdit) == 40 and C.sizeof(HiprTexelUpdateResult) == 16
 
 # Every symbol include/hiprenderer_c.h declares; tests check the library exports all of them.
 C_ABI_SYMBOLS = (
     "hipr_create", "hipr_destroy", "hipr_last_error", "hipr_device_count", "hipr_set_stream",
-    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_build_bvh2", "hipr_group_build_bvh2", "hipr_debug_build_times", "hipr_build_wide8", "hipr_group_build_wide8", "hipr_debug_collapse_times", "hipr_build_wide4", "hipr_group_build_wide4", "hipr_debug_collapse4_times", "hipr_rebuild_scene_trees", "hipr_group_rebuild_scene_trees", "hipr_edit_scene_instances", "hipr_group_edit_scene_instances", "hipr_append_scene_pools", "hipr_group_append_scene_pools", "hipr_update_scene_lighting", "hipr_group_update_scene_lighting", "hipr_debug_lighting_times", "hipr_debug_scene_buffer_bytes", "hipr_debug_append_times", "hipr_debug_rebuild_times", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
+    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_build_bvh2", "hipr_group_build_bvh2", "hipr_debug_build_times", "hipr_build_wide8", "hipr_group_build_wide8", "hipr_debug_collapse_times", "hipr_build_wide4", "hipr_group_build_wide4", "hipr_debug_collapse4_times", "hipr_rebuild_scene_trees", "hipr_group_rebuild_scene_trees", "hipr_edit_scene_instances", "hipr_group_edit_scene_instances", "hipr_append_scene_pools", "hipr_group_append_scene_pools", "hipr_update_scene_lighting", "hipr_group_update_scene_lighting", "hipr_debug_lighting_times", "hipr_update_scene_texels", "hipr_group_update_scene_texels", "hipr_debug_texel_update_times", "hipr_debug_scene_buffer_bytes", "hipr_debug_append_times", "hipr_debug_rebuild_times", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
     "hipr_set_frame", "hipr_owned_pixel_count",
     "hipr_render_pass", "hipr_set_samples_per_pass", "hipr_trace_pass", "hipr_accumulate_samples", "hipr_read_accumulation", "hipr_scatter_tiles", "hipr_synchronize", "hipr_get_counters",
     "hipr_device_malloc", "hipr_device_free", "hipr_device_memset", "hipr_copy_to_host", "hipr_present_flipped",
@@ -301,6 +330,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.hipr_update_scene_lighting.argtypes = [vp] + lighting
     lib.hipr_group_update_scene_lighting.argtypes = [vp] + lighting
     lib.hipr_debug_lighting_times.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.hipr_update_scene_texels.argtypes = [vp, C.POINTER(HiprTexelEdit), c_u32, C.POINTER(HiprTexelUpdateResult)]
+    lib.hipr_group_update_scene_texels.argtypes = [vp, C.POINTER(HiprTexelEdit), c_u32, C.POINTER(HiprTexelUpdateResult)]
+    lib.hipr_debug_texel_update_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.hipr_debug_scene_buffer_bytes.argtypes = [vp, C.c_int, C.POINTER(c_u64)]
     lib.hipr_debug_append_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.hipr_debug_rebuild_times.argtypes = [vp, C.POINTER(C.c_double)]

@@ -99,6 +99,7 @@ constexpr int HOST_COUNT_WORDS = 8 + COUNT_LINES * COUNT_PAIR_STRIDE;   // pinne
 
 // What the argument checks of a description derive on their way (preflight_scene).
 struct LightingScratch;      // below, with the other scratches
+struct TexelScratch;
 
 struct Preflight {
     uint32_t wide_stack_need = 0;       // worst-case stack need of the 4-wide tree: derived, not taken from the caller
@@ -192,6 +193,9 @@ struct ResidentScene {
     // replaced, the environment kept, removed or rebuilt from the resident texels (environment_build.h).
     int update_lighting(const HiprLight* new_lights, uint32_t light_count, int environment_action, const HiprEnvironmentBuild* build, float* out_per_pixel_PDF, HiprLightSample* out_samples,
                         LightingScratch& scratch, hipStream_t stream, HiprLightingResult* out);
+    // The device work of hipr_update_scene_texels, which has checked every rectangle against uploaded_textures (hipr_internal_check_texel_update): the rectangles
+    // written into the texel pool and the flags that follow texels decided again (texel_update.h).
+    int update_texels(const HiprTexelEdit* edits, uint32_t edit_count, TexelScratch& scratch, hipStream_t stream, HiprTexelUpdateResult* out);
     double append_ms[3] = {0.0, 0.0, 0.0};      // of the last append_pools: the allocations (host clock), the device-to-device copies of the resident parts, the tails and the mirror segments (events)
     Event append_events[3];             // made by the first append_pools
 
@@ -294,6 +298,13 @@ struct LightingScratch : Scratch<LightingBuffers> {
     Event events[4];                    // around the kernels before and after the integral is read; made by the first build
 };
 
+// The device scratch of hipr_update_scene_texels (texel_update.h): the rectangles' rows packed, a word per instance and the flag pass's few words.
+struct TexelBuffers { DeviceBuffer staging, touched, words; };
+struct TexelScratch : Scratch<TexelBuffers> {
+    double staging_ms = 0.0, write_ms = 0.0, coverage_ms = 0.0, leaf_ms = 0.0;      // of the last texel update
+    Event events[4];                    // around the rectangle writes, the flag pass and the leaf pass; made by the first update
+};
+
 // The context; HiprContext, the C-ABI's opaque type, is this and nothing else.
 struct Context {
     int device = 0;
@@ -386,6 +397,7 @@ struct Context {
     Collapse4Scratch collapse4;         // hipr_build_wide4; likewise
     RebuildScratch rebuild;             // hipr_rebuild_scene_trees, which also runs over the two above
     LightingScratch lighting;           // hipr_update_scene_lighting's environment build
+    TexelScratch texel_update;          // hipr_update_scene_texels
 
     hipEvent_t next_event() {
         if (events_used == event_pool.size()) {

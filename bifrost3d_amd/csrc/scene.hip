@@ -17,6 +17,7 @@
 #include "instance_edit.h"
 #include "pool_growth.h"
 #include "environment_build.h"
+#include "texel_update.h"
 
 #include <hip/hip_runtime.h>
 
@@ -910,6 +911,88 @@ int ResidentScene::update_lighting(const HiprLight* new_lights, uint32_t light_c
     return HIPR_OK;
 }
 
+// The device work of hipr_update_scene_texels (texel_update.h). The scratch is allocated BEFORE the scene is touched: a failed allocation leaves the scene as found.
+// Then, as the other writers: not ready, the copies and the passes on the stream, the host copies -- and the state the call found, ready or awaiting a rebuild: no
+// tree, corner or pool other than the texels has changed. The flag pass is left out when no resident instance wears a material that leaves its triangles' flags to an
+// edited texture (the host copies answer that): a tint texture's edit is the rectangle writes alone.
+int ResidentScene::update_texels(const HiprTexelEdit* edits, uint32_t edit_count, TexelScratch& x, hipStream_t st, HiprTexelUpdateResult* out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<TexelRectangle> rectangles(edit_count);
+    std::vector<bool> edited(uploaded_textures.size(), false);
+    uint64_t staging_bytes = 0;
+    bool environment_stale = false;
+    for (uint32_t k = 0; k < edit_count; ++k) {
+        rectangles[k] = planned_rectangle(edits[k], uploaded_textures[edits[k].texture_index], staging_bytes);
+        edited[edits[k].texture_index] = true;
+        environment_stale = environment_stale || (uploaded_environment && args.env_map_ID == int32_t(edits[k].texture_index));
+    }
+    // `touched`: the instances whose material's deciding coverage texture is an edited one
+    std::vector<uint32_t> touched(std::max<size_t>(uploaded_instances.size(), 1), 0u);
+    bool decides_flags = false;
+    for (size_t i = 0; i < uploaded_instances.size(); ++i)
+        if (const HiprTexture* deciding = deciding_coverage_texture(uploaded_materials[size_t(uploaded_instances[i].material_index)], uploaded_textures.data(), uint32_t(uploaded_textures.size())))
+            if (edited[size_t(deciding - uploaded_textures.data())]) { touched[i] = 1u; decides_flags = true; }
+    decides_flags = decides_flags && args.triangle_count != 0;
+    std::vector<uint8_t> packed(staging_bytes, uint8_t(0));
+    for (uint32_t k = 0; k < edit_count; ++k) pack_rectangle_rows(edits[k], rectangles[k], packed.data());
+    int r = x.staging.resize(staging_bytes);
+    if (decides_flags) {
+        r |= x.touched.resize(touched.size() * sizeof(uint32_t));
+        r |= x.words.resize(TEXEL_SCRATCH_WORDS * sizeof(uint32_t));
+    }
+    if (r) {
+        (void)hipGetLastError();      // the failed allocation's error is answered here: it must not meet the next call's check
+        return HIPR_ERROR_OUT_OF_MEMORY;
+    }
+    for (Event& e : x.events)
+        if (!e) e = make_event(hipEventDefault);
+    const bool timed = x.events[0] && x.events[1] && x.events[2] && x.events[3];
+    const bool was_ready = ready, awaited_rebuild = awaits_rebuild;
+    begin_write();
+    // 1. the rows, then the rectangles in list order
+    HIP_TRY(hipMemcpyAsync(x.staging.ptr, packed.data(), staging_bytes, hipMemcpyHostToDevice, st));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (timed) HIP_TRY(hipEventRecord(x.events[0], st));
+    for (const TexelRectangle& rectangle : rectangles) {
+        const uint64_t chunks = (rectangle.row_bytes + 3u) / 4u;
+        hipLaunchKernelGGL(k_write_texel_rectangle, dim3(uint32_t((chunks + TEXEL_UPDATE_BLOCK - 1) / TEXEL_UPDATE_BLOCK), std::min(rectangle.height, 65535u)), dim3(TEXEL_UPDATE_BLOCK), 0, st, rectangle,
+                           x.staging.as<uint8_t>(), texels.as<uint8_t>());
+    }
+    HIP_TRY(hipGetLastError());
+    if (timed) HIP_TRY(hipEventRecord(x.events[1], st));
+    uint32_t words[3] = {all_triangles_opaque ? 1u : 0u, 0u, 0u};      // what stays when no flag follows the edit
+    if (decides_flags) {
+        // 2. the flags of the touched instances' triangles; 3. the leaf records (queued whatever pass 2 finds: it writes only where a record's bits differ)
+        HIP_TRY(hipMemcpyAsync(x.touched.ptr, touched.data(), touched.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(x.words.ptr, 0, TEXEL_SCRATCH_WORDS * sizeof(uint32_t), st));
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(x.words.ptr), 1, 1, st));
+        const MaterialUpdateArrays a = {triangles.as<HiprTriangle>(), args.triangle_count, instances.as<HiprInstance>(), materials.as<HiprMaterial>(), indices.as<uint32_t>(),
+                                        reinterpret_cast<const float*>(args.texcoords), textures.as<HiprTexture>(), uint32_t(uploaded_textures.size()), texels.as<uint8_t>(),
+                                        x.touched.as<uint32_t>(), trace_triangles.as<uint32_t>(), shade_triangles.as<uint32_t>(), triangle_class.as<uint8_t>()};
+        hipLaunchKernelGGL(k_reflag_touched_triangles, dim3((args.triangle_count + TEXEL_UPDATE_BLOCK - 1) / TEXEL_UPDATE_BLOCK), dim3(TEXEL_UPDATE_BLOCK), 0, st, a, x.words.as<uint32_t>());
+        if (timed) HIP_TRY(hipEventRecord(x.events[2], st));
+        if (wide8.slot_count && refit_leaf_count)
+            hipLaunchKernelGGL(k_update_leaf_flags, dim3((refit_leaf_count + MATERIAL_UPDATE_BLOCK - 1) / MATERIAL_UPDATE_BLOCK), dim3(MATERIAL_UPDATE_BLOCK), 0, st, wide8_slots.as<HiprSlot8>(),
+                               refit_leaf_slots.as<uint32_t>(), refit_leaf_count, triangles.as<HiprTriangle>());
+        HIP_TRY(hipGetLastError());
+        if (timed) HIP_TRY(hipEventRecord(x.events[3], st));
+        HIP_TRY(hipMemcpyAsync(words, x.words.ptr, sizeof(words), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));      // `packed` and `touched` are read by now as well
+    float write_ms = 0.0f, flag_ms = 0.0f, leaf_ms = 0.0f;
+    if (timed) {
+        HIP_TRY(hipEventElapsedTime(&write_ms, x.events[0], x.events[1]));
+        if (decides_flags) { HIP_TRY(hipEventElapsedTime(&flag_ms, x.events[1], x.events[2])); HIP_TRY(hipEventElapsedTime(&leaf_ms, x.events[2], x.events[3])); }
+    }
+    x.staging_ms = ms(t0, t1); x.write_ms = write_ms; x.coverage_ms = flag_ms; x.leaf_ms = leaf_ms;
+    all_triangles_opaque = words[TEXEL_WORD_OPAQUE] != 0;
+    derive_switches_from_pools();
+    *out = {words[TEXEL_WORD_DECIDED], words[TEXEL_WORD_CHANGED], all_triangles_opaque ? 1u : 0u, environment_stale ? 1u : 0u};
+    ready = was_ready;
+    awaits_rebuild = awaited_rebuild;
+    return HIPR_OK;
+}
+
 // The last step of hipr_rebuild_scene_trees, which has refused everything it refuses: the new resident arrays, and what an upload derives from them. The pools, the
 // instances and the lights stay; all_triangles_opaque, any_coated_triangle and the other switches cannot change under a permutation of the triangles and stay. The
 // 4-wide array is not rebuilt: tree_stale stays set until the next upload or geometry update, as after the refit.
@@ -1759,6 +1842,52 @@ int hipr_debug_lighting_times(HiprContext* c, double* out4_ms) {
     if (!c || !out4_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_lighting_times: null argument");
     const LightingScratch& x = c->lighting;
     out4_ms[0] = x.upload_ms; out4_ms[1] = x.kernel_ms; out4_ms[2] = x.finish_ms; out4_ms[3] = x.readback_ms;
+    return HIPR_OK;
+}
+
+// Not part of the public header: every refusal of hipr_update_scene_texels that is not a failed allocation, and nothing else -- no HIP call, the device and the
+// books stay as they are. The group asks every member before any member writes.
+int hipr_internal_check_texel_update(HiprContext* c, const HiprTexelEdit* edits, uint32_t edit_count, const HiprTexelUpdateResult* out) {
+    const char* who = "hipr_update_scene_texels";
+    if (int st = check_context(c)) return st;
+    const ResidentScene& r = c->scene;
+    if (!r.ready && !r.awaits_rebuild) return fail(HIPR_ERROR_NOT_READY, "%s: no scene uploaded, or one a failed call left behind", who);
+    if (!out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null result", who);
+    if (edit_count && !edits) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null array with a non-zero count", who);
+    for (uint32_t k = 0; k < edit_count; ++k) {
+        const HiprTexelEdit& e = edits[k];
+        if (!e.texels) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: edit %u has no texels", who, k);
+        if (e.texture_index == 0 || e.texture_index >= r.uploaded_textures.size())
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: edit %u names texture %u of %zu resident textures (hipr_append_scene_pools brings a new one)", who, k, e.texture_index, r.uploaded_textures.size());
+        const HiprTexture& t = r.uploaded_textures[e.texture_index];
+        if (e.width == 0 || e.height == 0 || e.x >= t.width || e.y >= t.height || e.width > t.width - e.x || e.height > t.height - e.y)
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: edit %u is %u x %u texels at (%u, %u) of a texture of %u x %u", who, k, e.width, e.height, e.x, e.y, t.width, t.height);
+        if (e.row_pitch_bytes < uint64_t(e.width) * hipr::texel_bytes_of(t.format))
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: edit %u has a pitch of %llu bytes, a row takes %llu", who, k, (unsigned long long)e.row_pitch_bytes, (unsigned long long)(uint64_t(e.width) * hipr::texel_bytes_of(t.format)));
+    }
+    // The exhaustive search's items pair triangles of equal flags (build_trace_items): there a flag that follows a texel changes a topology, which only the host builds.
+    if (r.args.trace_item_count != 0)
+        for (uint32_t k = 0; k < edit_count; ++k)
+            for (const HiprMaterial& m : r.uploaded_materials)
+                if (m.coverage_texture_ID > 0 && uint32_t(m.coverage_texture_ID) == edits[k].texture_index)
+                    return fail(HIPR_ERROR_UNSUPPORTED, "%s: the uploaded scene carries the exhaustive search's items, which pair triangles by their flags, and texture %u is a material's coverage texture; upload the scene instead", who, edits[k].texture_index);
+    return HIPR_OK;
+}
+
+// Pixel edits of resident images (texel_update.h): the rectangles checked on the host, then ResidentScene::update_texels.
+int hipr_update_scene_texels(HiprContext* c, const HiprTexelEdit* edits, uint32_t edit_count, HiprTexelUpdateResult* out) {
+    if (int st = hipr_internal_check_texel_update(c, edits, edit_count, out)) return st;
+    if (!edit_count) { *out = {0u, 0u, c->scene.all_triangles_opaque ? 1u : 0u, 0u}; return HIPR_OK; }
+    if (int finish_status = finish_all(c)) return finish_status;      // no pending pass may go on over texels and flags that are about to change
+    c->break_chain(c->stream);
+    ScratchGuard<TexelScratch> guard(c->texel_update);
+    return c->scene.update_texels(edits, edit_count, c->texel_update, c->stream, out);
+}
+
+int hipr_debug_texel_update_times(HiprContext* c, double* out4_ms) {
+    if (!c || !out4_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_texel_update_times: null argument");
+    const TexelScratch& x = c->texel_update;
+    out4_ms[0] = x.staging_ms; out4_ms[1] = x.write_ms; out4_ms[2] = x.coverage_ms; out4_ms[3] = x.leaf_ms;
     return HIPR_OK;
 }
 

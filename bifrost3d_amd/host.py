@@ -29,6 +29,7 @@ def load_host_library() -> C.CDLL:
     lib.hiprh_scene_move_model.argtypes = [vp, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_double]
     lib.hiprh_scene_model_pose.argtypes = [vp, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_uint), C.POINTER(C.c_float), C.c_uint]
     lib.hiprh_scene_update_materials.argtypes = [vp, C.POINTER(capi.HiprMaterialUpdate), C.c_uint, C.POINTER(capi.HiprInstanceMaterial), C.c_uint]
+    lib.hiprh_scene_update_texels.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, C.c_ulonglong, C.POINTER(C.c_int)]
     lib.hiprh_scene_rebuild.argtypes = [vp]
     lib.hiprh_scene_stage_model.argtypes = [vp, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float]
     lib.hiprh_scene_adopt_trees.argtypes = [vp, vp, C.c_uint, vp, C.c_uint, vp, C.POINTER(capi.HiprWide8BuildResult)]
@@ -241,6 +242,22 @@ class Scene:
         if status < 0:
             raise capi.HiprError("hiprh_scene_update_materials failed")
         return status == 1
+
+    def update_texels(self, edits) -> bool:
+        """Pixel edits WITHOUT a rebuild (SceneBuilder::update_texels), in order: `edits` as capi.texel_edits takes them -- what Context.update_scene_texels takes. False as
+        soon as one is refused (where the device call would refuse); the ones before it stay applied. `environment_stale` says afterwards whether the environment's
+        PDF image and samples lag behind an edit of its map."""
+        array, keep = capi.texel_edits(edits)
+        stale = C.c_int(0)
+        for k in range(len(keep)):
+            e = array[k]
+            status = self.lib.hiprh_scene_update_texels(self.handle, e.texture_index, e.x, e.y, e.width, e.height, e.texels, e.row_pitch_bytes, C.byref(stale))
+            if status < 0:
+                raise capi.HiprError("hiprh_scene_update_texels failed")
+            self.environment_stale = bool(stale.value)
+            if status != 1:
+                return False
+        return True
 
     def rebuild(self):
         """A fresh build (triangle flags, BVH2, 4-wide and 8-wide trees) over the instances and materials as they stand."""

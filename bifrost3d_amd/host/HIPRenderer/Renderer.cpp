@@ -222,7 +222,7 @@ struct Renderer::Implementation {
     HiprSceneState scene_state = {{0, 0, 0}, 3};                     // next_event_sample_count = 3, OR/Renderer.cpp:479
     std::unique_ptr<SceneBuilder> scene;
     std::map<unsigned int, uint32_t> scene_mesh_index;      // Bifrost mesh ID -> the scene builder's mesh
-    Renderer::SceneUpdateCounts scene_updates = {0, 0, 0, 0, 0, 0, 0};
+    Renderer::SceneUpdateCounts scene_updates = {0, 0, 0, 0, 0, 0, 0, 0};
     Renderer::SceneBuildCounts retired_builds = {0, 0};      // of the scene builders that are gone
     Renderer::SceneCollapseCounts retired_collapses = {0, 0};
     Renderer::SceneRebuildCounts scene_rebuilds = {0, 0};
@@ -571,6 +571,52 @@ struct Renderer::Implementation {
         return true;
     }
 
+    // The pixel-edit tick on the device (HIPR_DEVICE_TEXEL_UPDATE=1, opt-in: the calls are measured, profiles/texel_update_device_vs_host.txt, the tick through this class is not; hipr_update_scene_texels; the reference asserts
+    // "Pixel update not implemented yet", OR/Renderer.cpp:697-698): images whose pixels were rewritten in place (Images::get_mutable_pixels) and that textures inside
+    // the uploaded pool show. Every such texture takes ONE rectangle, the whole image, converted as a flatten converts it (convert_image: RGB24 expanded); the scene
+    // builder follows without a rebuild (SceneBuilder::update_texels) and every camera with an uploaded scene has the rectangles written into its resident texel pool
+    // and the flags that follow texels decided again by kernels. When an edited image is the scene's environment map, the environment is rebuilt on the device in the
+    // same tick (update_lighting_on_the_device) -- with HIPR_DEVICE_LIGHTING=1 only; without it the tick takes the full path, so the sky's radiance and its sampling
+    // PDF never disagree. false: the caller takes the full path -- a new scene -- which is also what any refusal or error ends in.
+    static bool device_texel_update_wanted() {
+        const char* wanted = std::getenv("HIPR_DEVICE_TEXEL_UPDATE");
+        return wanted && std::atoi(wanted) != 0;
+    }
+    bool update_texels_on_the_device() {
+        if (!scene || scene->has_staged_transforms() || scene->has_staged_edits()) return false;
+        for (const CameraState& c : per_camera_state)
+            if (c.context && c.scene_uploaded && c.geometry_update_pending) return false;
+        TextureID environment_map = TextureID::invalid_UID(), edited_environment_map = TextureID::invalid_UID();
+        for (SceneRootID scene_ID : SceneRoots::get_iterable())
+            if (SceneRoots::get_environment_map(scene_ID) != TextureID::invalid_UID()) { environment_map = SceneRoots::get_environment_map(scene_ID); break; }      // one scene root is rendered
+        struct Whole { uint32_t texture; ImageData image; };
+        std::vector<Whole> images;
+        for (ImageID image_ID : Images::get_changed_images())
+            for (unsigned int t = 1; t < Textures::capacity(); ++t) {
+                if (Textures::get_image_ID(TextureID(t)) != image_ID) continue;
+                if (t >= scene->texture_count()) return false;
+                images.push_back({t, convert_image(image_ID)});
+                const HiprTexture& pooled = scene->textures()[t];
+                if (pooled.width != images.back().image.width || pooled.height != images.back().image.height || pooled.format != images.back().image.format) return false;
+                if (TextureID(t) == environment_map) edited_environment_map = environment_map;
+            }
+        if (edited_environment_map != TextureID::invalid_UID() && !device_lighting_wanted()) return false;
+        std::vector<HiprTexelEdit> edits;
+        for (const Whole& w : images) {
+            const uint64_t pitch = w.image.pixels.size() / w.image.height;
+            if (!scene->update_texels(w.texture, 0, 0, w.image.width, w.image.height, w.image.pixels.data(), pitch)) return false;
+            edits.push_back({w.texture, 0u, 0u, w.image.width, w.image.height, w.image.pixels.data(), pitch});
+        }
+        for (CameraState& c : per_camera_state) {
+            c.drop_batch();
+            if (!c.context || !c.scene_uploaded || edits.empty()) continue;
+            HiprTexelUpdateResult result = {};
+            if (hipr_group_update_scene_texels(c.context, edits.data(), uint32_t(edits.size()), &result) != HIPR_OK) return false;
+            ++scene_updates.texel_updates;
+        }
+        return edited_environment_map == TextureID::invalid_UID() || update_lighting_on_the_device(edited_environment_map);
+    }
+
     // ---- handle_updates -----------------------------------------------------------------------------------------------
     void handle_updates() {
         bool should_reset_accumulations = false, scene_dirty = false, models_edited = false;
@@ -607,7 +653,11 @@ struct Renderer::Implementation {
                 (pools_may_grow ? pools_grow : scene_dirty) = true;      // a destroyed mesh's data stays pooled ...
                 scene_mesh_index.erase(mesh_ID.get_index());      // ... but its ID is recycled after the tick: whatever mesh carries it from here on is not the one the builder holds
             }
-        if (!Images::get_changed_images().is_empty() || !Textures::get_changed_textures().is_empty()) {
+        // HIPR_DEVICE_TEXEL_UPDATE=1: images whose pixels were rewritten, and nothing else of images and textures, are dirt the resident scene can take
+        // (update_texels_on_the_device), where they are the tick's only dirt; unset, they make a new scene as they always did.
+        bool texels_edited = scene && device_texel_update_wanted() && !Images::get_changed_images().is_empty() && Textures::get_changed_textures().is_empty();
+        for (ImageID image_ID : Images::get_changed_images()) texels_edited = texels_edited && Images::get_changes(image_ID) == Images::Change::PixelsUpdated;
+        if (!texels_edited && (!Images::get_changed_images().is_empty() || !Textures::get_changed_textures().is_empty())) {
             bool created_past_the_pool = pools_may_grow;
             for (ImageID image_ID : Images::get_changed_images()) created_past_the_pool = created_past_the_pool && Images::get_changes(image_ID) == Images::Change::Created;
             for (TextureID texture_ID : Textures::get_changed_textures())
@@ -689,6 +739,13 @@ struct Renderer::Implementation {
         // Material edits are applied to the resident scene when they are the tick's only dirt; with anything else in the tick, or when the device path declines,
         // they make a new scene as they always did.
         if (materials_dirty) scene_dirty = true;
+        // Pixel edits likewise: with any other dirt in the tick, or when the device path declines, they make a new scene.
+        if (texels_edited) {
+            const bool only_dirt = !scene_dirty && !models_edited && !pools_grow && moved_models.empty() && changed_materials.empty() && material_assignments.empty() && !lights_recounted &&
+                                   !lights_moved && environment_map_set == TextureID::invalid_UID();
+            if (only_dirt && update_texels_on_the_device()) should_reset_accumulations = true;
+            else scene_dirty = true;
+        }
         // Lighting edits likewise: with any other dirt in the tick -- a moved model, a material, a model, a pool that grows (the map's own texture included) -- or when
         // the device path declines, they make a new scene.
         if (lights_recounted || environment_map_set != TextureID::invalid_UID()) {

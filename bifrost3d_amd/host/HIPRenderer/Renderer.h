@@ -100,8 +100,9 @@ public:
     // the resident scene (hipr_update_scene_materials), and ticks whose created and destroyed models were applied to the resident scenes and adopted by the scene
     // builder (HIPR_DEVICE_INSTANCE_EDIT=1, hipr_edit_scene_instances), and such ticks that also brought new meshes, materials or textures, appended to the resident
     // pools first (HIPR_DEVICE_POOL_GROWTH=1, hipr_append_scene_pools), and ticks whose light sources created or destroyed and whose environment map set were
-    // applied to the resident scenes and adopted by the scene builder (HIPR_DEVICE_LIGHTING=1, hipr_update_scene_lighting).
-    struct SceneUpdateCounts { unsigned int uploads, geometry_updates, device_refits, material_updates, instance_edits, pool_growths, lighting_updates; };
+    // applied to the resident scenes and adopted by the scene builder (HIPR_DEVICE_LIGHTING=1, hipr_update_scene_lighting), and pixel edits of pooled images
+    // applied to the resident scenes (HIPR_DEVICE_TEXEL_UPDATE=1, hipr_update_scene_texels; counted per camera, as the material edits).
+    struct SceneUpdateCounts { unsigned int uploads, geometry_updates, device_refits, material_updates, instance_edits, pool_growths, lighting_updates, texel_updates; };
     SceneUpdateCounts scene_update_counts() const;
     // Scene builds whose BVH2 the device made (HIPR_DEVICE_BUILD=1, hipr_build_bvh2), and builds where it was asked and declined, so that the host built the tree.
     struct SceneBuildCounts { unsigned int device_builds, declined_builds; };

@@ -217,6 +217,7 @@ void SceneBuilder::set_environment(uint32_t texture_index, uint32_t pdf_width, u
     m_environment = {int32_t(texture_index), pdf_width, pdf_height, nullptr, nullptr, uint32_t(m_environment_samples.size())};
     m_has_environment = true;
     m_environment_set_since = m_built;
+    m_environment_texels_edited = false;
     if (m_environment_samples.size() > 1) {   // next_event_estimation_possible (PresampledEnvironmentMap.h:64)
         HiprLight light = {};
         light.flags = HIPR_LIGHT_PRESAMPLED_ENVIRONMENT;
@@ -620,7 +621,12 @@ bool SceneBuilder::update_materials(const std::vector<HiprMaterialUpdate>& chang
         flags_changed = flags_changed || t.flags != before;
     }
     if (!flags_changed) return true;
-    // the leaf records of the 8-wide tree repeat the flags of their triangles; the tree is walked from the root, children in consecutive slots
+    refresh_leaf_material_bits();
+    return true;
+}
+
+// The leaf records of the 8-wide tree repeat the flags of their triangles; the tree is walked from the root, children in consecutive slots.
+void SceneBuilder::refresh_leaf_material_bits() {
     std::vector<HiprSlot8>& slots = m_bvh.wide8.slots;
     std::vector<uint32_t> nodes;
     if (!slots.empty()) nodes.push_back(0u);
@@ -635,6 +641,35 @@ bool SceneBuilder::update_materials(const std::vector<HiprMaterialUpdate>& chang
             else slots[child].leaf.flags = (slots[child].leaf.flags & ~15u) | hipr::leaf_material_bits(m_triangles.data(), slots[child].leaf);
         }
     }
+}
+
+bool SceneBuilder::update_texels(uint32_t texture_index, uint32_t x, uint32_t y, uint32_t width, uint32_t height, const void* pixels, uint64_t row_pitch_bytes) {
+    if (!m_built || !pixels || texture_index == 0 || texture_index >= m_textures.size() || texture_index >= m_built_pools.textures) return false;
+    const HiprTexture& t = m_textures[texture_index];
+    const uint64_t size = t.format == HIPR_TEXEL_R8 ? 1u : (t.format == HIPR_TEXEL_RGBA8 || t.format == HIPR_TEXEL_R32F ? 4u : 16u), row_bytes = uint64_t(width) * size;
+    if (width == 0 || height == 0 || x >= t.width || y >= t.height || width > t.width - x || height > t.height - y || row_pitch_bytes < row_bytes) return false;
+    // `affected`: the materials that leave their triangles' HIPR_TRIANGLE_OPAQUE to this texture (csrc/material_rules.h)
+    std::vector<bool> affected(m_materials.size(), false);
+    bool any_affected = false, names_coverage = false;
+    for (size_t k = 0; k < m_materials.size(); ++k) {
+        affected[k] = hipr::deciding_coverage_texture(m_materials[k], m_textures.data(), uint32_t(m_textures.size())) == &t;
+        any_affected = any_affected || affected[k];
+        names_coverage = names_coverage || (m_materials[k].coverage_texture_ID > 0 && uint32_t(m_materials[k].coverage_texture_ID) == texture_index);
+    }
+    if (names_coverage && m_triangles.size() <= 64) return false;      // the exhaustive search's items pair triangles by their flags: the device refuses, as for a material edit
+    for (uint32_t row = 0; row < height; ++row)
+        std::memcpy(m_texels.data() + t.texel_offset + (uint64_t(y + row) * t.width + x) * size, static_cast<const uint8_t*>(pixels) + row * row_pitch_bytes, size_t(row_bytes));
+    if (m_has_environment && m_environment.environment_map_ID == int32_t(texture_index)) m_environment_texels_edited = true;
+    if (!any_affected) return true;
+    bool flags_changed = false;
+    for (HiprTriangle& triangle : m_triangles) {
+        const HiprInstance& inst = m_instances[triangle.instance_index];
+        if (!affected[size_t(inst.material_index)]) continue;
+        const uint32_t before = triangle.flags;
+        triangle.flags = hipr::triangle_flags(m_materials[size_t(inst.material_index)], inst, triangle.primitive_index, m_indices.data(), m_texcoords.data(), m_textures.data(), uint32_t(m_textures.size()), m_texels.data());
+        flags_changed = flags_changed || triangle.flags != before;
+    }
+    if (flags_changed) refresh_leaf_material_bits();
     return true;
 }
 
@@ -720,6 +755,7 @@ bool SceneBuilder::adopt_lighting(const std::vector<HiprLight>& lights, int envi
         m_has_environment = false;
     } else if (environment_action != HIPR_ENVIRONMENT_KEEP) return false;
     m_environment_set_since = false;
+    if (environment_action != HIPR_ENVIRONMENT_KEEP) m_environment_texels_edited = false;
     m_desc.environment = m_has_environment ? &m_environment : nullptr;
     return set_lights(lights);
 }

@@ -153,8 +153,20 @@ public:
     // would make: the flags of the touched instances' triangles are recomputed (csrc/material_rules.h) and the leaf records of the 8-wide tree follow them. What
     // hipr_update_scene_materials does to the resident scene. Returns false, with nothing done, for an index out of range.
     bool update_materials(const std::vector<HiprMaterialUpdate>& changed, const std::vector<HiprInstanceMaterial>& assignments);
+    // Pixel edit of a texture of a BUILT scene without a rebuild (what hipr_update_scene_texels does to the resident scene): the rectangle (x, y, width, height) of
+    // texture `texture_index` takes `pixels` -- rows `row_pitch_bytes` apart, in the texture's pooled format (RGB24 already expanded, as add_texture leaves it). No
+    // corner moves and the tree builders read no flag, so the trees stay; the flags of the triangles of the materials whose deciding coverage texture this is are
+    // recomputed (csrc/material_rules.h) and the leaf records of the 8-wide tree follow them: desc() is then, in every array and scalar but the environment's, what
+    // a rebuild() makes of the edited image. Returns false, with nothing touched, where the device call would refuse: before the scene is built, a texture the
+    // device does not hold (0, outside the pool, added since the last build), a rectangle with an extent of 0 or reaching outside the texture, a pitch below a
+    // row's bytes, a coverage texture of a scene of at most 64 triangles. When the texture is the environment's map, the environment's PDF image and samples are
+    // left behind: environment_texels_edited() holds until set_environment or an adopt_lighting that builds or removes it (staged_environment_build makes what
+    // hipr_update_scene_lighting takes for that).
+    bool update_texels(uint32_t texture_index, uint32_t x, uint32_t y, uint32_t width, uint32_t height, const void* pixels, uint64_t row_pitch_bytes);
+    bool environment_texels_edited() const { return m_environment_texels_edited; }
     const std::vector<HiprMaterial>& materials() const { return m_materials; }
     const std::vector<HiprLight>& lights() const { return m_lights; }
+    const std::vector<HiprTexture>& textures() const { return m_textures; }      // slot 0, "no texture", included
     const std::vector<HiprInstance>& instances() const { return m_instances; }
     // The lights of a finalized scene replaced one for one (moved or re-coloured lights; the count must match).
     bool replace_lights(const std::vector<HiprLight>& lights);
@@ -201,6 +213,7 @@ private:
     void flatten_instance(uint32_t instance, std::vector<HiprTriangle>& world);
     bool trees_fit(uint32_t triangle_count, const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, const HiprSlot8* slots, const HiprWide8BuildResult& wide8) const;
     void note_instance_edit();
+    void refresh_leaf_material_bits();      // bits 0..3 of every leaf record of the 8-wide tree from m_triangles' flags
     bool list_instance_edits(std::vector<HiprInstanceEdit>& edits) const;      // staged_instance_edits without its question about the pools
     // The pool sizes at the last build or adoption (build_trees_over): what the device holds when it follows the builder, and where the tails begin.
     struct PoolSizes { size_t index_words = 0, vertices = 0, materials = 0, textures = 0, texel_bytes = 0, lights = 0; bool texcoords = false, tints = false, emission = false; };
@@ -209,6 +222,7 @@ private:
     // `mirrored_from` on. Cleared with every build.
     std::vector<HiprIndexSegment> m_index_log;
     bool m_environment_set_since = false;      // set_environment after the last build: the environment's data is an upload's business
+    bool m_environment_texels_edited = false;  // update_texels wrote into the environment's map: its PDF image and samples describe the image before
     static constexpr uint32_t NOT_BUILT = 0xFFFFFFFFu;
     std::vector<uint32_t> m_built_index;      // per instance: its index in the list the triangles and the trees were built over, NOT_BUILT for one created since
     uint32_t m_built_instance_count = 0;      // the length of that list

@@ -348,6 +348,20 @@ int hiprh_scene_update_materials(void* scene, const HiprMaterialUpdate* material
     } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_update_materials: %s\n", e.what()); return -1; }
 }
 
+// Pixel edit of a texture of a built scene (SceneBuilder::update_texels): the rectangle takes `pixels`, rows `row_pitch_bytes` apart, in the texture's pooled format; the
+// builder's description follows without a rebuild. Returns 1 when done, 0 where the device call would refuse (nothing done), -1 on error. out_environment_stale (may be
+// null): whether the environment's PDF image and samples lag behind an edit of its map.
+int hiprh_scene_update_texels(void* scene, unsigned texture_index, unsigned x, unsigned y, unsigned width, unsigned height, const void* pixels, unsigned long long row_pitch_bytes,
+                              int* out_environment_stale) {
+    if (!scene) return -1;
+    try {
+        SceneBuilder* builder = static_cast<SceneBuilder*>(scene);
+        const bool done = builder->update_texels(texture_index, x, y, width, height, pixels, row_pitch_bytes);
+        if (out_environment_stale) *out_environment_stale = builder->environment_texels_edited() ? 1 : 0;
+        return done ? 1 : 0;
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_update_texels: %s\n", e.what()); return -1; }
+}
+
 // SceneBuilder::rebuild: a fresh tree over the instances and materials as they stand. Returns 0, -1 on error.
 int hiprh_scene_rebuild(void* scene) {
     if (!scene) return -1;

@@ -269,6 +269,26 @@ class Context:
             out["samples"] = np.ascontiguousarray(samples[:result.sample_count])
         return out
 
+    def update_scene_texels(self, edits, group=None) -> dict:
+        """hipr_update_scene_texels: rectangles of new texels of textures the device holds, applied to the resident scene by kernels, no upload. `edits` as
+        capi.texel_edits takes them. Returns a dict of status and, when it is HIPR_OK, candidate_triangles, changed_triangles, all_triangles_opaque and
+        environment_stale: a refusal leaves the scene as found and is the caller's to answer with the full path. `group`: a HiprGroup handle, for
+        hipr_group_update_scene_texels."""
+        array, keep = capi.texel_edits(edits)
+        result = capi.HiprTexelUpdateResult()
+        call, handle = (self.lib.hipr_group_update_scene_texels, group) if group is not None else (self.lib.hipr_update_scene_texels, self.handle)
+        status = call(handle, array, len(keep), C.byref(result))
+        if status != capi.HIPR_OK:
+            return dict(status=status)
+        return dict(status=status, candidate_triangles=result.candidate_triangles, changed_triangles=result.changed_triangles, all_triangles_opaque=bool(result.all_triangles_opaque),
+                    environment_stale=bool(result.environment_stale))
+
+    def texel_update_times(self) -> dict:
+        """Milliseconds of the last update_scene_texels: the rows packed and their staging copy, the rectangle writes, the coverage passes, the leaf pass."""
+        out = (C.c_double * 4)()
+        self._check(self.lib.hipr_debug_texel_update_times(self.handle, out), "hipr_debug_texel_update_times")
+        return dict(staging=out[0], writes=out[1], coverage=out[2], leaves=out[3])
+
     def lighting_times(self) -> dict:
         """Milliseconds of the last update_scene_lighting: allocations + uploads, kernels, the host's finish of the samples, read-back."""
         out = (C.c_double * 4)()

@@ -595,6 +595,41 @@ int hipr_update_scene_lighting(HiprContext* context, const HiprLight* lights, ui
                                float* out_per_pixel_PDF /* may be NULL */, uint64_t pdf_capacity,
                                HiprLightSample* out_samples /* may be NULL */, uint32_t sample_capacity,
                                HiprLightingResult* out);
+/* Pixel edits of images the device already holds, applied to the RESIDENT scene on the device (csrc/texel_update.h; the reference asserts "Pixel update not
+ * implemented yet", OR/Renderer.cpp:697-698): a painted mask, a video frame on a screen, another lace pattern on a banner move no triangle and no tree, so no
+ * flatten on the host, no tree build and no upload of any pool is needed. Each edit is a rectangle of new texels of a texture of the RESIDENT pool, in the texture's
+ * resident format (all four HIPR_TEXEL_* are served; RGB24 already expanded, as SceneBuilder::add_texture leaves it); the rectangles are applied in list order, so
+ * where two overlap the later one wins. One thing an upload derives depends on texels and follows: HIPR_TRIANGLE_OPAQUE of the triangles whose material leaves the
+ * decision to its coverage texture (csrc/material_rules.h covered_everywhere) is decided again for every triangle of the materials whose deciding coverage texture is
+ * an edited one, with its copy in the trace records, bits 0..3 of the leaf records and the search instantiation that follows "all triangles opaque". Afterwards the texel pool, the
+ * triangles, the trace records, the leaf records and the kernel instantiations the context picks are, byte for byte, what SceneBuilder::update_texels and
+ * hipr_upload_scene on a fresh context leave. An empty list is HIPR_OK and changes nothing.
+ * The environment is NOT rebuilt: when an edited texture is the resident environment's map, `environment_stale` is 1 and, until a
+ * hipr_update_scene_lighting(..., HIPR_ENVIRONMENT_BUILD, ...) of that texture follows, the sky's radiance and the PDF image and samples it is importance sampled
+ * with disagree -- images stay unbiased only where the old PDF is non-zero wherever the new sky is, and are noisier at best. HIPRenderer::Renderer never leaves that gap.
+ * The call accepts the states hipr_append_scene_pools accepts (ready, or awaiting a rebuild after a refit) and leaves the state it found. Checked on the host before
+ * the device is touched, each leaving the scene as found:
+ *   HIPR_ERROR_NOT_READY          no scene, or a scene a failed call left behind;
+ *   HIPR_ERROR_INVALID_ARGUMENT   a null `out`; null `edits` with a non-zero count; a null `texels`; a texture index of 0 or outside the resident pool; a rectangle
+ *                                 with an extent of 0 or one that reaches outside the texture; a `row_pitch_bytes` below the bytes of a row of the rectangle;
+ *   HIPR_ERROR_UNSUPPORTED        the scene carries the exhaustive search's items (at most 64 triangles), which pair triangles of equal flags, AND an edited texture
+ *                                 is the coverage texture of a resident material: there a flag changes a topology, which only the host builds (as
+ *                                 hipr_update_scene_materials). Edits of the other textures of such a scene are served.
+ * Scratch (the packed rows, a word per instance) is allocated before anything resident is written: a failed allocation is HIPR_ERROR_OUT_OF_MEMORY and leaves the
+ * scene as found. A HIP failure after that leaves no scene, as with the other writers. */
+typedef struct HiprTexelEdit {
+    uint32_t texture_index;          /* a texture of the RESIDENT pool, > 0 */
+    uint32_t x, y, width, height;    /* the rectangle, inside the texture, no extent 0 */
+    const void* texels;              /* host, in the texture's RESIDENT format */
+    uint64_t row_pitch_bytes;        /* >= width * bytes per texel */
+} HiprTexelEdit;
+typedef struct HiprTexelUpdateResult {
+    uint32_t candidate_triangles;    /* triangles whose coverage was decided again */
+    uint32_t changed_triangles;      /* of those, how many changed HIPR_TRIANGLE_OPAQUE */
+    uint32_t all_triangles_opaque;   /* as resident afterwards */
+    uint32_t environment_stale;      /* 1: an edited texture is the resident environment's map; see above */
+} HiprTexelUpdateResult;
+int hipr_update_scene_texels(HiprContext* context, const HiprTexelEdit* edits, uint32_t edit_count, HiprTexelUpdateResult* out);
 int hipr_set_scene_state(HiprContext* context, const HiprSceneState* state);
 
 /* Entry points, numbered like OR/Types.h:33-44. set_backend() of the host renderer maps Backend values onto them
@@ -691,6 +726,7 @@ int hipr_group_append_scene_pools(HiprGroup* group, const HiprPoolGrowth* growth
 int hipr_group_update_scene_lighting(HiprGroup* group, const HiprLight* lights, uint32_t light_count, int environment_action, const HiprEnvironmentBuild* build,
                                      float* out_per_pixel_PDF, uint64_t pdf_capacity, HiprLightSample* out_samples, uint32_t sample_capacity,
                                      HiprLightingResult* out);   /* every member checks before any member writes; member 0's arrays are handed out; their results must agree */
+int hipr_group_update_scene_texels(HiprGroup* group, const HiprTexelEdit* edits, uint32_t edit_count, HiprTexelUpdateResult* out);   /* every member checks before any member writes */
 int hipr_group_update_scene_materials(HiprGroup* group, const HiprMaterialUpdate* materials, uint32_t material_count,
                                       const HiprInstanceMaterial* assignments, uint32_t assignment_count);   /* every member checks before any member writes */
 int hipr_group_set_scene_state(HiprGroup* group, const HiprSceneState* state);
@@ -869,6 +905,10 @@ int hipr_debug_rebuild_times(HiprContext* context, double* out5_ms);
 /* ... and for the context's last successful hipr_update_scene_lighting: the allocations with the uploads of the tables and the lights queued (the host's clock), the
  * kernels (between events on the stream: no synchronise is added for them), the host's finish of the samples, the read-back with the samples' upload. */
 int hipr_debug_lighting_times(HiprContext* context, double* out4_ms);
+/* ... and for the context's last successful hipr_update_scene_texels that did any work: the rows packed and their staging copy queued (the host's clock), the
+ * rectangle writes, the coverage pass (the flags of the affected materials' triangles decided again) and the leaf pass (each between events on the stream: the call
+ * does not synchronise for them) (tools/texel_update_probe.py). */
+int hipr_debug_texel_update_times(HiprContext* context, double* out4_ms);
 
 #ifdef __cplusplus
 }
