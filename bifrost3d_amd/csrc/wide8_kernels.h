@@ -79,6 +79,28 @@ HD bool is_analytic_light(uint32_t flags, float radius) {
 HD float analytic_light_distance(const HiprLight& l, f3 o, f3 d) {
     return (l.flags & HIPR_LIGHT_TYPE_MASK) == HIPR_LIGHT_SPHERE ? ray_sphere(o, d, L3(l, 3), l.data[6]) : ray_disk(o, d, L3(l, 3), L3(l, 7), l.data[6]);
 }
+// The same test in two steps, for a retiring wave: far fewer than one ray in a hundred meets a light, and the wave should not pay the correctly rounded square root
+// of the sphere for the others. analytic_light_reachable is ray_sphere / ray_disk up to the decision that the ray meets the light's surface at all, statement for
+// statement (`along`: -b of the sphere, the plane distance of the disk; `disc`: the sphere's discriminant); analytic_light_distance_of finishes it for the lanes
+// that passed -- the value analytic_light_distance returns for them. A lane that did not pass has NaN there, which no bound admits.
+HD bool analytic_light_reachable(const HiprLight& l, f3 o, f3 d, float& along, float& disc) {
+    if ((l.flags & HIPR_LIGHT_TYPE_MASK) == HIPR_LIGHT_SPHERE) {
+        const f3 to = o - L3(l, 3);
+        const float b = dot(to, d);
+        const f3 fbd = to - b * d;
+        along = -b;
+        disc = l.data[6] * l.data[6] - dot(fbd, fbd);
+        return disc > 0.0f;
+    }
+    const float t = ray_plane(o, d, L3(l, 3), L3(l, 7));
+    const f3 v = (o + d * t) - L3(l, 3);
+    along = t;
+    disc = 0.0f;
+    return dot(v, v) <= l.data[6] * l.data[6] && t >= 0.0f;
+}
+HD float analytic_light_distance_of(const HiprLight& l, float along, float disc) {
+    return (l.flags & HIPR_LIGHT_TYPE_MASK) == HIPR_LIGHT_SPHERE ? along - sqrtf(disc) : along;
+}
 
 // What a lane is doing, in the one word `item`: the slot (24 bits) of the node it visits next, the same with the top bit set for a leaf record, or one of two values
 // for a lane without work -- its ray traversed and waiting to be retired, or no ray at all. The wave's votes are then single compares of a register with a small
@@ -182,6 +204,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
         // stores its slot -- 32 scattered bytes that changed nothing. In the instantiations without the coverage code and without instrumentation only: the others pay for
         // the compare with 4 to 8 B more scratch (profiles/ab_shade_ray_kinds.txt, resource lines) and keep the unconditional sum.
         constexpr bool SKIP_ZERO_SUMS = !COVERAGE && !INSTRUMENT;
+        // ... and the two-step light test of the retire below: in the uninstrumented instantiations whose shadow rays, if any, run without the coverage code.
+        constexpr bool LEAN_RETIRE = !INSTRUMENT && (!COVERAGE || MODE == TRACE_CLOSEST);
         bool adds_nothing = false;
         if constexpr (SKIP_ZERO_SUMS) adds_nothing = pay_x == 0.0f && pay_y == 0.0f && pay_z == 0.0f;
         if constexpr (MODE != TRACE_CLOSEST) if (finished && is_shadow && !adds_nothing) acc = radiance[pay_k];
@@ -213,7 +237,31 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
                     if (!adds_nothing) radiance[pay_k] = acc;
                 }
             } else if constexpr (MODE != TRACE_SHADOW) {    // analytic area lights, LightSources.cu:31-70, in the order of the scene's list
-                if (analytic_lights == 1) {
+                if constexpr (LEAN_RETIRE) {
+                    // The light test in two steps (analytic_light_reachable): every retiring lane takes the cheap decision, and the wave runs the square root and the
+                    // compare with the ray's bounds only where one of its lanes can still hit -- for nearly all rounds that is a branch over them. A lane that
+                    // passes evaluates analytic_light_distance's own expression, and one that does not has NaN there in the whole test, which the compare refuses.
+                    if (analytic_lights == 1) {
+                        float along, disc;
+                        const bool reachable = analytic_light_reachable(held_light, o, d, along, disc);
+                        if (wave_any(reachable)) {
+                            asm volatile("" : "+v"(disc));      // opaque here: the compiler otherwise takes the square root above the vote, for every round
+                            const float t = analytic_light_distance_of(held_light, along, disc);
+                            if (reachable && t > tmin && t < tmax) { tmax = t; pay_x = 0; pay_y = 0; pay_z = __uint_as_float(HIPR_HIT_LIGHT | held_light_index); }
+                        }
+                    } else if (analytic_lights > 1) {
+                        for (uint32_t li = 0; li < sc.light_count; ++li) {
+                            const HiprLight l = load_light_uniform(sc.lights, li);
+                            if (!is_analytic_light(l.flags, l.data[6])) continue;
+                            float along, disc;
+                            const bool reachable = analytic_light_reachable(l, o, d, along, disc);
+                            if (!wave_any(reachable)) continue;
+                            asm volatile("" : "+v"(disc));
+                            const float t = analytic_light_distance_of(l, along, disc);
+                            if (reachable && t > tmin && t < tmax) { tmax = t; pay_x = 0; pay_y = 0; pay_z = __uint_as_float(HIPR_HIT_LIGHT | li); }
+                        }
+                    }
+                } else if (analytic_lights == 1) {
                     const float t = analytic_light_distance(held_light, o, d);
                     if (t > tmin && t < tmax) { tmax = t; pay_x = 0; pay_y = 0; pay_z = __uint_as_float(HIPR_HIT_LIGHT | held_light_index); }
                 } else if (analytic_lights > 1) {
@@ -288,7 +336,23 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
             if (__popcll(lmask) * HIPR_WIDE8_LEAF_VOTE_DEN > __popcll(nmask) * HIPR_WIDE8_LEAF_VOTE_NUM) {
                 if (leaf_mode) {
                     const uint4* rp = item_slot(tree.slots, item);
-                    const uint4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3];
+                    // The record's fourth quad -- the two triangle ids, the flags, the facing margin -- is read by the closest-hit selection, the culling, the selectors
+                    // and the coverage code. A shadow ray of a launch without coverage code (and without the counters) reads none of them but "is there a B", and that
+                    // it takes from e3: a record of one triangle holds e3 = +0 in every component (wide8_refit.h refit_make_record, host/Wide8Builder.cpp make_record),
+                    // and a B that is there has a corner that differs from a in some bit, so e3 != 0 in some component. Should a record ever hold a B
+                    // under e3 == 0, nothing is lost: with e3 == 0 the solve's p = d x e3 has only products with a zero in it, det = e2 . p is +-0 or NaN
+                    // (NaN: a ray component that is not finite), and triangle_inside refuses both (det != 0 is false for +-0; every ordered compare is false for NaN).
+                    // So the shadow lanes issue three loads per record where they issued four, and a wave whose record lanes are all shadow rays -- half the record
+                    // iterations of the atrium -- branches over the fourth. The shadow lanes' r3 is left undefined (an opaque empty asm: zeros would cost four moves
+                    // per iteration), and no statement a shadow lane's result depends on may read it.
+                    constexpr bool LEAN_RECORDS = !COVERAGE && !INSTRUMENT && MODE != TRACE_CLOSEST;
+                    const uint4 r0 = rp[0], r1 = rp[1], r2 = rp[2];
+                    uint4 r3;
+                    if constexpr (LEAN_RECORDS) {
+                        asm("" : "=v"(r3.x), "=v"(r3.y), "=v"(r3.z), "=v"(r3.w));
+                        if (MODE == TRACE_FUSED && !is_shadow) r3 = rp[3];
+                    } else r3 = rp[3];
+                    const bool e3_set = ((r2.y | r2.z | r2.w) & 0x7FFFFFFFu) != 0u;
                     const f3 a = mk3(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z));
                     const f3 e1 = mk3(__uint_as_float(r0.w), __uint_as_float(r1.x), __uint_as_float(r1.y));
                     const f3 e2 = mk3(__uint_as_float(r1.z), __uint_as_float(r1.w), __uint_as_float(r2.x));
@@ -308,7 +372,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
 #pragma unroll
                     for (int which = 0; which < 2; ++which) {
                         const uint32_t id = which == 0 ? r3.x : r3.y;
-                        testing = testing & (id != HIPR_LEAF8_NONE);
+                        if (LEAN_RECORDS && is_shadow) testing = testing & (which == 0 || e3_set);     // A is always there
+                        else testing = testing & (id != HIPR_LEAF8_NONE);
                         if (testing) {
                             if (INSTRUMENT) { tris += is_shadow ? 0u : 1u; shadow_tris += is_shadow ? 1u : 0u; }
                             TriangleTest test;
