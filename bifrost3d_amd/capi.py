@@ -270,7 +270,7 @@ C_ABI_SYMBOLS = (
     "hipr_group_create", "hipr_group_destroy", "hipr_group_size", "hipr_group_context", "hipr_group_gather_description", "hipr_group_upload_tables", "hipr_group_upload_scene",
     "hipr_group_set_scene_state", "hipr_group_set_entry_point", "hipr_group_use_scratch_accumulation", "hipr_group_set_frame", "hipr_group_set_samples_per_pass",
     "hipr_group_trace_pass", "hipr_group_accumulate_samples", "hipr_group_read_accumulation", "hipr_group_get_counters",
-    "hipr_debug_shading", "hipr_debug_shade", "hipr_debug_light", "hipr_debug_math", "hipr_debug_generate", "hipr_debug_sobol", "hipr_debug_valu_issue_rates", "hipr_debug_sample_offsets", "hipr_debug_trace_closest", "hipr_debug_trace_shadow", "hipr_debug_trace_fused", "hipr_debug_classify_hits",
+    "hipr_debug_shading", "hipr_debug_shade", "hipr_debug_light", "hipr_debug_math", "hipr_debug_generate", "hipr_debug_sobol", "hipr_debug_valu_issue_rates", "hipr_debug_sample_offsets", "hipr_debug_trace_closest", "hipr_debug_trace_shadow", "hipr_debug_trace_fused", "hipr_debug_trace_hinted", "hipr_debug_classify_hits",
 )
 
 
@@ -380,6 +380,7 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.hipr_debug_trace_closest.argtypes = [vp, C.POINTER(c_f), C.POINTER(c_u32), c_u32, C.POINTER(c_f)]
     lib.hipr_debug_trace_shadow.argtypes = [vp, C.POINTER(c_f), c_u32, C.POINTER(c_f)]
     lib.hipr_debug_trace_fused.argtypes = [vp, C.POINTER(c_f), C.POINTER(c_u32), c_u32, C.POINTER(c_f), c_u32, C.POINTER(c_f), C.POINTER(c_f)]
+    lib.hipr_debug_trace_hinted.argtypes = [vp, C.c_int, C.POINTER(c_f), C.POINTER(c_u32), c_u32, C.POINTER(c_f), c_u32, C.POINTER(c_u32), c_u32, C.POINTER(c_f), C.POINTER(c_f), C.POINTER(c_u32)]
     lib.hipr_debug_classify_hits.argtypes = [vp, C.POINTER(c_f), c_u32, C.c_int, c_u32, C.POINTER(c_u32)]
     if path is None:
         _lib = lib

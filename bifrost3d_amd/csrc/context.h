@@ -82,6 +82,7 @@ struct Wavefront {
     hipStream_t stream = nullptr;       // borrowed: wavefront 0 runs on the context stream, the others on their own
     Event shade_done[2], counts_copied[2], finished;   // by bounce parity: two bounces are in flight
     DeviceBuffer path[2][4], hits, shadow[3], queue_counts, order, nee_flags, sort_keys[2], sort_order, sort_temp;     // sort_*: ray_sort.hip (HIPR_COHERENCE_SORT=1)   // queue_counts: COUNT_LINES 64 B lines (see there); order: k_classify_hits' listing of a bounce's rays
+    DeviceBuffer camera_hints;          // the hint table of the wavefront's camera rays (wide8_kernels.h): one word per 64 queue entries, zeroed when the slots are partitioned
     PinnedWords host_counts;            // pinned: {continuing paths, shadow rays} per bounce parity, [4] staging word
     uint32_t first_slot = 0, n_slots = 0;      // first_slot: the wavefront's phase in the round-robin deal of 64-slot groups (partition_path_slots)
 
@@ -118,6 +119,15 @@ struct ResidentScene {
     DeviceScene args = {};              // also carries what is not the scene's: the tables, the sample offsets, the environment tint (hipr_create, hipr_upload_tables, hipr_set_scene_state)
     Wide8Scene wide8 = {};              // the 8-wide tree with leaf records: what the persistent kernels walk when the scene brings one
     uint32_t wide8_height = 0, wide_stack_entries = 0;
+    // The generation of the 8-wide tree, 1 ... 255: wide8.hint_tag carries it in its top byte, and so does every entry of a hint table that names a record slot of
+    // this tree (wide8_kernels.h hint_start). new_wide8_tree() is the one place that bumps it, called wherever the slot array is replaced or the kind of a slot can
+    // change (upload_wide8: upload and geometry update, host adoption included; install_rebuilt_trees: device rebuild, instance edits, pool growth). A refit keeps the
+    // kinds and the generation. hint_wraps counts the times the generation started over: the context clears its tables before the next pass (begin_pass).
+    uint32_t hint_generation = 0, hint_wraps = 0;
+    void new_wide8_tree() {
+        if (++hint_generation > 255u) { hint_generation = 1u; ++hint_wraps; }
+        wide8.hint_tag = hint_generation << 24;
+    }
     int stack_size = 16;
     int shading_models = 7;             // bit mask of the shading models the scene's instances reference
     // Kernel instantiations picked by what the pools hold. A geometry update leaves the material, texture and environment pools in place, so these keep what
@@ -349,6 +359,8 @@ struct Context {
     uint32_t traced_samples = 0;        // samples the radiance buffer holds since the last hipr_trace_pass
     float pass_depth_normalizer = 0.0f; // depth entry: far - near of the traced pass's camera
     DeviceBuffer radiance, accumulation, scratch_accumulation, counters, work_counters;
+    DeviceBuffer occluder_hints;        // the hint table of the shadow rays shade(0) queues (wide8_kernels.h): one word per 64 radiance slots, zeroed when the slots are partitioned
+    uint32_t hint_wraps_seen = 0;       // ResidentScene::hint_wraps when the hint tables were last cleared
     bool use_scratch = false;
     int entry = HIPR_ENTRY_PATH_TRACING;
     DeviceBuffer& active_accumulation() { return use_scratch ? scratch_accumulation : accumulation; }

@@ -102,10 +102,11 @@ struct TraceWork {
     const uint32_t* shadow_count;       // on the device: the entries of the wavefront's shadow queue; nullptr in a launch over the path queue alone
     uint32_t upper_bound;               // of the rays of the launch: sizes the grid
     const uint32_t* sorted = nullptr;   // ray_sort.hip's listing of the launch's rays (HIPR_RAY_SORT builds)
+    uint32_t* hints = nullptr;          // the launch's hint table (wide8_kernels.h): one word per 64 entries of `in` (closest-only) or per 64 radiance slots (the others); nullptr: no hints
 };
 
 // Every instantiation of a kernel family has the family's type: picking a kernel is picking a pointer.
-using Wide8Kernel = void (*)(DeviceScene, Wide8Scene, PathState, float4*, ShadowQueue, float4*, const uint32_t*, const uint32_t*, uint32_t*, int, DeviceCounters*, const uint32_t*);
+using Wide8Kernel = void (*)(DeviceScene, Wide8Scene, PathState, float4*, ShadowQueue, float4*, const uint32_t*, const uint32_t*, uint32_t*, int, DeviceCounters*, const uint32_t*, uint32_t*);
 using Wide4Kernel = void (*)(DeviceScene, PathState, float4*, ShadowQueue, float4*, const uint32_t*, const uint32_t*, uint32_t*, int, DeviceCounters*);
 using ClosestKernel = void (*)(DeviceScene, PathState, float4*, const uint32_t*, DeviceCounters*);
 using ShadowKernel = void (*)(DeviceScene, ShadowQueue, float4*, const uint32_t*, DeviceCounters*);
@@ -142,7 +143,8 @@ void launch_wide8(HiprContext* c, const Wavefront& w, const TraceWork& work, int
     if constexpr (!INSTRUMENT && MODE != TRACE_CLOSEST) if (lean && !opaque && c->scene.coverage_textures_r8) kernel = k_trace_wide8<STACK, MODE, INSTRUMENT, true, false, true>;
     if (lean && opaque) kernel = k_trace_wide8<STACK, MODE, INSTRUMENT, false>;
     hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(TRACE_BLOCK), 0, w.stream, c->scene.args, c->scene.wide8, work.in, w.hits.as<float4>(), w.shadow_queue(), c->radiance.as<float4>(),
-                       work.closest_count, work.shadow_count, p.work_counter, c->knobs.refill_below, c->counters.as<DeviceCounters>(), work.sorted);
+                       work.closest_count, work.shadow_count, p.work_counter, c->knobs.refill_below, c->counters.as<DeviceCounters>(), work.sorted,
+                       INSTRUMENT || work.sorted ? nullptr : work.hints);      // the counting and the sorted instantiations have no code for hints: their counters and order are the oracle's
 }
 
 // One persistent launch over the 4-wide tree (kernels.h).
@@ -248,6 +250,16 @@ void launch_shade(HiprContext* c, const Wavefront& w, const HiprCameraState& cam
     c->shade_unit().shade(c->scene.shading_models, a);
 }
 
+// The hint tables of the trace launches (wide8_kernels.h) start empty: an all-zero word names no tree. Called where nothing is queued: when the slots are partitioned
+// (new buffers, and entries that stand for other pixels) and when the scene's tree generation has wrapped (begin_pass).
+int clear_hint_tables(HiprContext* c) {
+    for (Wavefront& w : c->wavefronts) if (w.camera_hints.ptr) HIP_TRY(hipMemsetAsync(w.camera_hints.ptr, 0, w.camera_hints.bytes, c->stream));
+    if (c->occluder_hints.ptr) HIP_TRY(hipMemsetAsync(c->occluder_hints.ptr, 0, c->occluder_hints.bytes, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));      // the wavefronts' own streams are not ordered behind the context's
+    c->hint_wraps_seen = c->scene.hint_wraps;
+    return HIPR_OK;
+}
+
 // Splits the path slots of a pass (owned tiles x 64 x samples_per_pass) over the wavefronts on a tile (= wave) boundary and sizes the
 // queues and the per-sample radiance buffer; small passes stay one wavefront. Buffers only ever grow. The accumulation is not touched.
 int partition_path_slots(HiprContext* c) {
@@ -271,7 +283,7 @@ int partition_path_slots(HiprContext* c) {
         const size_t bytes = size_t(std::max(w.n_slots, 64u)) * 16;
         if (g >= c->wavefront_count && !second_slot) {   // queues of wavefronts this pass size does not use go back to the allocator
             for (auto& buffers : w.path) for (DeviceBuffer& b : buffers) b.release();
-            w.hits.release(); w.order.release(); w.nee_flags.release();
+            w.hits.release(); w.order.release(); w.nee_flags.release(); w.camera_hints.release();
             w.sort_keys[0].release(); w.sort_keys[1].release(); w.sort_order.release(); w.sort_temp.release();
             for (DeviceBuffer& b : w.shadow) b.release();
             continue;
@@ -279,6 +291,7 @@ int partition_path_slots(HiprContext* c) {
         for (int i = 0; i < 2; ++i) for (int j = 0; j < 4; ++j) r |= w.path[i][j].resize(j == 3 ? bytes / 2 : bytes);      // [3]: the 8-byte meta records
         r |= w.hits.resize(bytes);
         r |= w.order.resize(bytes / 4);
+        r |= w.camera_hints.resize(bytes / 16 / 64 * sizeof(uint32_t));      // one word per 64 queue entries (bytes / 16 entries, a multiple of 64)
         if (c->knobs.shade_split) r |= w.nee_flags.resize(bytes / 16);
 #if HIPR_RAY_SORT
         if (c->knobs.coherence_sort) {      // both queues of a fused launch: 2 x n_slots entries
@@ -297,7 +310,8 @@ int partition_path_slots(HiprContext* c) {
     }
     r |= c->radiance.resize(slots * 16);
     if (two_slots) r |= c->radiance_other.resize(slots * 16);
-    return r;
+    r |= c->occluder_hints.resize(std::max<uint64_t>(slots, 64u) / 64u * sizeof(uint32_t));      // one word per 64 radiance slots
+    return r ? r : clear_hint_tables(c);
 }
 
 void set_frame_divisors(FrameInfo& f) { f.by_samples_per_pass = make_divisor(f.samples_per_pass); f.by_tiles_x = make_divisor(f.tiles_x); }
@@ -337,8 +351,12 @@ int enqueue_bounce(HiprContext* c, Wavefront& w, const HiprCameraState& camera, 
     }
 
     c->begin_timed(HIPR_KERNEL_TRACE_CLOSEST, w.stream);
-    if (k > 0 && fused) trace_rays<TRACE_FUSED>(c, w, {w.path_state(parity), in_count, shadow_in, 2u * bound});
-    else trace_rays<TRACE_CLOSEST>(c, w, {w.path_state(parity), in_count, nullptr, bound});
+    // Hints (wide8_kernels.h): the camera rays start on the record their pixel's samples hit in the last pass, the shadow rays shade(0) queued on the record that
+    // stopped their pixel's last. From bounce 1 on (closest hits) and bounce 2 on (shadow rays) neighbouring entries have nothing in common any more: measured
+    // worthless there (profiles/ab_trace_hints.txt section 0), so those launches get no table.
+    const bool hinted = c->use_wide8();
+    if (k > 0 && fused) trace_rays<TRACE_FUSED>(c, w, {w.path_state(parity), in_count, shadow_in, 2u * bound, nullptr, hinted && k == 1 ? c->occluder_hints.as<uint32_t>() : nullptr});
+    else trace_rays<TRACE_CLOSEST>(c, w, {w.path_state(parity), in_count, nullptr, bound, nullptr, hinted && k == 0 ? w.camera_hints.as<uint32_t>() : nullptr});
     c->end_timed(w.stream);
     if (k > 0 && !fused) {
         c->begin_timed(HIPR_KERNEL_TRACE_SHADOW, w.stream);
@@ -496,6 +514,8 @@ int begin_pass(HiprContext* c, int slot, bool pipelined) {
         if (int s = finish_slot(c, slot)) return s;
         c->next_slot = 1 - slot;
     } else if (int s = finish_all(c)) return s;
+    if (c->hint_wraps_seen != c->scene.hint_wraps)      // the tree generation started over: an old entry could carry a new tree's tag. A scene writer has drained every pass since.
+        if (int s = clear_hint_tables(c)) return s;
     if (slot != c->traced_slot) std::swap(c->radiance, c->radiance_other);      // `radiance` is the buffer of the pass being traced / last traced
     c->traced_slot = c->active_slot = slot;
     HiprContext::PassSlot& ps = c->pass_slots[slot];
@@ -1317,6 +1337,75 @@ int hipr_debug_trace_fused(HiprContext* c, const float* closest_rays, const uint
         HIP_TRY(hipMemcpy(result.data(), bacc.ptr, result.size() * 4, hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < n_shadow; ++i) out_transmittance[i] = result[4 * i];
     }
+    c->total = {};
+    c->total.closest_rays = n_closest;
+    c->total.shadow_rays = n_shadow;
+    return HIPR_OK;
+}
+
+// The launches of the three entries above over the 8-wide tree, each GIVEN A HINT TABLE (wide8_kernels.h): `mode` 0 = closest-only (n_shadow must be 0; the table is
+// keyed by ray index / 64), 1 = shadow-only (n_closest must be 0), 2 = fused (both keyed by shadow ray index / 64: the radiance slot of ray i is i). `hints` holds
+// `hint_words` words -- at least one per 64 rays of the keyed kind -- that the launch reads and writes; they are returned as the launch left them. An entry that carries the
+// resident tree's tag (*out_tag, when asked for) must name a leaf record: anything else in such an entry is refused here, since the kernel would read a node as a record.
+int hipr_debug_trace_hinted(HiprContext* c, int mode, const float* closest_rays, const uint32_t* skip, uint32_t n_closest, const float* shadow_rays, uint32_t n_shadow, uint32_t* hints,
+                            uint32_t hint_words, float* out_hits, float* out_transmittance, uint32_t* out_tag) {
+    if (int s = check_context(c)) return s;
+    if (!c->scene.ready) return fail(HIPR_ERROR_NOT_READY, "no scene uploaded");
+    if (!c->use_wide8()) return fail(HIPR_ERROR_UNSUPPORTED, "hipr_debug_trace_hinted: hints are the 8-wide kernel's");
+    const uint32_t tag = c->scene.wide8.hint_tag;
+    if (out_tag) *out_tag = tag;
+    if (mode < 0 || mode > 2 || (mode == TRACE_CLOSEST && n_shadow) || (mode == TRACE_SHADOW && n_closest)) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_trace_hinted: mode %d with %u + %u rays", mode, n_closest, n_shadow);
+    if ((n_closest && (!closest_rays || !out_hits)) || (n_shadow && (!shadow_rays || !out_transmittance))) return fail(HIPR_ERROR_INVALID_ARGUMENT, "null argument");
+    if (n_closest > 0x7FFFFFFFu || n_shadow > 0x7FFFFFFFu) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_trace_hinted: more than 2^31 rays of a kind");
+    if (n_closest + n_shadow == 0) return HIPR_OK;
+    const uint32_t keyed = mode == TRACE_CLOSEST ? n_closest : n_shadow;
+    if (!hints || uint64_t(hint_words) * 64u < keyed) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_trace_hinted: %u hint words for %u rays", hint_words, keyed);
+    if (int s = drain(c)) return s;
+    {      // which slots are leaf records: the refit's list (made at upload and by every tree install)
+        std::vector<uint32_t> leaves(c->scene.refit_leaf_count);
+        if (!leaves.empty()) HIP_TRY(hipMemcpy(leaves.data(), c->scene.refit_leaf_slots.ptr, leaves.size() * 4, hipMemcpyDeviceToHost));
+        std::vector<bool> is_record(c->scene.wide8.slot_count, false);
+        for (uint32_t slot : leaves) if (slot < is_record.size()) is_record[slot] = true;
+        for (uint32_t i = 0; i < hint_words; ++i)
+            if ((hints[i] ^ tag) < (1u << 24) && ((hints[i] & 0xFFFFFFu) >= is_record.size() || !is_record[hints[i] & 0xFFFFFFu]))
+                return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_trace_hinted: entry %u carries the tree's tag and names slot %u, which is no leaf record", i, hints[i] & 0xFFFFFFu);
+    }
+    const size_t nc = std::max(n_closest, 1u), ns = std::max(n_shadow, 1u);      // an empty queue still has its buffers
+    std::vector<float> o(nc * 4, 0.0f), d(nc * 4, 0.0f), so(ns * 4, 0.0f), sd(ns * 4, 0.0f), rad(ns * 4, 0.0f), ones(ns * 4, 1.0f);
+    std::vector<uint32_t> meta(nc * 2, 0u);
+    if (n_closest) debug_prepare_rays(closest_rays, n_closest, o, d);
+    for (uint32_t i = 0; i < n_closest; ++i) { meta[2 * i] = i; meta[2 * i + 1] = skip ? skip[i] : HIPR_NO_TRIANGLE; }
+    for (uint32_t i = 0; i < n_shadow; ++i) {
+        std::memcpy(&so[4 * i], shadow_rays + 8 * size_t(i), 12);
+        so[4 * i + 3] = shadow_rays[8 * size_t(i) + 7];       // tmax
+        std::memcpy(&sd[4 * i], shadow_rays + 8 * size_t(i) + 4, 12);
+        std::memcpy(&sd[4 * i + 3], &i, 4);                   // slot
+    }
+    const uint32_t counts[2] = {n_closest, n_shadow};
+    DeviceBuffer bo, bd, bm, bh, bso, bsd, br, bacc, bc, bhints;
+    int r = bo.upload(o.data(), o.size() * 4, c->stream) | bd.upload(d.data(), d.size() * 4, c->stream) | bm.upload(meta.data(), meta.size() * 4, c->stream) | bh.resize(nc * 16) |
+            bso.upload(so.data(), so.size() * 4, c->stream) | bsd.upload(sd.data(), sd.size() * 4, c->stream) | br.upload(ones.data(), ones.size() * 4, c->stream) |
+            bacc.upload(rad.data(), rad.size() * 4, c->stream) | bc.upload(counts, 8, c->stream) | bhints.upload(hints, size_t(hint_words) * 4, c->stream);
+    if (r) return HIPR_ERROR_OUT_OF_MEMORY;
+    HIP_TRY(hipMemsetAsync(c->counters.ptr, 0, sizeof(DeviceCounters), c->stream));
+    PathState in = {bo.as<float4>(), bd.as<float4>(), nullptr, bm.as<uint2>()};
+    Wavefront w;
+    w.stream = c->stream;
+    w.hits = std::move(bh);
+    w.shadow[0] = std::move(bso); w.shadow[1] = std::move(bsd); w.shadow[2] = std::move(br);
+    std::swap(c->radiance, bacc);      // the launch writes the context's radiance buffer: this call's, for its duration
+    if (mode == TRACE_CLOSEST) trace_rays<TRACE_CLOSEST>(c, w, {in, bc.as<uint32_t>(), nullptr, n_closest, nullptr, bhints.as<uint32_t>()});
+    else if (mode == TRACE_SHADOW) trace_rays<TRACE_SHADOW>(c, w, {PathState{}, nullptr, bc.as<uint32_t>() + 1, n_shadow, nullptr, bhints.as<uint32_t>()});
+    else trace_rays<TRACE_FUSED>(c, w, {in, bc.as<uint32_t>(), bc.as<uint32_t>() + 1, n_closest + n_shadow, nullptr, bhints.as<uint32_t>()});
+    std::swap(c->radiance, bacc);
+    if (int finish_status = finish_all(c)) return finish_status;
+    if (n_closest) HIP_TRY(hipMemcpy(out_hits, w.hits.ptr, size_t(n_closest) * 16, hipMemcpyDeviceToHost));
+    if (n_shadow) {
+        std::vector<float> result(size_t(n_shadow) * 4);
+        HIP_TRY(hipMemcpy(result.data(), bacc.ptr, result.size() * 4, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n_shadow; ++i) out_transmittance[i] = result[4 * i];
+    }
+    HIP_TRY(hipMemcpy(hints, bhints.ptr, size_t(hint_words) * 4, hipMemcpyDeviceToHost));
     c->total = {};
     c->total.closest_rays = n_closest;
     c->total.shadow_rays = n_shadow;

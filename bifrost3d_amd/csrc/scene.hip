@@ -344,6 +344,7 @@ int ResidentScene::upload_wide8(const HiprSceneDesc* s, uint32_t height, bool cu
     for (int a = 0; a < 3; ++a) { wide8.grid_min[a] = s->wide8_grid_min[a]; wide8.grid_cell[a] = s->wide8_grid_cell[a]; }
     wide8.cull_backfaces = cull_backfaces ? 1u : 0u;
     wide8_height = height;
+    new_wide8_tree();      // the slots may be another tree's: no hint taken from the old ones names a record of these
     return HIPR_OK;
 }
 
@@ -1035,6 +1036,7 @@ int ResidentScene::install_rebuilt_trees(const RebuiltTrees& built, hipStream_t 
     wide8.slot_count = built.wide8.slot_count;
     for (int a = 0; a < 3; ++a) { wide8.grid_min[a] = built.wide8.grid_min[a]; wide8.grid_cell[a] = built.wide8.grid_cell[a]; }
     wide8_height = built.wide8.height;
+    new_wide8_tree();
     const uint32_t bvh_max_depth = built.deepest + 1u;      // BvhBuildResult::max_depth
     stack_size = bvh_max_depth <= 16 ? 16 : (bvh_max_depth <= 32 ? 32 : 64);
     queue_triangle_records(st);

@@ -39,7 +39,21 @@ struct Wide8Scene {
     uint32_t slot_count;
     float grid_min[3], grid_cell[3];
     uint32_t cull_backfaces;     // hipr_set_backface_culling: closest hits clearly on the back of a one-sided record triangle are stepped over
+    uint32_t hint_tag;           // the tree's generation (1 ... 255) in the top byte: what a hint table's entry carries there to name a record slot of THIS tree (hint_start)
 };
+
+// A HINT is the record slot a ray looks at first: `tag | slot` in one word of a table the launch is given (nullptr: no hints), where the tag's top byte is the generation
+// of the tree the slot was taken from (Wide8Scene::hint_tag; never 0, and a table starts all zero, so an empty entry names no tree). hint_start decides whether an entry
+// may be used -- it carries this tree's tag and its slot lies inside the tree -- and, where it may, puts the ray on that record with the ROOT AS A GROUP OF ITS OWN, ITS ONE
+// CHILD STILL PENDING: bit `octant` of `pending` stands for position octant ^ octant = 0, slot base + 0 = 0, an inner node. The next-item step of the traversal loop
+// then yields the root and leaves (gx, gy) = (1 << 24, 1 << 8), the state an unhinted ray starts in, so the loop itself has no code for hints.
+HD bool hint_start(uint32_t hint, uint32_t hint_tag, uint32_t slot_count, uint32_t octant, uint32_t& item, uint32_t& gy) {
+    const uint32_t slot = hint & 0xFFFFFFu;
+    if ((hint ^ hint_tag) >= (1u << 24) || slot >= slot_count) return false;
+    item = slot | 0x80000000u;      // ITEM_RECORD
+    gy = (1u << octant) | (1u << 8);
+    return true;
+}
 
 // LDS stack entries (8 bytes each) by tree height: the stack holds at most one group per level above the current one.
 constexpr int WIDE8_STACK_SHALLOW = 12;      // 12 KB per block of two waves: twelve blocks per CU, six waves per SIMD
@@ -112,16 +126,50 @@ __device__ __forceinline__ bool item_on_node(uint32_t item) { return int32_t(ite
 // the slot's address: the 24-bit multiply drops the top bit, and its 30-bit product is an offset the loads take next to the scalar base
 __device__ __forceinline__ const uint4* item_slot(const uint4* slots, uint32_t item) { return (const uint4*)((const char*)slots + __umul24(item, 64u)); }
 
+// The next item of a ray whose current group is (gx, gy): the child behind the lowest pending bit, which is taken off the group, or ITEM_FINISHED when none is pending
+// (the caller has popped the stack before, so an empty group is the end of the traversal). Only the low three bits of `octant` are read. One text for the kernel's
+// loop, which expands it in place, and for next_item_of_group below, through which the host build of the tests runs it (tests/native/TraceHintStartHost.hip).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define WIDE8_VALID_BELOW(gx, position) __popc(__builtin_amdgcn_ubfe(gx, 24u, position))
+#else
+#define WIDE8_VALID_BELOW(gx, position) __builtin_popcount(((gx) >> 24) & ((1u << (position)) - 1u))      // the host build of the tests
+#endif
+#define WIDE8_NEXT_ITEM(item, gx, gy, octant)                                                                                                                          \
+    {                                                                                                                                                                  \
+        const bool done = (gy & 0xFFu) == 0u;                                                                                                                          \
+        const uint32_t p = uint32_t(__builtin_ctz(gy | 0x100u));      /* the low byte is non-zero unless the ray is done */                                            \
+        gy &= gy - 1u;                                                /* (of a ray that is done this clears a bit nobody reads again) */                               \
+        const uint32_t position = (p ^ octant) & 7u;                                                                                                                   \
+        const uint32_t slot = (gx & 0xFFFFFFu) + uint32_t(WIDE8_VALID_BELOW(gx, position));              /* base + the valid children in lower positions */            \
+        const uint32_t record = ((gy >> position) & 0x100u) ^ 0x100u;                                    /* the child is not an inner node */                          \
+        item = done ? ITEM_FINISHED : (slot | record << 23);          /* 0x100 << 23: ITEM_RECORD */                                                                   \
+    }
+HD uint32_t next_item_of_group(uint32_t gx, uint32_t& gy, uint32_t octant) {
+    uint32_t item;
+    WIDE8_NEXT_ITEM(item, gx, gy, octant)
+    return item;
+}
+
 // COVERAGE_R8: ... and every coverage texture is single-channel 8-bit, linear (kernels.h material_coverage_r8).
 // COVERAGE: the scene holds triangles that are not statically opaque (coverage textures, cut-outs, partial coverage): a shadow ray that hits one samples its material's
 // coverage. Scenes without any (the common case; decided at upload) run the instantiation without that code: it is a fifth of the kernel's instructions and, though never
 // executed there, it weighs on the register allocation of the loop around it (profiles/r04_ab_trace_without_coverage.txt).
+// HINTS (`hints`, nullptr: none; off in the counting and SORTED instantiations, whose counters and order are the oracle's): a ray may look at one record before it
+// starts on the root (hint_start above). The result does not depend on what the table holds:
+//   * a closest-only launch (the camera rays of a pass) keys the table by ray_index >> 6 -- entry i of a wavefront is the same pixel and sample in every pass, and its 64
+//     neighbours are one pixel's samples -- and stores the record of the ray's final hit at the retire. It is carried there above the three bits of `octant`, whose
+//     readers mask them, so that it costs no register (profiles/ab_trace_hints.txt section 4). The hinted record only seeds tmax; `closer` is independent of order (ties go to the lower
+//     id), and met again the record finds t == tmax and id == pay_z and changes nothing.
+//   * the shadow rays of a launch without coverage code key it by pay_k >> 6 (64 path slots) and the fully shadowed ones store the record that stopped them at the retire
+//     (carried in ray_index, which a shadow ray does not read again). Any hit ends such a ray with exactly +0, whichever occluder is found first. With coverage code a
+//     record tested twice would apply its transmittance twice: no hints there.
+// Lanes race for an entry with plain aligned word stores; whichever wins is a good hint, and a stale or cold entry costs one record visit.
 // SORTED: the rays are taken in the order of `sorted` (ray_sort.hip: closest-hit rays first, each kind by origin cell and direction octant) instead of queue order;
 // every result is stored where it is in queue order, so nothing downstream sees the difference.
 template <int STACK, int MODE, bool INSTRUMENT, bool COVERAGE = true, bool SORTED = false, bool COVERAGE_R8 = false>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wide8_waves_per_simd(STACK)))) void k_trace_wide8(DeviceScene sc, Wide8Scene tree, PathState in, float4* hits, ShadowQueue q,
         float4* radiance, const uint32_t* closest_count_ptr, const uint32_t* shadow_count_ptr, uint32_t* work_counter, int refill_below, DeviceCounters* counters,
-        const uint32_t* sorted = nullptr) {
+        const uint32_t* sorted = nullptr, uint32_t* hints = nullptr) {
     __shared__ uint2 s_stack[STACK * TRACE_BLOCK];
     uint2* stack = s_stack + threadIdx.x;
     const uint32_t n_closest = MODE != TRACE_SHADOW ? *closest_count_ptr : 0u;
@@ -130,6 +178,10 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
     const unsigned long long lt = (1ull << lane) - 1ull;
     const uint32_t chunk_size = min(TRACE_CHUNK_MAX, max(64u, (n / (gridDim.x * (TRACE_BLOCK / 64u) * 2u)) & ~63u));
 
+    // The hints (the kernel's header): the camera rays' in the closest-only launches, the occluders' where shadow rays run without the coverage code.
+    constexpr bool CAMERA_HINTS = !INSTRUMENT && !SORTED && MODE == TRACE_CLOSEST;
+    constexpr bool OCCLUDER_HINTS = !INSTRUMENT && !SORTED && !COVERAGE && MODE != TRACE_CLOSEST;
+    constexpr bool HINTED = CAMERA_HINTS || OCCLUDER_HINTS;
     uint32_t chunk_next = 0, chunk_end = 0;   // wave uniform
     uint32_t shard = (blockIdx.x & 7u) * (TRACE_SHARDS / 8u) + ((blockIdx.x >> 3) % (TRACE_SHARDS / 8u));     // blocks of one XCD start on neighbouring shards
     bool exhausted = false;
@@ -192,7 +244,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
                 }
             }
             if (chunk_next < chunk_end) {
-                idx = chunk_next + __popcll(idle & lt);
+                // (the hinted instantiations count the idle lanes below this one with v_mbcnt: `lt` is then not kept, and its two registers make room for the hints)
+                idx = chunk_next + (HINTED ? __builtin_amdgcn_mbcnt_hi(uint32_t(idle >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(idle), 0u)) : uint32_t(__popcll(idle & lt)));
                 refill = !item_active(item) && idx < chunk_end;
                 chunk_next = min(chunk_next + uint32_t(__popcll(idle)), chunk_end);
             }
@@ -213,6 +266,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
         uint32_t entry = 0;
         uint2 meta = make_uint2(0u, HIPR_NO_TRIANGLE);
         float4 ro = make_float4(0, 0, 0, 0), rdv = ro, rr = ro;
+        uint32_t hint = 0u;                        // no tree's tag: hint_start refuses it
         if (refill) {
             if (MODE == TRACE_FUSED) new_is_shadow = idx >= n_closest;
             entry = SORTED ? sorted[idx] : idx;
@@ -223,6 +277,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
                 }
             } else if constexpr (MODE != TRACE_SHADOW) {    // a dead entry's origin and direction are loaded (the entry is one of the launch's) and not used
                 meta = in.meta[entry]; ro = in.o_tmin[entry]; rdv = in.d_pdf[entry];
+                if constexpr (CAMERA_HINTS) if (hints) hint = hints[entry >> 6];
             }
         }
         // ... the scalar ones last: their wait passes under the vector loads'. (Issued first, the light's twelve registers are live across the address arithmetic above,
@@ -235,6 +290,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
                 if constexpr (MODE != TRACE_CLOSEST) {
                     acc.x += pay_x; acc.y += pay_y; acc.z += pay_z;
                     if (!adds_nothing) radiance[pay_k] = acc;
+                    if constexpr (OCCLUDER_HINTS) if (hints && adds_nothing && int32_t(ray_index) < 0) hints[pay_k >> 6] = tree.hint_tag | (ray_index & 0xFFFFFFu);
                 }
             } else if constexpr (MODE != TRACE_SHADOW) {    // analytic area lights, LightSources.cu:31-70, in the order of the scene's list
                 if constexpr (LEAN_RETIRE) {
@@ -273,6 +329,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
                     }
                 }
                 hits[ray_index] = make_float4(tmax, pay_x, pay_y, pay_z);
+                if constexpr (CAMERA_HINTS) if (hints && octant >= 8u) hints[ray_index >> 6] = tree.hint_tag | (octant >> 8);      // (a light in front of the hit: the record is still the pixel's best guess)
             }
             item = ITEM_IDLE;
         }
@@ -281,9 +338,10 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
             is_shadow = new_is_shadow;
             bool dead = false;
             if (new_is_shadow) {
-                ray_index = entry - n_closest;
+                ray_index = OCCLUDER_HINTS ? 0u : entry - n_closest;      // with hints: the record that stopped the ray (ITEM_RECORD set), 0 until one does
                 pay_x = rr.x; pay_y = rr.y; pay_z = rr.z;
                 pay_k = __float_as_uint(rdv.w);
+                if constexpr (OCCLUDER_HINTS) if (hints) hint = hints[pay_k >> 6];       // a second, dependent load: in the rounds of these launches that refill shadow rays
                 tmin = 0.0f; tmax = ro.w;
             } else {
                 ray_index = entry;
@@ -308,6 +366,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
                 sp = 0;
                 gx = 1u << 24; gy = 1u << 8;       // the root as a group of its own (one inner child in position 0 of base 0), already taken:
                 item = tree.slot_count == 0 ? ITEM_FINISHED : 0u;      // the ray starts on the root node
+                if constexpr (HINTED) hint_start(hint, tree.hint_tag, tree.slot_count, octant, item, gy);      // ... or on the record its hint names
             }
         }
         unsigned long long busy = wave_ballot(item_active(item));
@@ -405,6 +464,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
                                     if (pay_x < 0.0000001f && pay_y < 0.0000001f && pay_z < 0.0000001f) {   // fully shadowed: the ray is done
                                         pay_x = pay_y = pay_z = 0.0f;
                                         testing = false;
+                                        if constexpr (OCCLUDER_HINTS) ray_index = item;
                                         gy = 0u; sp = 0;        // nothing left to visit: the common tail below retires the ray
                                     }
                                 }
@@ -416,6 +476,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
                                     const float facing = which == 0 ? test.det : __uint_as_float(__float_as_uint(test.det) ^ ((flags & 16u) << 27));
                                     const bool refused = facing < (which == 0 ? refuse_a_below : refuse_b_below);
                                     const bool closer = !refused & (id != pay_k) & (t > tmin) & ((t < tmax) | ((t == tmax) & (id < __float_as_uint(pay_z))));
+                                    if constexpr (CAMERA_HINTS) octant = closer ? (item << 8) | (octant & 7u) : octant;      // the record of the best hit so far, above the octant's three bits
                                     tmax = closer ? t : tmax; pay_x = closer ? u : pay_x; pay_y = closer ? v : pay_y; pay_z = closer ? __uint_as_float(id) : pay_z;
                                 }
                             }
@@ -493,13 +554,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(wid
                     const uint2 popped = stack[sp * TRACE_BLOCK];
                     gx = popped.x; gy = popped.y;
                 }
-                const bool done = (gy & 0xFFu) == 0u;
-                const uint32_t p = uint32_t(__builtin_ctz(gy | 0x100u));      // the low byte is non-zero unless the ray is done
-                gy &= gy - 1u;                                                // (of a ray that is done this clears a bit nobody reads again)
-                const uint32_t position = (p ^ octant) & 7u;
-                const uint32_t slot = (gx & 0xFFFFFFu) + uint32_t(__popc(__builtin_amdgcn_ubfe(gx, 24u, position)));      // base + the valid children in lower positions
-                const uint32_t record = ((gy >> position) & 0x100u) ^ 0x100u;                                            // the child is not an inner node
-                item = done ? ITEM_FINISHED : (slot | record << 23);          // 0x100 << 23: ITEM_RECORD
+                WIDE8_NEXT_ITEM(item, gx, gy, octant)
             }
             busy = wave_ballot(item_active(item));
         } while (busy && (exhausted || __popcll(busy) >= refill_below));

@@ -542,3 +542,21 @@ class Context:
         self._check(self.lib.hipr_debug_trace_fused(self.handle, closest_rays.ctypes.data_as(fp), sk, len(closest_rays), shadow_rays.ctypes.data_as(fp), len(shadow_rays),
                                                     hits.ctypes.data_as(fp), out.ctypes.data_as(fp)), "hipr_debug_trace_fused")
         return hits, out
+
+    def debug_trace_hinted(self, mode, closest_rays, skip, shadow_rays, hints):
+        """hipr_debug_trace_hinted: the closest-only (mode 0), shadow-only (1) or fused (2) launch over the 8-wide tree with the hint table `hints` (uint32 words, tag | record
+        slot) -> (hits (n_closest, 4), transmittance (n_shadow,), the table as the launch left it, the resident tree's tag)."""
+        closest_rays = np.ascontiguousarray(closest_rays, np.float32).reshape(-1, 8)
+        shadow_rays = np.ascontiguousarray(shadow_rays, np.float32).reshape(-1, 8)
+        hints = np.array(hints, np.uint32).reshape(-1)      # a copy: the call writes it
+        hits = np.zeros((len(closest_rays), 4), np.float32)
+        out = np.zeros(len(shadow_rays), np.float32)
+        tag = C.c_uint32(0)
+        fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, np.uint32)
+            assert len(skip) == len(closest_rays)
+        sk = skip.ctypes.data_as(up) if skip is not None else None
+        self._check(self.lib.hipr_debug_trace_hinted(self.handle, int(mode), closest_rays.ctypes.data_as(fp), sk, len(closest_rays), shadow_rays.ctypes.data_as(fp), len(shadow_rays),
+                                                     hints.ctypes.data_as(up), len(hints), hits.ctypes.data_as(fp), out.ctypes.data_as(fp), C.byref(tag)), "hipr_debug_trace_hinted")
+        return hits, out, hints, tag.value

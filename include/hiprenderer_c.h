@@ -868,6 +868,14 @@ int hipr_debug_trace_shadow(HiprContext* context, const float* rays, uint32_t n,
  * n_shadow shadow rays in the layouts of the two entries above; either count may be 0, and its pointers are then not read. */
 int hipr_debug_trace_fused(HiprContext* context, const float* closest_rays, const uint32_t* skip, uint32_t n_closest, const float* shadow_rays, uint32_t n_shadow,
                            float* out_hits, float* out_transmittance);
+/* The three launches above over the 8-wide tree (HIPR_ERROR_UNSUPPORTED for other searches), GIVEN A HINT TABLE: the record slot a ray looks at before it starts on the
+ * root, `tag | slot` per word, the tag being the resident tree's generation in the top byte (*out_tag when out_tag is not NULL; never 0, and it changes whenever the
+ * tree is replaced). mode 0 = closest-only (n_shadow = 0; word = ray index / 64), 1 = shadow-only (n_closest = 0), 2 = fused (1 and 2: word = shadow ray index / 64).
+ * hints: hint_words words, at least one per 64 rays of the keyed kind, read and written by the launch and returned as it left them. A word that carries the tree's tag
+ * must name a leaf record (HIPR_ERROR_INVALID_ARGUMENT otherwise); any other word is ignored by the kernel. Results do not depend on what the table holds. Launches
+ * that have no code for hints (instrumentation on; shadow rays of a scene with coverage) leave the table as given. */
+int hipr_debug_trace_hinted(HiprContext* context, int mode, const float* closest_rays, const uint32_t* skip, uint32_t n_closest, const float* shadow_rays, uint32_t n_shadow,
+                            uint32_t* hints, uint32_t hint_words, float* out_hits, float* out_transmittance, uint32_t* out_tag);
 /* K5c: the listing pass of a bounce on n given hits (hits_n4: float4 {t, u, v, bits(triangle | 0x80000000 + light | 0xFFFFFFFF miss)} per queue entry). out_order[p]
  * = the queue entry the shade kernel takes at place p: every chunk of 4096 places holds that chunk's own entries as [plain surface hits | coated surface hits |
  * everything else], each class in queue order. coat_classes != 0 lists the hits on triangles of a coated material apart (needs an uploaded scene, and every
