@@ -259,10 +259,55 @@ assert C.sizeof(HiprIndexSegment) == 8 and C.sizeof(HiprPoolGrowth) == 112
 assert C.sizeof(HiprEnvironmentBuild) == 48 and C.sizeof(HiprLightingResult) == 24 and C.sizeof(HiprLightSample) == 32
 assert C.sizeof(HiprTexelEdit) == 40 and C.sizeof(HiprTexelUpdateResult) == 16
 
+
+class HiprVertexEdit(C.Structure):
+    _fields_ = [("first_vertex", c_u32), ("vertex_count", c_u32), ("geometry", C.c_void_p), ("texcoords", C.c_void_p), ("tints", C.c_void_p), ("emissions", C.c_void_p)]
+
+
+class HiprVertexUpdateResult(C.Structure):
+    _fields_ = [("refit", HiprRefitResult), ("moved_triangles", c_u32), ("candidate_triangles", c_u32), ("changed_triangles", c_u32), ("all_triangles_opaque", c_u32)]
+
+
+assert C.sizeof(HiprVertexEdit) == 40 and C.sizeof(HiprVertexUpdateResult) == 64
+
+VERTEX_ATTRIBUTES = ("geometry", "texcoords", "tints", "emissions")
+
+
+def vertex_geometry_dtype():
+    """HiprVertexGeometry as a numpy record: the position and the octahedral normal, 16 bytes."""
+    import numpy as np
+    return np.dtype([("position", "<f4", (3,)), ("oct_normal", "<i2", (2,))])
+
+
+def vertex_edits(edits):
+    """Dicts of `first` (a vertex of the RESIDENT pools) and any of `geometry` (records of vertex_geometry_dtype(), or raw (n, 4) words), `texcoords` (n, 2) float32,
+    `tints` (n,) uint32 and `emissions` (n, 3) float32 -- `count` in place of the arrays' length for a call that is to be refused -- as the HiprVertexEdit array of
+    hipr_update_scene_vertices (one spare element: never a null array). Returns (array, keep-alive): the array points into the arrays of keep-alive."""
+    import numpy as np
+    edits = list(edits)
+    array, keep = (HiprVertexEdit * max(len(edits), 1))(), []
+    kinds = dict(geometry=(None, 16), texcoords=(np.float32, 8), tints=(np.uint32, 4), emissions=(np.float32, 12))
+    for k, edit in enumerate(edits):
+        pointers, count = [], None
+        for name in VERTEX_ATTRIBUTES:
+            values = edit.get(name)
+            if values is None:
+                pointers.append(None)
+                continue
+            dtype, size = kinds[name]
+            values = np.ascontiguousarray(values) if dtype is None else np.ascontiguousarray(values, dtype)
+            assert values.nbytes % size == 0, name
+            count = values.nbytes // size if count is None else count
+            assert values.nbytes // size == count, "the arrays of one edit describe the same vertices"
+            keep.append(values)
+            pointers.append(values.ctypes.data)
+        array[k] = HiprVertexEdit(int(edit["first"]), int(edit.get("count", count or 0)), *pointers)
+    return array, keep or [None]
+
 # Every symbol include/hiprenderer_c.h declares; tests check the library exports all of them.
 C_ABI_SYMBOLS = (
     "hipr_create", "hipr_destroy", "hipr_last_error", "hipr_device_count", "hipr_set_stream",
-    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_build_bvh2", "hipr_group_build_bvh2", "hipr_debug_build_times", "hipr_build_wide8", "hipr_group_build_wide8", "hipr_debug_collapse_times", "hipr_build_wide4", "hipr_group_build_wide4", "hipr_debug_collapse4_times", "hipr_rebuild_scene_trees", "hipr_group_rebuild_scene_trees", "hipr_edit_scene_instances", "hipr_group_edit_scene_instances", "hipr_append_scene_pools", "hipr_group_append_scene_pools", "hipr_update_scene_lighting", "hipr_group_update_scene_lighting", "hipr_debug_lighting_times", "hipr_update_scene_texels", "hipr_group_update_scene_texels", "hipr_debug_texel_update_times", "hipr_debug_scene_buffer_bytes", "hipr_debug_append_times", "hipr_debug_rebuild_times", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
+    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_build_bvh2", "hipr_group_build_bvh2", "hipr_debug_build_times", "hipr_build_wide8", "hipr_group_build_wide8", "hipr_debug_collapse_times", "hipr_build_wide4", "hipr_group_build_wide4", "hipr_debug_collapse4_times", "hipr_rebuild_scene_trees", "hipr_group_rebuild_scene_trees", "hipr_edit_scene_instances", "hipr_group_edit_scene_instances", "hipr_append_scene_pools", "hipr_group_append_scene_pools", "hipr_update_scene_lighting", "hipr_group_update_scene_lighting", "hipr_debug_lighting_times", "hipr_update_scene_texels", "hipr_group_update_scene_texels", "hipr_debug_texel_update_times", "hipr_update_scene_vertices", "hipr_group_update_scene_vertices", "hipr_debug_vertex_update_times", "hipr_debug_scene_buffer_bytes", "hipr_debug_append_times", "hipr_debug_rebuild_times", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
     "hipr_set_frame", "hipr_owned_pixel_count",
     "hipr_render_pass", "hipr_set_samples_per_pass", "hipr_trace_pass", "hipr_accumulate_samples", "hipr_read_accumulation", "hipr_scatter_tiles", "hipr_synchronize", "hipr_get_counters",
     "hipr_device_malloc", "hipr_device_free", "hipr_device_memset", "hipr_copy_to_host", "hipr_present_flipped",
@@ -333,6 +378,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.hipr_update_scene_texels.argtypes = [vp, C.POINTER(HiprTexelEdit), c_u32, C.POINTER(HiprTexelUpdateResult)]
     lib.hipr_group_update_scene_texels.argtypes = [vp, C.POINTER(HiprTexelEdit), c_u32, C.POINTER(HiprTexelUpdateResult)]
     lib.hipr_debug_texel_update_times.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.hipr_update_scene_vertices.argtypes = [vp, C.POINTER(HiprVertexEdit), c_u32, C.POINTER(HiprVertexUpdateResult)]
+    lib.hipr_group_update_scene_vertices.argtypes = [vp, C.POINTER(HiprVertexEdit), c_u32, C.POINTER(HiprVertexUpdateResult)]
+    lib.hipr_debug_vertex_update_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.hipr_debug_scene_buffer_bytes.argtypes = [vp, C.c_int, C.POINTER(c_u64)]
     lib.hipr_debug_append_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.hipr_debug_rebuild_times.argtypes = [vp, C.POINTER(C.c_double)]

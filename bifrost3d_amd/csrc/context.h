@@ -101,6 +101,7 @@ constexpr int HOST_COUNT_WORDS = 8 + COUNT_LINES * COUNT_PAIR_STRIDE;   // pinne
 // What the argument checks of a description derive on their way (preflight_scene).
 struct LightingScratch;      // below, with the other scratches
 struct TexelScratch;
+struct VertexScratch;
 
 struct Preflight {
     uint32_t wide_stack_need = 0;       // worst-case stack need of the 4-wide tree: derived, not taken from the caller
@@ -206,6 +207,9 @@ struct ResidentScene {
     // The device work of hipr_update_scene_texels, which has checked every rectangle against uploaded_textures (hipr_internal_check_texel_update): the rectangles
     // written into the texel pool and the flags that follow texels decided again (texel_update.h).
     int update_texels(const HiprTexelEdit* edits, uint32_t edit_count, TexelScratch& scratch, hipStream_t stream, HiprTexelUpdateResult* out);
+    // The device work of hipr_update_scene_vertices, which has checked every range against the host copies (hipr_internal_check_vertex_update): the ranges written
+    // into the vertex pools and everything an upload derives from vertex data brought along (vertex_update.h).
+    int update_vertices(const HiprVertexEdit* edits, uint32_t edit_count, VertexScratch& scratch, hipStream_t stream, HiprVertexUpdateResult* out);
     double append_ms[3] = {0.0, 0.0, 0.0};      // of the last append_pools: the allocations (host clock), the device-to-device copies of the resident parts, the tails and the mirror segments (events)
     Event append_events[3];             // made by the first append_pools
 
@@ -315,6 +319,14 @@ struct TexelScratch : Scratch<TexelBuffers> {
     Event events[4];                    // around the rectangle writes, the flag pass and the leaf pass; made by the first update
 };
 
+// The device scratch of hipr_update_scene_vertices (vertex_update.h): the segment table, a word per instance and the ranges' rows packed, a byte per pool vertex
+// for each kind of mark, and the passes' few words.
+struct VertexBuffers { DeviceBuffer staging, marks_geometry, marks_texcoords, words; };
+struct VertexScratch : Scratch<VertexBuffers> {
+    double staging_ms = 0.0, write_ms = 0.0, refit_ms = 0.0, flag_ms = 0.0;      // of the last vertex update
+    Event events[4];                    // around the pool writes, the refit passes with the records, the flag pass with the leaf pass; made by the first update
+};
+
 // The context; HiprContext, the C-ABI's opaque type, is this and nothing else.
 struct Context {
     int device = 0;
@@ -410,6 +422,7 @@ struct Context {
     RebuildScratch rebuild;             // hipr_rebuild_scene_trees, which also runs over the two above
     LightingScratch lighting;           // hipr_update_scene_lighting's environment build
     TexelScratch texel_update;          // hipr_update_scene_texels
+    VertexScratch vertex_update;        // hipr_update_scene_vertices
 
     hipEvent_t next_event() {
         if (events_used == event_pool.size()) {

@@ -40,10 +40,11 @@ struct MaterialUpdateArrays {
 };
 constexpr uint32_t MATERIAL_TRACE_FLAG_WORD = 11, MATERIAL_TRACE_WORDS = 12, MATERIAL_SHADE_INDEX_WORD = 15, MATERIAL_SHADE_WORDS = 32;
 
-// Pass 1 for triangle t; reports what the triangle contributes to the two reductions.
-MRHD void update_triangle_material(const MaterialUpdateArrays& a, uint32_t t, bool& opaque, bool& coated) {
+// Pass 1 for triangle t; reports what the triangle contributes to the two reductions. `touched`: the triangle is recomputed (the material edit and the texel edit ask
+// a.touched of its instance; the vertex edit decides per triangle, vertex_update.h).
+MRHD void update_triangle_material(const MaterialUpdateArrays& a, uint32_t t, bool touched, bool& opaque, bool& coated) {
     HiprTriangle& tri = a.triangles[t];
-    if (!a.touched[tri.instance_index]) {
+    if (!touched) {
         opaque = (tri.flags & HIPR_TRIANGLE_OPAQUE) != 0;
         coated = (a.triangle_class[t] & 1u) != 0;
         return;
@@ -58,6 +59,9 @@ MRHD void update_triangle_material(const MaterialUpdateArrays& a, uint32_t t, bo
     a.triangle_class[t] = uint8_t(cls);
     opaque = (flags & HIPR_TRIANGLE_OPAQUE) != 0;
     coated = cls != 0;
+}
+MRHD void update_triangle_material(const MaterialUpdateArrays& a, uint32_t t, bool& opaque, bool& coated) {
+    update_triangle_material(a, t, a.touched[a.triangles[t].instance_index] != 0, opaque, coated);
 }
 
 // Pass 2 for one leaf slot.

@@ -18,6 +18,7 @@
 #include "pool_growth.h"
 #include "environment_build.h"
 #include "texel_update.h"
+#include "vertex_update.h"
 
 #include <hip/hip_runtime.h>
 
@@ -994,6 +995,127 @@ int ResidentScene::update_texels(const HiprTexelEdit* edits, uint32_t edit_count
     return HIPR_OK;
 }
 
+// The device work of hipr_update_scene_vertices (vertex_update.h). The scratch is allocated BEFORE the scene is touched: a failed allocation leaves the scene as
+// found. Then, as the other writers: not ready, ONE staging copy (the segment table, a word per instance, the rows), the passes on the stream, the host copies. What
+// follows the pool writes depends on what the edits carry: geometry -- the moved triangles with the bounds, the refit of the tree and the records, and the state
+// refit_transforms leaves (tree_stale; awaits_rebuild when a pair parted; the per-pixel trace hints stay, a refit keeps the kinds of the slots); texcoords or tints --
+// the records; texcoords, when a resident instance's material leaves its triangles' flags to its coverage texture (the host copies answer that) -- the flag pass and
+// the leaf pass. Two synchronises, the refit's: for the bounds, and at the end.
+int ResidentScene::update_vertices(const HiprVertexEdit* edits, uint32_t edit_count, VertexScratch& x, hipStream_t st, HiprVertexUpdateResult* out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    VertexPlan plan;
+    plan_vertex_edits(edits, edit_count, plan);
+    std::vector<uint32_t> decides(std::max<size_t>(uploaded_instances.size(), 1), 0u);
+    bool decides_flags = false;
+    if (plan.carries[VERTEX_POOL_TEXCOORDS])
+        for (size_t i = 0; i < uploaded_instances.size(); ++i)
+            if ((uploaded_instances[i].mesh_flags & HIPR_MESH_TEXCOORDS) &&
+                deciding_coverage_texture(uploaded_materials[size_t(uploaded_instances[i].material_index)], uploaded_textures.data(), uint32_t(uploaded_textures.size()))) { decides[i] = 1u; decides_flags = true; }
+    const bool moves = plan.carries[VERTEX_POOL_GEOMETRY];
+    const bool records = moves || plan.carries[VERTEX_POOL_TEXCOORDS] || plan.carries[VERTEX_POOL_TINTS];
+    // the staging buffer: the table, the instance words, the rows -- each part a multiple of 16 bytes
+    const size_t table_bytes = plan.table.size() * sizeof(VertexSegment), decides_bytes = (decides.size() * sizeof(uint32_t) + 15u) & ~size_t(15);
+    const size_t staging_bytes = table_bytes + decides_bytes + size_t(plan.word_count) * 4u;
+    std::vector<uint8_t> packed(staging_bytes, uint8_t(0));
+    std::memcpy(packed.data(), plan.table.data(), table_bytes);
+    std::memcpy(packed.data() + table_bytes, decides.data(), decides.size() * sizeof(uint32_t));
+    pack_vertex_rows(plan, packed.data() + table_bytes + decides_bytes);
+    int r = x.staging.resize(staging_bytes);
+    r |= x.words.resize(VERTEX_SCRATCH_WORDS * sizeof(uint32_t));
+    if (moves) r |= x.marks_geometry.resize(std::max<size_t>(uploaded_vertex_count, 1));
+    if (decides_flags) r |= x.marks_texcoords.resize(std::max<size_t>(uploaded_vertex_count, 1));
+    if (r) {
+        (void)hipGetLastError();      // the failed allocation's error is answered here: it must not meet the next call's check
+        return HIPR_ERROR_OUT_OF_MEMORY;
+    }
+    for (Event& e : x.events)
+        if (!e) e = make_event(hipEventDefault);
+    const bool timed = x.events[0] && x.events[1] && x.events[2] && x.events[3];
+    begin_write();
+    // 1. the staging copy, then the words and the marks
+    HIP_TRY(hipMemcpyAsync(x.staging.ptr, packed.data(), staging_bytes, hipMemcpyHostToDevice, st));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (timed) HIP_TRY(hipEventRecord(x.events[0], st));
+    if (moves) HIP_TRY(hipMemsetAsync(x.marks_geometry.ptr, 0, uploaded_vertex_count, st));
+    if (decides_flags) HIP_TRY(hipMemsetAsync(x.marks_texcoords.ptr, 0, uploaded_vertex_count, st));
+    HIP_TRY(hipMemsetAsync(x.words.ptr, 0, VERTEX_SCRATCH_WORDS * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(x.words.ptr), 1, 1, st));
+    const VertexPools pools = {{geometry.as<uint32_t>(), texcoords.as<uint32_t>(), tints.as<uint32_t>(), emissions.as<uint32_t>()},
+                               {moves ? x.marks_geometry.as<uint8_t>() : nullptr, decides_flags ? x.marks_texcoords.as<uint8_t>() : nullptr}};
+    hipLaunchKernelGGL(k_write_vertex_words, dim3(uint32_t((plan.word_count + VERTEX_UPDATE_BLOCK - 1) / VERTEX_UPDATE_BLOCK)), dim3(VERTEX_UPDATE_BLOCK), 0, st,
+                       reinterpret_cast<const VertexSegment*>(x.staging.as<uint8_t>()), uint32_t(plan.table.size()), reinterpret_cast<const uint32_t*>(x.staging.as<uint8_t>() + table_bytes + decides_bytes),
+                       plan.word_count, pools);
+    HIP_TRY(hipGetLastError());
+    if (timed) HIP_TRY(hipEventRecord(x.events[1], st));
+    float grid_min[3] = {wide8.grid_min[0], wide8.grid_min[1], wide8.grid_min[2]}, grid_cell[3] = {wide8.grid_cell[0], wide8.grid_cell[1], wide8.grid_cell[2]};
+    if (moves) {
+        // 2. the moved triangles and the scene's bounds, then the tree (wide8_refit.h)
+        HIP_TRY(hipMemsetAsync(refit_scratch.ptr, 0, REFIT_SCRATCH_BYTES, st));
+        const uint32_t blocks = (args.triangle_count + REFIT_BLOCK - 1) / REFIT_BLOCK;
+        hipLaunchKernelGGL(k_refit_marked_triangles, dim3(blocks), dim3(REFIT_BLOCK), 0, st, triangles.as<HiprTriangle>(), args.triangle_count, instances.as<HiprInstance>(), x.marks_geometry.as<uint8_t>(),
+                           indices.as<uint32_t>(), geometry.as<HiprVertexGeometry>(), refit_partial.as<RefitBound>(), x.words.as<uint32_t>());
+        hipLaunchKernelGGL(k_refit_bounds_final, dim3(1), dim3(REFIT_BLOCK), 0, st, refit_partial.as<RefitBound>(), blocks, refit_scratch.as<RefitBound>());
+        HIP_TRY(hipGetLastError());
+        RefitBound bounds[6];
+        HIP_TRY(hipMemcpyAsync(bounds, refit_scratch.ptr, sizeof(bounds), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));      // `packed` is read by now as well
+        const float lo[3] = {bounds[0].v, bounds[1].v, bounds[2].v}, hi[3] = {bounds[3].v, bounds[4].v, bounds[5].v};
+        refit_grid(lo, hi, grid_min, grid_cell);
+        queue_refit_tree<true>(grid_min, grid_cell, st);
+    }
+    if (records) queue_triangle_records(st);
+    HIP_TRY(hipGetLastError());
+    if (timed) HIP_TRY(hipEventRecord(x.events[2], st));
+    if (decides_flags) {
+        // 3. the flags of the triangles that read a marked texture coordinate, then the leaf records (queued whatever the pass finds: it writes only where bits differ)
+        const MaterialUpdateArrays a = {triangles.as<HiprTriangle>(), args.triangle_count, instances.as<HiprInstance>(), materials.as<HiprMaterial>(), indices.as<uint32_t>(),
+                                        reinterpret_cast<const float*>(args.texcoords), textures.as<HiprTexture>(), uint32_t(uploaded_textures.size()), texels.as<uint8_t>(),
+                                        reinterpret_cast<const uint32_t*>(x.staging.as<uint8_t>() + table_bytes), trace_triangles.as<uint32_t>(), shade_triangles.as<uint32_t>(), triangle_class.as<uint8_t>()};
+        hipLaunchKernelGGL(k_reflag_marked_triangles, dim3((args.triangle_count + VERTEX_UPDATE_BLOCK - 1) / VERTEX_UPDATE_BLOCK), dim3(VERTEX_UPDATE_BLOCK), 0, st, a, x.marks_texcoords.as<uint8_t>(),
+                           x.words.as<uint32_t>());
+        if (wide8.slot_count && refit_leaf_count)
+            hipLaunchKernelGGL(k_update_leaf_flags, dim3((refit_leaf_count + MATERIAL_UPDATE_BLOCK - 1) / MATERIAL_UPDATE_BLOCK), dim3(MATERIAL_UPDATE_BLOCK), 0, st, wide8_slots.as<HiprSlot8>(),
+                               refit_leaf_slots.as<uint32_t>(), refit_leaf_count, triangles.as<HiprTriangle>());
+        HIP_TRY(hipGetLastError());
+    }
+    if (timed) HIP_TRY(hipEventRecord(x.events[3], st));
+    // 4. the read-backs: the refit's flag and area, the four words
+    struct { uint32_t flag; uint32_t pad[3]; double area; } tail = {};
+    uint32_t words[4] = {all_triangles_opaque ? 1u : 0u, 0u, 0u, 0u};
+    if (moves) HIP_TRY(hipMemcpyAsync(&tail, refit_scratch.as<char>() + REFIT_SCRATCH_FLAG, sizeof(tail), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(words, x.words.ptr, sizeof(words), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float write_ms = 0.0f, refit_ms = 0.0f, flag_ms = 0.0f;
+    if (timed) {
+        HIP_TRY(hipEventElapsedTime(&write_ms, x.events[0], x.events[1]));
+        HIP_TRY(hipEventElapsedTime(&refit_ms, x.events[1], x.events[2]));
+        HIP_TRY(hipEventElapsedTime(&flag_ms, x.events[2], x.events[3]));
+    }
+    x.staging_ms = ms(t0, t1); x.write_ms = write_ms; x.refit_ms = refit_ms; x.flag_ms = flag_ms;
+    if (decides_flags) {
+        all_triangles_opaque = words[VERTEX_WORD_OPAQUE] != 0;
+        derive_switches_from_pools();
+    }
+    int needs_rebuild = 0;
+    if (moves) {
+        tree_stale = true;
+        for (int a = 0; a < 3; ++a) { wide8.grid_min[a] = grid_min[a]; wide8.grid_cell[a] = grid_cell[a]; }
+        current_half_area = tail.area;
+        needs_rebuild = tail.flag ? 1 : 0;      // a pair parted: this tree cannot hold the scene any more
+    }
+    out->refit.needs_rebuild = needs_rebuild;
+    out->refit.child_half_area = current_half_area;
+    out->refit.uploaded_half_area = uploaded_half_area;
+    for (int a = 0; a < 3; ++a) { out->refit.grid_min[a] = wide8.grid_min[a]; out->refit.grid_cell[a] = wide8.grid_cell[a]; }
+    out->moved_triangles = words[VERTEX_WORD_MOVED];
+    out->candidate_triangles = decides_flags ? words[VERTEX_WORD_DECIDED] : 0u;
+    out->changed_triangles = decides_flags ? words[VERTEX_WORD_CHANGED] : 0u;
+    out->all_triangles_opaque = all_triangles_opaque ? 1u : 0u;
+    ready = !needs_rebuild;
+    awaits_rebuild = !ready;
+    return HIPR_OK;
+}
+
 // The last step of hipr_rebuild_scene_trees, which has refused everything it refuses: the new resident arrays, and what an upload derives from them. The pools, the
 // instances and the lights stay; all_triangles_opaque, any_coated_triangle and the other switches cannot change under a permutation of the triangles and stay. The
 // 4-wide array is not rebuilt: tree_stale stays set until the next upload or geometry update, as after the refit.
@@ -1890,6 +2012,61 @@ int hipr_debug_texel_update_times(HiprContext* c, double* out4_ms) {
     if (!c || !out4_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_texel_update_times: null argument");
     const TexelScratch& x = c->texel_update;
     out4_ms[0] = x.staging_ms; out4_ms[1] = x.write_ms; out4_ms[2] = x.coverage_ms; out4_ms[3] = x.leaf_ms;
+    return HIPR_OK;
+}
+
+// Not part of the public header: every refusal of hipr_update_scene_vertices that is not a failed allocation, and nothing else -- no HIP call, the device and the
+// books stay as they are. The group asks every member before any member writes.
+int hipr_internal_check_vertex_update(HiprContext* c, const HiprVertexEdit* edits, uint32_t edit_count, const HiprVertexUpdateResult* out) {
+    const char* who = "hipr_update_scene_vertices";
+    if (int st = check_context(c)) return st;
+    const ResidentScene& r = c->scene;
+    if (!r.ready) return fail(HIPR_ERROR_NOT_READY, "%s: no scene uploaded, one a failed call left behind, or one that awaits hipr_rebuild_scene_trees", who);
+    if (!out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null result", who);
+    if (edit_count && !edits) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null array with a non-zero count", who);
+    for (uint32_t k = 0; k < edit_count; ++k) {
+        const HiprVertexEdit& e = edits[k];
+        if (e.vertex_count == 0) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: edit %u has no vertices", who, k);
+        if (!e.geometry && !e.texcoords && !e.tints && !e.emissions) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: edit %u carries no attribute", who, k);
+        if (uint64_t(e.first_vertex) + e.vertex_count > r.uploaded_vertex_count)
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: edit %u is %u vertices from %u on, the resident pools hold %u", who, k, e.vertex_count, e.first_vertex, r.uploaded_vertex_count);
+        if ((e.texcoords && !(r.uploaded_mesh_attributes & HIPR_MESH_TEXCOORDS)) || (e.tints && !(r.uploaded_mesh_attributes & HIPR_MESH_TINTS)) ||
+            (e.emissions && !(r.uploaded_mesh_attributes & HIPR_MESH_EMISSIVE)))
+            return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: edit %u carries an attribute whose pool the device does not hold (hipr_append_scene_pools brings one)", who, k);
+        for (uint32_t v = 0; v < e.vertex_count; ++v) {
+            if (e.geometry && !(std::isfinite(e.geometry[v].position[0]) && std::isfinite(e.geometry[v].position[1]) && std::isfinite(e.geometry[v].position[2])))
+                return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: edit %u: the position of vertex %u is not finite", who, k, e.first_vertex + v);
+            if (e.texcoords && !(std::isfinite(e.texcoords[2 * size_t(v)]) && std::isfinite(e.texcoords[2 * size_t(v) + 1])))
+                return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: edit %u: the texture coordinate of vertex %u is not finite", who, k, e.first_vertex + v);
+        }
+    }
+    // what hipr_refit_scene_transforms refuses: the arrays another search walks are the ones this call leaves stale, and the exhaustive search's items are built on the host
+    if (r.wide8.slot_count == 0 || !c->use_wide8() || r.args.trace_item_count != 0 || r.args.triangle_count > 0x55555555u)
+        return fail(HIPR_ERROR_UNSUPPORTED, "%s: the uploaded scene is not traced through the 8-wide tree; edit on the host and upload the scene instead", who);
+    return HIPR_OK;
+}
+
+// Vertex edits of resident meshes (vertex_update.h): the ranges checked on the host, then ResidentScene::update_vertices.
+int hipr_update_scene_vertices(HiprContext* c, const HiprVertexEdit* edits, uint32_t edit_count, HiprVertexUpdateResult* out) {
+    if (int st = hipr_internal_check_vertex_update(c, edits, edit_count, out)) return st;
+    if (!edit_count) {
+        const ResidentScene& r = c->scene;
+        out->refit.needs_rebuild = 0; out->refit.child_half_area = r.current_half_area; out->refit.uploaded_half_area = r.uploaded_half_area;
+        for (int a = 0; a < 3; ++a) { out->refit.grid_min[a] = r.wide8.grid_min[a]; out->refit.grid_cell[a] = r.wide8.grid_cell[a]; }
+        out->moved_triangles = out->candidate_triangles = out->changed_triangles = 0u;
+        out->all_triangles_opaque = r.all_triangles_opaque ? 1u : 0u;
+        return HIPR_OK;
+    }
+    if (int finish_status = finish_all(c)) return finish_status;      // no pending pass may go on over vertices and triangles that are about to change
+    c->break_chain(c->stream);
+    ScratchGuard<VertexScratch> guard(c->vertex_update);
+    return c->scene.update_vertices(edits, edit_count, c->vertex_update, c->stream, out);
+}
+
+int hipr_debug_vertex_update_times(HiprContext* c, double* out4_ms) {
+    if (!c || !out4_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_vertex_update_times: null argument");
+    const VertexScratch& x = c->vertex_update;
+    out4_ms[0] = x.staging_ms; out4_ms[1] = x.write_ms; out4_ms[2] = x.refit_ms; out4_ms[3] = x.flag_ms;
     return HIPR_OK;
 }
 

@@ -30,6 +30,11 @@ def load_host_library() -> C.CDLL:
     lib.hiprh_scene_model_pose.argtypes = [vp, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_uint), C.POINTER(C.c_float), C.c_uint]
     lib.hiprh_scene_update_materials.argtypes = [vp, C.POINTER(capi.HiprMaterialUpdate), C.c_uint, C.POINTER(capi.HiprInstanceMaterial), C.c_uint]
     lib.hiprh_scene_update_texels.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, C.c_ulonglong, C.POINTER(C.c_int)]
+    lib.hiprh_scene_update_vertices.argtypes = [vp, C.POINTER(C.c_uint), C.POINTER(capi.HiprVertexEdit), C.c_uint, C.c_double]
+    lib.hiprh_scene_stage_vertex_edits.argtypes = [vp, C.POINTER(C.c_uint), C.POINTER(capi.HiprVertexEdit), C.c_uint, C.POINTER(capi.HiprVertexEdit)]
+    lib.hiprh_scene_apply_staged.argtypes = [vp, C.c_double]
+    lib.hiprh_vertex_geometry.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint, vp]
+    lib.hiprh_scene_mesh_range.argtypes = [vp, C.c_uint, C.POINTER(C.c_uint)]
     lib.hiprh_scene_rebuild.argtypes = [vp]
     lib.hiprh_scene_stage_model.argtypes = [vp, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float]
     lib.hiprh_scene_adopt_trees.argtypes = [vp, vp, C.c_uint, vp, C.c_uint, vp, C.POINTER(capi.HiprWide8BuildResult)]
@@ -258,6 +263,58 @@ class Scene:
             if status != 1:
                 return False
         return True
+
+    def _mesh_vertex_edits(self, edits):
+        edits = list(edits)
+        array, keep = capi.vertex_edits(edits)
+        return edits, array, keep, (C.c_uint * max(len(edits), 1))(*[int(e["mesh"]) for e in edits])
+
+    def update_vertices(self, edits, rebuild_threshold: float = 0.0):
+        """Vertex edits WITHOUT a rebuild (SceneBuilder::update_vertices, the whole host path): `edits` as capi.vertex_edits takes them, each with a `mesh` and its
+        `first` MESH-relative. True when the topology was kept, False when the builder rebuilt the scene, None when the edits were refused (nothing touched)."""
+        edits, array, keep, meshes = self._mesh_vertex_edits(edits)
+        status = self.lib.hiprh_scene_update_vertices(self.handle, meshes, array, len(edits), rebuild_threshold)
+        if status == -1:
+            raise capi.HiprError("hiprh_scene_update_vertices failed")
+        return None if status == -2 else status == 1
+
+    def stage_vertex_edits(self, edits):
+        """SceneBuilder::stage_vertex_edits: the pools and the flags are written, the triangles and the trees stay behind -- `desc` must not be read until
+        apply_staged(), rebuild() or an adoption has caught up. Returns the edits in POOL coordinates, what Context.update_scene_vertices takes, or None when they
+        were refused (nothing touched)."""
+        edits, array, keep, meshes = self._mesh_vertex_edits(edits)
+        pooled = (capi.HiprVertexEdit * max(len(edits), 1))()
+        status = self.lib.hiprh_scene_stage_vertex_edits(self.handle, meshes, array, len(edits), pooled)
+        if status < 0:
+            raise capi.HiprError("hiprh_scene_stage_vertex_edits failed")
+        if status != 1:
+            return None
+        return [dict({name: e[name] for name in capi.VERTEX_ATTRIBUTES if e.get(name) is not None}, first=int(pooled[k].first_vertex)) for k, e in enumerate(edits)]
+
+    def apply_staged(self, rebuild_threshold: float = 0.0) -> bool:
+        """SceneBuilder::apply_staged_transforms: everything staged reaches the triangles and the trees. True when the topology was kept, False after a rebuild."""
+        status = self.lib.hiprh_scene_apply_staged(self.handle, rebuild_threshold)
+        if status < 0:
+            raise capi.HiprError("hiprh_scene_apply_staged failed")
+        return status == 1
+
+    def vertex_geometry(self, positions, normals=None) -> np.ndarray:
+        """Positions (n, 3) and normals (n, 3; None: a mesh without) packed as the geometry pool holds them (SceneBuilder::vertex_geometry): records of
+        capi.vertex_geometry_dtype()."""
+        positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        normals = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(len(positions), 3)
+        out = np.zeros(len(positions), capi.vertex_geometry_dtype())
+        floats = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+        if self.lib.hiprh_vertex_geometry(floats(positions), floats(normals), len(positions), C.c_void_p(out.ctypes.data)) != 0:
+            raise capi.HiprError("hiprh_vertex_geometry failed")
+        return out
+
+    def mesh_range(self, mesh: int) -> dict:
+        """Where a mesh lies in the pools: vertex_offset, vertex_count, index_offset (in triples), primitive_count, flags."""
+        out = (C.c_uint * 5)()
+        if self.lib.hiprh_scene_mesh_range(self.handle, mesh, out) != 1:
+            raise capi.HiprError(f"the scene has no mesh {mesh}")
+        return dict(vertex_offset=int(out[0]), vertex_count=int(out[1]), index_offset=int(out[2]), primitive_count=int(out[3]), flags=int(out[4]))
 
     def rebuild(self):
         """A fresh build (triangle flags, BVH2, 4-wide and 8-wide trees) over the instances and materials as they stand."""

@@ -81,13 +81,7 @@ uint32_t SceneBuilder::add_mesh(MeshData mesh) {
     for (const Vector3ui& p : mesh.primitives) { m_indices.push_back(p.x); m_indices.push_back(p.y); m_indices.push_back(p.z); }
     m_index_log.push_back({HIPR_SEGMENT_FROM_HOST, 3u * r.primitive_count});
     for (uint32_t i = 0; i < r.vertex_count; ++i) {
-        HiprVertexGeometry g = {};
-        g.position[0] = mesh.positions[i].x; g.position[1] = mesh.positions[i].y; g.position[2] = mesh.positions[i].z;
-        if (r.flags & HIPR_MESH_NORMALS) {
-            OctahedralNormal e = OctahedralNormal::encode_precise(mesh.normals[i]);
-            g.oct_normal[0] = e.encoding.x; g.oct_normal[1] = e.encoding.y;
-        }
-        m_geometry.push_back(g);
+        m_geometry.push_back(vertex_geometry(mesh.positions[i], (r.flags & HIPR_MESH_NORMALS) ? &mesh.normals[i] : nullptr));
         Vector2f tc = (r.flags & HIPR_MESH_TEXCOORDS) ? mesh.texcoords[i] : Vector2f{0, 0};
         m_texcoords.push_back(tc.x); m_texcoords.push_back(tc.y);
         m_tints.push_back((r.flags & HIPR_MESH_TINTS) ? mesh.tints[i] : 0xFFFFFFFFu);
@@ -100,6 +94,23 @@ uint32_t SceneBuilder::add_mesh(MeshData mesh) {
     m_meshes.push_back(r);
     m_pools_grew = true;
     return uint32_t(m_meshes.size() - 1);
+}
+
+HiprVertexGeometry SceneBuilder::vertex_geometry(Vector3f position, const Vector3f* normal) {
+    HiprVertexGeometry g = {};
+    g.position[0] = position.x; g.position[1] = position.y; g.position[2] = position.z;
+    if (normal) {
+        OctahedralNormal e = OctahedralNormal::encode_precise(*normal);
+        g.oct_normal[0] = e.encoding.x; g.oct_normal[1] = e.encoding.y;
+    }
+    return g;
+}
+
+bool SceneBuilder::mesh_range(uint32_t mesh, uint32_t (&out)[5]) const {
+    if (mesh >= m_meshes.size()) return false;
+    const MeshRecord& r = m_meshes[mesh];
+    out[0] = r.vertex_offset; out[1] = r.vertex_count; out[2] = r.index_offset; out[3] = r.primitive_count; out[4] = r.flags;
+    return true;
 }
 
 uint32_t SceneBuilder::add_material(const HiprMaterial& material) {
@@ -377,6 +388,53 @@ bool SceneBuilder::apply_staged_transforms(double rebuild_threshold) {
     }
     return true;
 }
+
+bool SceneBuilder::write_vertex_edits(const std::vector<VertexEdit>& edits, std::vector<HiprVertexEdit>* pool_edits) {
+    if (!m_built || has_staged_edits()) return false;
+    for (const VertexEdit& e : edits) {
+        if (e.mesh >= m_meshes.size() || e.vertex_count == 0 || (!e.geometry && !e.texcoords && !e.tints && !e.emissions)) return false;
+        const MeshRecord& r = m_meshes[e.mesh];
+        if (uint64_t(e.first_vertex) + e.vertex_count > r.vertex_count || size_t(r.vertex_offset) + r.vertex_count > m_built_pools.vertices) return false;
+        if ((e.texcoords && !m_built_pools.texcoords) || (e.tints && !m_built_pools.tints) || (e.emissions && !m_built_pools.emission)) return false;
+        for (uint32_t v = 0; v < e.vertex_count; ++v) {
+            if (e.geometry && !(std::isfinite(e.geometry[v].position[0]) && std::isfinite(e.geometry[v].position[1]) && std::isfinite(e.geometry[v].position[2]))) return false;
+            if (e.texcoords && !(std::isfinite(e.texcoords[2 * size_t(v)]) && std::isfinite(e.texcoords[2 * size_t(v) + 1]))) return false;
+        }
+    }
+    std::vector<bool> moved_mesh(m_meshes.size(), false), mapped_mesh(m_meshes.size(), false);
+    bool any_mapped = false;
+    for (const VertexEdit& e : edits) {
+        const size_t at = size_t(m_meshes[e.mesh].vertex_offset) + e.first_vertex, n = e.vertex_count;
+        if (e.geometry) { std::copy(e.geometry, e.geometry + n, m_geometry.begin() + ptrdiff_t(at)); moved_mesh[e.mesh] = true; }
+        if (e.texcoords) { std::copy(e.texcoords, e.texcoords + 2 * n, m_texcoords.begin() + ptrdiff_t(2 * at)); mapped_mesh[e.mesh] = true; any_mapped = true; }
+        if (e.tints) std::copy(e.tints, e.tints + n, m_tints.begin() + ptrdiff_t(at));
+        if (e.emissions) std::copy(e.emissions, e.emissions + 3 * n, m_emissions.begin() + ptrdiff_t(3 * at));
+        if (pool_edits) pool_edits->push_back({uint32_t(at), e.vertex_count, e.geometry, e.texcoords, e.tints, e.emissions});
+    }
+    if (any_mapped) {      // the flags that follow texture coordinates (csrc/material_rules.h), and the leaf records' copies
+        bool flags_changed = false;
+        for (HiprTriangle& triangle : m_triangles) {
+            if (!mapped_mesh[m_instance_mesh[triangle.instance_index]]) continue;
+            const HiprInstance& inst = m_instances[triangle.instance_index];
+            const uint32_t before = triangle.flags;
+            triangle.flags = hipr::triangle_flags(m_materials[size_t(inst.material_index)], inst, triangle.primitive_index, m_indices.data(), m_texcoords.data(), m_textures.data(), uint32_t(m_textures.size()), m_texels.data());
+            flags_changed = flags_changed || triangle.flags != before;
+        }
+        if (flags_changed) refresh_leaf_material_bits();
+    }
+    if (m_staged_moved.size() != m_instances.size()) m_staged_moved.assign(m_instances.size(), false);
+    for (size_t i = 0; i < m_instances.size(); ++i)
+        if (moved_mesh[m_instance_mesh[i]]) { m_staged_moved[i] = true; m_staged = true; }
+    return true;
+}
+
+bool SceneBuilder::update_vertices(const std::vector<VertexEdit>& edits, double rebuild_threshold, bool* refused) {
+    const bool written = write_vertex_edits(edits, nullptr);
+    if (refused) *refused = !written;
+    return written && apply_staged_transforms(rebuild_threshold);
+}
+
+bool SceneBuilder::stage_vertex_edits(const std::vector<VertexEdit>& edits, std::vector<HiprVertexEdit>& pool_edits) { return write_vertex_edits(edits, &pool_edits); }
 
 // The world-space corners of the triangles of the instances flagged in `moved`, recomputed in place from the instances' matrices, and the scene's bounds.
 void SceneBuilder::move_triangles(const std::vector<bool>& moved) {

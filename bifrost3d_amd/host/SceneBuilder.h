@@ -164,6 +164,29 @@ public:
     // hipr_update_scene_lighting takes for that).
     bool update_texels(uint32_t texture_index, uint32_t x, uint32_t y, uint32_t width, uint32_t height, const void* pixels, uint64_t row_pitch_bytes);
     bool environment_texels_edited() const { return m_environment_texels_edited; }
+    // Vertex edit of meshes of a BUILT scene without a rebuild (what hipr_update_scene_vertices does to the resident scene): vertices [first_vertex, first_vertex +
+    // vertex_count) of mesh `mesh` -- MESH-relative -- take the arrays that are not null, in the pools' own layout (geometry: vertex_geometry() packs a position and
+    // a normal as add_mesh does). Edits apply in order. update_vertices is the whole host path: the pools are written, the corners of the instances over those
+    // meshes recomputed (move_triangles), the coverage flags of their triangles decided again (csrc/material_rules.h) with the leaf records' bits, and the trees
+    // refitted under the rule of update_model_transforms: true = topology kept (desc() is then what hipr_update_scene_vertices leaves on the device), false = the
+    // scene was rebuilt (a parted pair, the ratio rule) -- or, with *refused set, nothing was touched: before the scene is built, with an instance edit staged, a
+    // mesh or a range the scene does not hold or the device does not hold yet (added since the last build), a count of 0, no array, an attribute whose pool did not
+    // exist at the last build, a position or texture coordinate that is not finite.
+    // stage_vertex_edits is the device path's companion, in the manner of stage_model_transforms: it writes the pools (they are the source data) and the flags,
+    // marks the instances over the meshes whose geometry changed as staged and appends the edits in POOL coordinates -- what hipr_update_scene_vertices takes -- to
+    // `pool_edits`; apply_staged_transforms() then brings triangles and trees along before desc() is next handed out. False, nothing touched: refused as above.
+    struct VertexEdit {
+        uint32_t mesh, first_vertex, vertex_count;
+        const HiprVertexGeometry* geometry;      // or null: positions and normals stay
+        const float* texcoords;                  // float2 each, or null
+        const uint32_t* tints;                   // or null
+        const float* emissions;                  // float3 each, or null
+    };
+    bool update_vertices(const std::vector<VertexEdit>& edits, double rebuild_threshold = 1.5, bool* refused = nullptr);
+    bool stage_vertex_edits(const std::vector<VertexEdit>& edits, std::vector<HiprVertexEdit>& pool_edits);
+    static HiprVertexGeometry vertex_geometry(Vector3f position, const Vector3f* normal);      // null: no normal, as a mesh without normals holds it
+    // vertex_offset, vertex_count, index_offset (in triples), primitive_count and flags of a mesh; false for a mesh the scene does not hold
+    bool mesh_range(uint32_t mesh, uint32_t (&out)[5]) const;
     const std::vector<HiprMaterial>& materials() const { return m_materials; }
     const std::vector<HiprLight>& lights() const { return m_lights; }
     const std::vector<HiprTexture>& textures() const { return m_textures; }      // slot 0, "no texture", included
@@ -213,6 +236,7 @@ private:
     void flatten_instance(uint32_t instance, std::vector<HiprTriangle>& world);
     bool trees_fit(uint32_t triangle_count, const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, const HiprSlot8* slots, const HiprWide8BuildResult& wide8) const;
     void note_instance_edit();
+    bool write_vertex_edits(const std::vector<VertexEdit>& edits, std::vector<HiprVertexEdit>* pool_edits);      // what update_vertices and stage_vertex_edits share
     void refresh_leaf_material_bits();      // bits 0..3 of every leaf record of the 8-wide tree from m_triangles' flags
     bool list_instance_edits(std::vector<HiprInstanceEdit>& edits) const;      // staged_instance_edits without its question about the pools
     // The pool sizes at the last build or adoption (build_trees_over): what the device holds when it follows the builder, and where the tails begin.

@@ -362,6 +362,64 @@ int hiprh_scene_update_texels(void* scene, unsigned texture_index, unsigned x, u
     } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_update_texels: %s\n", e.what()); return -1; }
 }
 
+namespace {
+std::vector<SceneBuilder::VertexEdit> mesh_vertex_edits(const unsigned* meshes, const HiprVertexEdit* edits, unsigned count) {
+    std::vector<SceneBuilder::VertexEdit> out(count);
+    for (unsigned k = 0; k < count; ++k) out[k] = {meshes[k], edits[k].first_vertex, edits[k].vertex_count, edits[k].geometry, edits[k].texcoords, edits[k].tints, edits[k].emissions};
+    return out;
+}
+}
+
+// Vertex edits of meshes of a built scene (SceneBuilder::update_vertices), the whole host path: edit k names mesh meshes[k] and, MESH-relative, the range and the
+// arrays of edits[k]. Returns 1 when the topology was kept, 0 when the scene was rebuilt, -2 when the edits were refused (nothing touched), -1 on error.
+int hiprh_scene_update_vertices(void* scene, const unsigned* meshes, const HiprVertexEdit* edits, unsigned count, double rebuild_threshold) {
+    if (!scene || (count && (!meshes || !edits))) return -1;
+    try {
+        bool refused = false;
+        const bool kept = static_cast<SceneBuilder*>(scene)->update_vertices(mesh_vertex_edits(meshes, edits, count), rebuild_threshold > 0.0 ? rebuild_threshold : 1.5, &refused);
+        return refused ? -2 : (kept ? 1 : 0);
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_update_vertices: %s\n", e.what()); return -1; }
+}
+
+// SceneBuilder::stage_vertex_edits: the pools and the flags are written, the triangles and the trees stay behind (hiprh_scene_desc must not be asked until
+// hiprh_scene_apply_staged, hiprh_scene_rebuild or an adoption has caught up); out_pool_edits[0 .. count) are the edits in POOL coordinates, what
+// hipr_update_scene_vertices takes. Returns 1, 0 when refused (nothing touched), -1 on error.
+int hiprh_scene_stage_vertex_edits(void* scene, const unsigned* meshes, const HiprVertexEdit* edits, unsigned count, HiprVertexEdit* out_pool_edits) {
+    if (!scene || (count && (!meshes || !edits || !out_pool_edits))) return -1;
+    try {
+        std::vector<HiprVertexEdit> pool_edits;
+        if (!static_cast<SceneBuilder*>(scene)->stage_vertex_edits(mesh_vertex_edits(meshes, edits, count), pool_edits)) return 0;
+        std::copy(pool_edits.begin(), pool_edits.end(), out_pool_edits);
+        return 1;
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_stage_vertex_edits: %s\n", e.what()); return -1; }
+}
+
+// SceneBuilder::apply_staged_transforms: everything staged reaches the triangles and the trees. Returns 1 when the topology was kept, 0 after a rebuild, -1 on error.
+int hiprh_scene_apply_staged(void* scene, double rebuild_threshold) {
+    if (!scene) return -1;
+    try { return static_cast<SceneBuilder*>(scene)->apply_staged_transforms(rebuild_threshold > 0.0 ? rebuild_threshold : 1.5) ? 1 : 0; }
+    catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_apply_staged: %s\n", e.what()); return -1; }
+}
+
+// SceneBuilder::vertex_geometry for `count` vertices: positions and (may be null) normals, float3 each, packed as the geometry pool holds them.
+int hiprh_vertex_geometry(const float* positions, const float* normals, unsigned count, HiprVertexGeometry* out) {
+    if (!positions || !out) return -1;
+    for (unsigned v = 0; v < count; ++v) {
+        const Vector3f normal = normals ? Vector3f(normals[3 * v], normals[3 * v + 1], normals[3 * v + 2]) : Vector3f(0, 0, 0);
+        out[v] = SceneBuilder::vertex_geometry(Vector3f(positions[3 * v], positions[3 * v + 1], positions[3 * v + 2]), normals ? &normal : nullptr);
+    }
+    return 0;
+}
+
+// SceneBuilder::mesh_range: out5 = vertex_offset, vertex_count, index_offset (in triples), primitive_count, flags. Returns 1, 0 for a mesh the scene does not hold.
+int hiprh_scene_mesh_range(void* scene, unsigned mesh, unsigned* out5) {
+    if (!scene || !out5) return -1;
+    uint32_t range[5];
+    if (!static_cast<SceneBuilder*>(scene)->mesh_range(mesh, range)) return 0;
+    std::copy(range, range + 5, out5);
+    return 1;
+}
+
 // SceneBuilder::rebuild: a fresh tree over the instances and materials as they stand. Returns 0, -1 on error.
 int hiprh_scene_rebuild(void* scene) {
     if (!scene) return -1;

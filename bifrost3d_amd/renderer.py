@@ -289,6 +289,30 @@ class Context:
         self._check(self.lib.hipr_debug_texel_update_times(self.handle, out), "hipr_debug_texel_update_times")
         return dict(staging=out[0], writes=out[1], coverage=out[2], leaves=out[3])
 
+    def update_scene_vertices(self, edits, group=None) -> dict:
+        """hipr_update_scene_vertices: new values for vertices of meshes the device holds, applied to the resident scene by kernels, no upload. `edits` as
+        capi.vertex_edits takes them, in POOL coordinates (Scene.stage_vertex_edits makes them). Returns a dict of status and, when it is HIPR_OK, needs_rebuild,
+        child_half_area, uploaded_half_area, grid_min, grid_cell, moved_triangles, candidate_triangles, changed_triangles and all_triangles_opaque: a refusal leaves
+        the scene as found and is the caller's to answer with the full path. `group`: a HiprGroup handle, for hipr_group_update_scene_vertices."""
+        edits = list(edits)
+        array, keep = capi.vertex_edits(edits)
+        result = capi.HiprVertexUpdateResult()
+        call, handle = (self.lib.hipr_group_update_scene_vertices, group) if group is not None else (self.lib.hipr_update_scene_vertices, self.handle)
+        status = call(handle, array, len(edits), C.byref(result))
+        if status != capi.HIPR_OK:
+            return dict(status=status)
+        refit = result.refit
+        return dict(status=status, needs_rebuild=bool(refit.needs_rebuild), child_half_area=refit.child_half_area, uploaded_half_area=refit.uploaded_half_area,
+                    grid_min=np.array(refit.grid_min[:], np.float32), grid_cell=np.array(refit.grid_cell[:], np.float32), moved_triangles=result.moved_triangles,
+                    candidate_triangles=result.candidate_triangles, changed_triangles=result.changed_triangles, all_triangles_opaque=bool(result.all_triangles_opaque))
+
+    def vertex_update_times(self) -> dict:
+        """Milliseconds of the last update_scene_vertices: the table and rows packed and their staging copy, the pool writes, the refit passes with the records, the
+        flag pass with the leaf pass."""
+        out = (C.c_double * 4)()
+        self._check(self.lib.hipr_debug_vertex_update_times(self.handle, out), "hipr_debug_vertex_update_times")
+        return dict(staging=out[0], writes=out[1], refit=out[2], flags=out[3])
+
     def lighting_times(self) -> dict:
         """Milliseconds of the last update_scene_lighting: allocations + uploads, kernels, the host's finish of the samples, read-back."""
         out = (C.c_double * 4)()

@@ -630,6 +630,46 @@ typedef struct HiprTexelUpdateResult {
     uint32_t environment_stale;      /* 1: an edited texture is the resident environment's map; see above */
 } HiprTexelUpdateResult;
 int hipr_update_scene_texels(HiprContext* context, const HiprTexelEdit* edits, uint32_t edit_count, HiprTexelUpdateResult* out);
+/* Vertex edits of meshes the device already holds, applied to the RESIDENT scene on the device (csrc/vertex_update.h): a skinned character, a cloth step, a sculpt
+ * stroke, a scrolled texture coordinate or a repainted vertex tint moves no index triple and changes no topology, so no flatten on the host, no tree build and no
+ * upload of any pool is needed. The reference cannot express the edit (Assets/Mesh.h knows meshes created and destroyed only). Each edit is a range of vertices of
+ * the RESIDENT pools -- an instance's vertex_offset + the mesh's own index -- with new values for any of the four per-vertex attributes; the edits are applied in
+ * list order, so where two overlap the later one wins. What an upload derives from vertex data follows:
+ *   positions    the world-space corners of every triangle that reads an edited vertex (through its instance's own index triples: mirrored instances and meshes
+ *                worn by several instances are served), the scene's bounds and the 8-wide tree's grid, every leaf record and the quantised boxes above it, the
+ *                trace records and the shading records;
+ *   normals      the shading records;
+ *   texcoords    the shading records, and HIPR_TRIANGLE_OPAQUE of the triangles whose material leaves the decision to its coverage texture (csrc/material_rules.h
+ *                covered_everywhere) with its copy in the trace records, bits 0..3 of the leaf records and the search instantiation that follows "all triangles
+ *                opaque";
+ *   tints        the shading records;
+ *   emissions    nothing: they are read from the pool.
+ * Afterwards the vertex pools, the triangles, the 8-wide tree, the trace and shading records, the grid, both half areas and the kernel instantiations the context
+ * picks are, byte for byte, what SceneBuilder::update_vertices and hipr_upload_scene on a fresh context leave. An empty list is HIPR_OK and changes nothing.
+ * When an edit carries geometry the BVH2 and the 4-wide arrays go stale exactly as after hipr_refit_scene_transforms, and `refit.needs_rebuild` = 1 (vertices that
+ * shared a world position at build time parted) leaves the scene awaiting hipr_rebuild_scene_trees, exactly as there. HIPRenderer::Renderer does not take this path.
+ * Checked on the host before the device is touched, each leaving the scene as found:
+ *   HIPR_ERROR_NOT_READY          no scene, a scene a failed call left behind, or a scene awaiting a rebuild;
+ *   HIPR_ERROR_INVALID_ARGUMENT   a null `out`; null `edits` with a non-zero count; an edit with `vertex_count` 0 or with all four pointers null; a range past the
+ *                                 resident pool; an attribute pointer whose resident pool is absent; a position or a texcoord that is not finite;
+ *   HIPR_ERROR_UNSUPPORTED        what hipr_refit_scene_transforms refuses: no 8-wide tree, another search walked, the exhaustive search's items, more than
+ *                                 0x55555555 triangles.
+ * Scratch (the packed staging buffer, a byte per pool vertex and kind of mark) is allocated before anything resident is written: a failed allocation is
+ * HIPR_ERROR_OUT_OF_MEMORY and leaves the scene as found. A HIP failure after that leaves no scene, as with the other writers. */
+typedef struct HiprVertexEdit {
+    uint32_t first_vertex;                 /* index into the RESIDENT vertex pools (an instance's vertex_offset + the mesh's own index) */
+    uint32_t vertex_count;                 /* > 0, first_vertex + vertex_count <= the resident vertex count */
+    const HiprVertexGeometry* geometry;    /* vertex_count entries, or NULL: positions and normals stay */
+    const float*    texcoords;             /* float2 each, or NULL */
+    const uint32_t* tints;                 /* uchar4 each, or NULL */
+    const float*    emissions;             /* float3 each, or NULL */
+} HiprVertexEdit;
+typedef struct HiprVertexUpdateResult {
+    HiprRefitResult refit;                 /* as hipr_refit_scene_transforms fills it; areas and grid as resident afterwards also when no position changed */
+    uint32_t moved_triangles;              /* triangles with a corner in an edited geometry range */
+    uint32_t candidate_triangles, changed_triangles, all_triangles_opaque;   /* as HiprTexelUpdateResult */
+} HiprVertexUpdateResult;
+int hipr_update_scene_vertices(HiprContext* context, const HiprVertexEdit* edits, uint32_t edit_count, HiprVertexUpdateResult* out);
 int hipr_set_scene_state(HiprContext* context, const HiprSceneState* state);
 
 /* Entry points, numbered like OR/Types.h:33-44. set_backend() of the host renderer maps Backend values onto them
@@ -727,6 +767,7 @@ int hipr_group_update_scene_lighting(HiprGroup* group, const HiprLight* lights, 
                                      float* out_per_pixel_PDF, uint64_t pdf_capacity, HiprLightSample* out_samples, uint32_t sample_capacity,
                                      HiprLightingResult* out);   /* every member checks before any member writes; member 0's arrays are handed out; their results must agree */
 int hipr_group_update_scene_texels(HiprGroup* group, const HiprTexelEdit* edits, uint32_t edit_count, HiprTexelUpdateResult* out);   /* every member checks before any member writes */
+int hipr_group_update_scene_vertices(HiprGroup* group, const HiprVertexEdit* edits, uint32_t edit_count, HiprVertexUpdateResult* out);   /* every member checks before any member writes */
 int hipr_group_update_scene_materials(HiprGroup* group, const HiprMaterialUpdate* materials, uint32_t material_count,
                                       const HiprInstanceMaterial* assignments, uint32_t assignment_count);   /* every member checks before any member writes */
 int hipr_group_set_scene_state(HiprGroup* group, const HiprSceneState* state);
@@ -917,6 +958,10 @@ int hipr_debug_lighting_times(HiprContext* context, double* out4_ms);
  * rectangle writes, the coverage pass (the flags of the affected materials' triangles decided again) and the leaf pass (each between events on the stream: the call
  * does not synchronise for them) (tools/texel_update_probe.py). */
 int hipr_debug_texel_update_times(HiprContext* context, double* out4_ms);
+/* ... and for the context's last successful hipr_update_scene_vertices that did any work: the segments and rows packed and their staging copy queued (the host's
+ * clock), the pool writes with the marks, the moved triangles with the refit passes and the records, the flag pass with the leaf pass (each between events on the
+ * stream: the call does not synchronise for them) (tools/vertex_update_probe.py). */
+int hipr_debug_vertex_update_times(HiprContext* context, double* out4_ms);
 
 #ifdef __cplusplus
 }
