@@ -304,10 +304,71 @@ def vertex_edits(edits):
         array[k] = HiprVertexEdit(int(edit["first"]), int(edit.get("count", count or 0)), *pointers)
     return array, keep or [None]
 
+
+class HiprRigDesc(C.Structure):
+    _fields_ = [("first_vertex", c_u32), ("vertex_count", c_u32), ("joint_count", c_u32), ("target_count", c_u32), ("rest_positions", C.c_void_p), ("rest_normals", C.c_void_p),
+                ("joints", C.c_void_p), ("weights", C.c_void_p), ("target_positions", C.c_void_p), ("target_normals", C.c_void_p)]
+
+
+class HiprRigPose(C.Structure):
+    _fields_ = [("rig", c_u32), ("reserved", c_u32), ("joint_matrices", C.c_void_p), ("target_weights", C.c_void_p)]
+
+
+assert C.sizeof(HiprRigDesc) == 64 and C.sizeof(HiprRigPose) == 24
+
+RIG_ARRAYS = ("rest_positions", "rest_normals", "joints", "weights", "target_positions", "target_normals")
+
+
+def rig_descs(rigs):
+    """Dicts of `first` (a vertex of the RESIDENT pools; MESH-relative for Scene.set_rigs), `rest_positions` (n, 3) float32 and any of `rest_normals` (n, 3), `joints`
+    (n, 4) uint16 with `weights` (n, 4) float32, `target_positions` (t, n, 3) float32 and `target_normals` (t, n, 3) as the HiprRigDesc array of hipr_set_scene_rigs
+    (one spare element: never a null array). `joint_count` defaults to the largest index + 1, `target_count` to the targets given, `count` to the rest positions'
+    length; each can be given for a call that is to be refused, and an array given as the string "null" stays a null pointer whatever the counts say. Returns
+    (array, keep-alive)."""
+    import numpy as np
+    rigs = list(rigs)
+    array, keep = (HiprRigDesc * max(len(rigs), 1))(), []
+    kinds = dict(rest_positions=np.float32, rest_normals=np.float32, joints=np.uint16, weights=np.float32, target_positions=np.float32, target_normals=np.float32)
+    for k, rig in enumerate(rigs):
+        held = {}
+        for name in RIG_ARRAYS:
+            values = rig.get(name)
+            if values is None or isinstance(values, str):
+                held[name] = None
+                continue
+            held[name] = np.ascontiguousarray(values, kinds[name])
+            keep.append(held[name])
+        positions, joints, targets = held["rest_positions"], held["joints"], held["target_positions"]
+        count = int(rig.get("count", 0 if positions is None else positions.size // 3))
+        joint_count = int(rig.get("joint_count", 0 if joints is None or not joints.size else int(joints.max()) + 1))
+        target_count = int(rig.get("target_count", 0 if targets is None or not count else targets.size // (3 * count)))
+        array[k] = HiprRigDesc(int(rig["first"]), count, joint_count, target_count, *[None if held[name] is None else held[name].ctypes.data for name in RIG_ARRAYS])
+    return array, keep or [None]
+
+
+def rig_poses(poses):
+    """Dicts of `rig` (an index into the bound set) and any of `matrices` (joint_count, 3, 4) float32 and `weights` (target_count,) float32 as the HiprRigPose array
+    of hipr_pose_scene_rigs (one spare element). Returns (array, keep-alive)."""
+    import numpy as np
+    poses = list(poses)
+    array, keep = (HiprRigPose * max(len(poses), 1))(), []
+    for k, pose in enumerate(poses):
+        pointers = []
+        for name in ("matrices", "weights"):
+            values = pose.get(name)
+            if values is None:
+                pointers.append(None)
+                continue
+            values = np.ascontiguousarray(values, np.float32)
+            keep.append(values)
+            pointers.append(values.ctypes.data)
+        array[k] = HiprRigPose(int(pose["rig"]), 0, *pointers)
+    return array, keep or [None]
+
 # Every symbol include/hiprenderer_c.h declares; tests check the library exports all of them.
 C_ABI_SYMBOLS = (
     "hipr_create", "hipr_destroy", "hipr_last_error", "hipr_device_count", "hipr_set_stream",
-    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_build_bvh2", "hipr_group_build_bvh2", "hipr_debug_build_times", "hipr_build_wide8", "hipr_group_build_wide8", "hipr_debug_collapse_times", "hipr_build_wide4", "hipr_group_build_wide4", "hipr_debug_collapse4_times", "hipr_rebuild_scene_trees", "hipr_group_rebuild_scene_trees", "hipr_edit_scene_instances", "hipr_group_edit_scene_instances", "hipr_append_scene_pools", "hipr_group_append_scene_pools", "hipr_update_scene_lighting", "hipr_group_update_scene_lighting", "hipr_debug_lighting_times", "hipr_update_scene_texels", "hipr_group_update_scene_texels", "hipr_debug_texel_update_times", "hipr_update_scene_vertices", "hipr_group_update_scene_vertices", "hipr_debug_vertex_update_times", "hipr_debug_scene_buffer_bytes", "hipr_debug_append_times", "hipr_debug_rebuild_times", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
+    "hipr_upload_tables", "hipr_upload_scene", "hipr_validate_scene", "hipr_update_scene_geometry", "hipr_group_update_scene_geometry", "hipr_refit_scene_transforms", "hipr_group_refit_scene_transforms", "hipr_update_scene_materials", "hipr_group_update_scene_materials", "hipr_build_bvh2", "hipr_group_build_bvh2", "hipr_debug_build_times", "hipr_build_wide8", "hipr_group_build_wide8", "hipr_debug_collapse_times", "hipr_build_wide4", "hipr_group_build_wide4", "hipr_debug_collapse4_times", "hipr_rebuild_scene_trees", "hipr_group_rebuild_scene_trees", "hipr_edit_scene_instances", "hipr_group_edit_scene_instances", "hipr_append_scene_pools", "hipr_group_append_scene_pools", "hipr_update_scene_lighting", "hipr_group_update_scene_lighting", "hipr_debug_lighting_times", "hipr_update_scene_texels", "hipr_group_update_scene_texels", "hipr_debug_texel_update_times", "hipr_update_scene_vertices", "hipr_group_update_scene_vertices", "hipr_debug_vertex_update_times", "hipr_set_scene_rigs", "hipr_group_set_scene_rigs", "hipr_pose_scene_rigs", "hipr_group_pose_scene_rigs", "hipr_debug_vertex_pose_times", "hipr_debug_set_pose_lds_joints", "hipr_debug_scene_buffer_bytes", "hipr_debug_append_times", "hipr_debug_rebuild_times", "hipr_debug_read_scene_buffer", "hipr_set_scene_state", "hipr_set_entry_point", "hipr_use_scratch_accumulation",
     "hipr_set_frame", "hipr_owned_pixel_count",
     "hipr_render_pass", "hipr_set_samples_per_pass", "hipr_trace_pass", "hipr_accumulate_samples", "hipr_read_accumulation", "hipr_scatter_tiles", "hipr_synchronize", "hipr_get_counters",
     "hipr_device_malloc", "hipr_device_free", "hipr_device_memset", "hipr_copy_to_host", "hipr_present_flipped",
@@ -381,6 +442,12 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.hipr_update_scene_vertices.argtypes = [vp, C.POINTER(HiprVertexEdit), c_u32, C.POINTER(HiprVertexUpdateResult)]
     lib.hipr_group_update_scene_vertices.argtypes = [vp, C.POINTER(HiprVertexEdit), c_u32, C.POINTER(HiprVertexUpdateResult)]
     lib.hipr_debug_vertex_update_times.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.hipr_set_scene_rigs.argtypes = [vp, C.POINTER(HiprRigDesc), c_u32]
+    lib.hipr_group_set_scene_rigs.argtypes = [vp, C.POINTER(HiprRigDesc), c_u32]
+    lib.hipr_pose_scene_rigs.argtypes = [vp, C.POINTER(HiprRigPose), c_u32, C.POINTER(HiprVertexUpdateResult)]
+    lib.hipr_group_pose_scene_rigs.argtypes = [vp, C.POINTER(HiprRigPose), c_u32, C.POINTER(HiprVertexUpdateResult)]
+    lib.hipr_debug_vertex_pose_times.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.hipr_debug_set_pose_lds_joints.argtypes = [vp, c_u32]
     lib.hipr_debug_scene_buffer_bytes.argtypes = [vp, C.c_int, C.POINTER(c_u64)]
     lib.hipr_debug_append_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.hipr_debug_rebuild_times.argtypes = [vp, C.POINTER(C.c_double)]

@@ -102,6 +102,7 @@ constexpr int HOST_COUNT_WORDS = 8 + COUNT_LINES * COUNT_PAIR_STRIDE;   // pinne
 struct LightingScratch;      // below, with the other scratches
 struct TexelScratch;
 struct VertexScratch;
+struct PoseScratch;
 
 struct Preflight {
     uint32_t wide_stack_need = 0;       // worst-case stack need of the 4-wide tree: derived, not taken from the caller
@@ -210,6 +211,16 @@ struct ResidentScene {
     // The device work of hipr_update_scene_vertices, which has checked every range against the host copies (hipr_internal_check_vertex_update): the ranges written
     // into the vertex pools and everything an upload derives from vertex data brought along (vertex_update.h).
     int update_vertices(const HiprVertexEdit* edits, uint32_t edit_count, VertexScratch& scratch, hipStream_t stream, HiprVertexUpdateResult* out);
+    // The rigs hipr_set_scene_rigs bound (vertex_pose.h): a record per rig and the rest data of all of them on the device, and the host's book the poses are checked
+    // against. upload() drops them; every other writer keeps them (none moves a pool vertex).
+    DeviceBuffer rig_records, rig_data;
+    struct Rig { uint32_t first_vertex, vertex_count, joint_count, target_count, flags; };      // vertex_pose.h RigBook, which this unit's includes do not reach: scene.hip asserts the layout
+    std::vector<Rig> rigs;
+    uint32_t pose_lds_joints = 32;      // POSE_LDS_JOINTS (scene.hip asserts it); hipr_debug_set_pose_lds_joints sets it
+    // The device work of hipr_set_scene_rigs, which has checked the list (check_rig_descs): the new set allocated and copied, then the old one let go.
+    int set_rigs(const HiprRigDesc* descs, uint32_t count, hipStream_t stream);
+    // The device work of hipr_pose_scene_rigs, which has checked the poses (hipr_internal_check_rig_poses): the pose kernel, then queue_refit_of_marked and finish_vertex_writes.
+    int pose_rigs(const HiprRigPose* poses, uint32_t pose_count, PoseScratch& scratch, VertexScratch& vertex_scratch, hipStream_t stream, HiprVertexUpdateResult* out);
     double append_ms[3] = {0.0, 0.0, 0.0};      // of the last append_pools: the allocations (host clock), the device-to-device copies of the resident parts, the tails and the mirror segments (events)
     Event append_events[3];             // made by the first append_pools
 
@@ -222,6 +233,12 @@ private:
     int upload_wide8(const HiprSceneDesc* s, uint32_t height, bool cull_backfaces, hipStream_t stream);
     int prepare_refit(const HiprSceneDesc* s, bool new_topology, hipStream_t stream);
     template <bool WRITE> void queue_refit_tree(const float* grid_min, const float* grid_cell, hipStream_t stream) const;
+    // What follows writes into the geometry pool whose vertices are marked in `marks` (a byte per pool vertex), shared by update_vertices and pose_rigs: the moved
+    // triangles (words[VERTEX_WORD_MOVED]) with the bounds, the grid and the refit of the tree, queued on the stream after ONE synchronise for the bounds.
+    int queue_refit_of_marked(const uint8_t* marks, uint32_t* words, float* grid_min, float* grid_cell, hipStream_t stream);
+    // ... and the end of both calls once everything is queued: the read-backs, the state refit_transforms leaves, `out` filled. all-opaque and the two counts of the
+    // flag pass are the caller's (decides_flags false: none ran).
+    int finish_vertex_writes(bool moves, bool decides_flags, const uint32_t* device_words, const float* grid_min, const float* grid_cell, hipStream_t stream, HiprVertexUpdateResult* out);
 };
 
 // What tunes a context: read from the environment once, when the context is made (knobs_from_environment), and written by the setters of the C-ABI that are named here.
@@ -327,6 +344,14 @@ struct VertexScratch : Scratch<VertexBuffers> {
     Event events[4];                    // around the pool writes, the refit passes with the records, the flag pass with the leaf pass; made by the first update
 };
 
+// The device scratch of hipr_pose_scene_rigs (vertex_pose.h): the block table, the calls, the matrices and the target weights packed. The marks and the passes'
+// words are the vertex update's (VertexScratch): the continuation is shared.
+struct PoseBuffers { DeviceBuffer staging; };
+struct PoseScratch : Scratch<PoseBuffers> {
+    double staging_ms = 0.0, pose_ms = 0.0, refit_ms = 0.0;      // of the last pose
+    Event events[3];                    // around the pose kernel, the refit passes with the records; made by the first pose
+};
+
 // The context; HiprContext, the C-ABI's opaque type, is this and nothing else.
 struct Context {
     int device = 0;
@@ -423,6 +448,7 @@ struct Context {
     LightingScratch lighting;           // hipr_update_scene_lighting's environment build
     TexelScratch texel_update;          // hipr_update_scene_texels
     VertexScratch vertex_update;        // hipr_update_scene_vertices
+    PoseScratch vertex_pose;            // hipr_pose_scene_rigs
 
     hipEvent_t next_event() {
         if (events_used == event_pool.size()) {

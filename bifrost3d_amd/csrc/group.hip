@@ -42,6 +42,8 @@ extern "C" int hipr_internal_check_material_update(HiprContext* context, const H
 extern "C" int hipr_internal_check_pool_growth(HiprContext* context, const HiprPoolGrowth* growth);   // scene.hip: every refusal of hipr_append_scene_pools short of a failed allocation
 extern "C" int hipr_internal_check_texel_update(HiprContext* context, const HiprTexelEdit* edits, uint32_t edit_count, const HiprTexelUpdateResult* out);   // scene.hip: every refusal of hipr_update_scene_texels short of a failed allocation
 extern "C" int hipr_internal_check_vertex_update(HiprContext* context, const HiprVertexEdit* edits, uint32_t edit_count, const HiprVertexUpdateResult* out);   // scene.hip: every refusal of hipr_update_scene_vertices short of a failed allocation
+extern "C" int hipr_internal_check_scene_rigs(HiprContext* context, const HiprRigDesc* rigs, uint32_t count);   // scene.hip: every refusal of hipr_set_scene_rigs short of a failed allocation
+extern "C" int hipr_internal_check_rig_poses(HiprContext* context, const HiprRigPose* poses, uint32_t pose_count, const HiprVertexUpdateResult* out);   // scene.hip: every refusal of hipr_pose_scene_rigs short of a failed allocation
 extern "C" int hipr_internal_check_lighting_update(HiprContext* context, const HiprLight* lights, uint32_t light_count, int environment_action, const HiprEnvironmentBuild* build,
                                                    const float* out_per_pixel_PDF, uint64_t pdf_capacity, const HiprLightSample* out_samples, uint32_t sample_capacity,
                                                    const HiprLightingResult* out);   // scene.hip: every refusal of hipr_update_scene_lighting short of a failed allocation
@@ -472,6 +474,34 @@ int hipr_group_update_scene_vertices(HiprGroup* g, const HiprVertexEdit* edits, 
         if (std::memcmp(&r, &results[0], sizeof(r))) {
             hipr_internal_set_last_error("hipr_group_update_scene_vertices: the members' scenes disagree");
             fprintf(stderr, "hiprenderer: hipr_group_update_scene_vertices: the members' scenes disagree\n");
+            return HIPR_ERROR_HIP;
+        }
+    *out = results[0];
+    return HIPR_OK;
+}
+
+// hipr_set_scene_rigs on every member: every member checks before any member writes.
+int hipr_group_set_scene_rigs(HiprGroup* g, const HiprRigDesc* rigs, uint32_t count) {
+    if (!g || g->members.empty()) return HIPR_ERROR_INVALID_ARGUMENT;
+    for (Member& m : g->members)
+        if (int s = hipr_internal_check_scene_rigs(m.context, rigs, count)) return s;
+    return for_each_member(g, [&](Member& m, uint32_t) { return hipr_set_scene_rigs(m.context, rigs, count); });
+}
+
+// hipr_pose_scene_rigs on every member: every member checks before any member writes; the same kernels over the same rigs make the same scene, so member 0's
+// result is the one handed out.
+int hipr_group_pose_scene_rigs(HiprGroup* g, const HiprRigPose* poses, uint32_t pose_count, HiprVertexUpdateResult* out) {
+    if (!g || !out || g->members.empty()) return HIPR_ERROR_INVALID_ARGUMENT;
+    for (Member& m : g->members)
+        if (int s = hipr_internal_check_rig_poses(m.context, poses, pose_count, out)) return s;
+    std::vector<HiprVertexUpdateResult> results(g->members.size());
+    for (HiprVertexUpdateResult& r : results) std::memset(&r, 0, sizeof(r));      // the padding too: the results are compared as bytes
+    const int status = for_each_member(g, [&](Member& m, uint32_t index) { return hipr_pose_scene_rigs(m.context, poses, pose_count, &results[index]); });
+    if (status) return status;
+    for (const HiprVertexUpdateResult& r : results)
+        if (std::memcmp(&r, &results[0], sizeof(r))) {
+            hipr_internal_set_last_error("hipr_group_pose_scene_rigs: the members' scenes disagree");
+            fprintf(stderr, "hiprenderer: hipr_group_pose_scene_rigs: the members' scenes disagree\n");
             return HIPR_ERROR_HIP;
         }
     *out = results[0];

@@ -19,6 +19,7 @@
 #include "environment_build.h"
 #include "texel_update.h"
 #include "vertex_update.h"
+#include "vertex_pose.h"
 
 #include <hip/hip_runtime.h>
 
@@ -523,6 +524,9 @@ int ResidentScene::prepare_refit(const HiprSceneDesc* s, bool new_topology, hipS
 int ResidentScene::upload(const HiprSceneDesc* s, const Preflight& checked, int requested_variant, bool cull_backfaces, hipStream_t stream) {
     begin_write();
     wide4_awaits_geometry = false;
+    rigs.clear();      // hipr_set_scene_rigs' ranges are coordinates of the pools that go now
+    rig_records.release();
+    rig_data.release();
     if (int r = upload_pools(s, true, stream)) return r;
     const HiprEnvironment* env = s->environment;
     args.nodes = nodes.as<float4>();
@@ -1048,21 +1052,9 @@ int ResidentScene::update_vertices(const HiprVertexEdit* edits, uint32_t edit_co
     HIP_TRY(hipGetLastError());
     if (timed) HIP_TRY(hipEventRecord(x.events[1], st));
     float grid_min[3] = {wide8.grid_min[0], wide8.grid_min[1], wide8.grid_min[2]}, grid_cell[3] = {wide8.grid_cell[0], wide8.grid_cell[1], wide8.grid_cell[2]};
-    if (moves) {
-        // 2. the moved triangles and the scene's bounds, then the tree (wide8_refit.h)
-        HIP_TRY(hipMemsetAsync(refit_scratch.ptr, 0, REFIT_SCRATCH_BYTES, st));
-        const uint32_t blocks = (args.triangle_count + REFIT_BLOCK - 1) / REFIT_BLOCK;
-        hipLaunchKernelGGL(k_refit_marked_triangles, dim3(blocks), dim3(REFIT_BLOCK), 0, st, triangles.as<HiprTriangle>(), args.triangle_count, instances.as<HiprInstance>(), x.marks_geometry.as<uint8_t>(),
-                           indices.as<uint32_t>(), geometry.as<HiprVertexGeometry>(), refit_partial.as<RefitBound>(), x.words.as<uint32_t>());
-        hipLaunchKernelGGL(k_refit_bounds_final, dim3(1), dim3(REFIT_BLOCK), 0, st, refit_partial.as<RefitBound>(), blocks, refit_scratch.as<RefitBound>());
-        HIP_TRY(hipGetLastError());
-        RefitBound bounds[6];
-        HIP_TRY(hipMemcpyAsync(bounds, refit_scratch.ptr, sizeof(bounds), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));      // `packed` is read by now as well
-        const float lo[3] = {bounds[0].v, bounds[1].v, bounds[2].v}, hi[3] = {bounds[3].v, bounds[4].v, bounds[5].v};
-        refit_grid(lo, hi, grid_min, grid_cell);
-        queue_refit_tree<true>(grid_min, grid_cell, st);
-    }
+    // 2. the moved triangles and the scene's bounds, then the tree (wide8_refit.h); `packed` is read once that has synchronised
+    if (moves)
+        if (int status = queue_refit_of_marked(x.marks_geometry.as<uint8_t>(), x.words.as<uint32_t>(), grid_min, grid_cell, st)) return status;
     if (records) queue_triangle_records(st);
     HIP_TRY(hipGetLastError());
     if (timed) HIP_TRY(hipEventRecord(x.events[2], st));
@@ -1079,12 +1071,8 @@ int ResidentScene::update_vertices(const HiprVertexEdit* edits, uint32_t edit_co
         HIP_TRY(hipGetLastError());
     }
     if (timed) HIP_TRY(hipEventRecord(x.events[3], st));
-    // 4. the read-backs: the refit's flag and area, the four words
-    struct { uint32_t flag; uint32_t pad[3]; double area; } tail = {};
-    uint32_t words[4] = {all_triangles_opaque ? 1u : 0u, 0u, 0u, 0u};
-    if (moves) HIP_TRY(hipMemcpyAsync(&tail, refit_scratch.as<char>() + REFIT_SCRATCH_FLAG, sizeof(tail), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(words, x.words.ptr, sizeof(words), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    // 4. the read-backs, the books and the answer
+    if (int status = finish_vertex_writes(moves, decides_flags, x.words.as<uint32_t>(), grid_min, grid_cell, st, out)) return status;
     float write_ms = 0.0f, refit_ms = 0.0f, flag_ms = 0.0f;
     if (timed) {
         HIP_TRY(hipEventElapsedTime(&write_ms, x.events[0], x.events[1]));
@@ -1092,6 +1080,36 @@ int ResidentScene::update_vertices(const HiprVertexEdit* edits, uint32_t edit_co
         HIP_TRY(hipEventElapsedTime(&flag_ms, x.events[2], x.events[3]));
     }
     x.staging_ms = ms(t0, t1); x.write_ms = write_ms; x.refit_ms = refit_ms; x.flag_ms = flag_ms;
+    return HIPR_OK;
+}
+
+// What update_vertices and pose_rigs share after their writes into the geometry pool (vertex_update.h pass 2, then the refit of the tree): the triangles that read a
+// marked vertex get their corners again and are counted in words[VERTEX_WORD_MOVED], every triangle feeds the bounds, ONE synchronise brings the bounds to the
+// host for the grid, and the tree's refit is queued.
+int ResidentScene::queue_refit_of_marked(const uint8_t* marks, uint32_t* words, float* grid_min, float* grid_cell, hipStream_t st) {
+    HIP_TRY(hipMemsetAsync(refit_scratch.ptr, 0, REFIT_SCRATCH_BYTES, st));
+    const uint32_t blocks = (args.triangle_count + REFIT_BLOCK - 1) / REFIT_BLOCK;
+    hipLaunchKernelGGL(k_refit_marked_triangles, dim3(blocks), dim3(REFIT_BLOCK), 0, st, triangles.as<HiprTriangle>(), args.triangle_count, instances.as<HiprInstance>(), marks,
+                       indices.as<uint32_t>(), geometry.as<HiprVertexGeometry>(), refit_partial.as<RefitBound>(), words);
+    hipLaunchKernelGGL(k_refit_bounds_final, dim3(1), dim3(REFIT_BLOCK), 0, st, refit_partial.as<RefitBound>(), blocks, refit_scratch.as<RefitBound>());
+    HIP_TRY(hipGetLastError());
+    RefitBound bounds[6];
+    HIP_TRY(hipMemcpyAsync(bounds, refit_scratch.ptr, sizeof(bounds), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));      // the caller's staging copy is read by now as well
+    const float lo[3] = {bounds[0].v, bounds[1].v, bounds[2].v}, hi[3] = {bounds[3].v, bounds[4].v, bounds[5].v};
+    refit_grid(lo, hi, grid_min, grid_cell);
+    queue_refit_tree<true>(grid_min, grid_cell, st);
+    return HIPR_OK;
+}
+
+// The end of both calls, everything queued: the refit's flag and area and the passes' four words read back, then the books, the state refit_transforms leaves
+// (tree_stale; awaits_rebuild when a pair parted) and the answer. decides_flags: the flag pass ran, its words count.
+int ResidentScene::finish_vertex_writes(bool moves, bool decides_flags, const uint32_t* device_words, const float* grid_min, const float* grid_cell, hipStream_t st, HiprVertexUpdateResult* out) {
+    struct { uint32_t flag; uint32_t pad[3]; double area; } tail = {};
+    uint32_t words[4] = {all_triangles_opaque ? 1u : 0u, 0u, 0u, 0u};
+    if (moves) HIP_TRY(hipMemcpyAsync(&tail, refit_scratch.as<char>() + REFIT_SCRATCH_FLAG, sizeof(tail), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(words, device_words, sizeof(words), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     if (decides_flags) {
         all_triangles_opaque = words[VERTEX_WORD_OPAQUE] != 0;
         derive_switches_from_pools();
@@ -1113,6 +1131,86 @@ int ResidentScene::update_vertices(const HiprVertexEdit* edits, uint32_t edit_co
     out->all_triangles_opaque = all_triangles_opaque ? 1u : 0u;
     ready = !needs_rebuild;
     awaits_rebuild = !ready;
+    return HIPR_OK;
+}
+
+static_assert(POSE_LDS_JOINTS == 32u, "ResidentScene::pose_lds_joints starts at the budget that ships (context.h)");
+static_assert(sizeof(ResidentScene::Rig) == sizeof(RigBook) && offsetof(ResidentScene::Rig, first_vertex) == offsetof(RigBook, first_vertex) &&
+              offsetof(ResidentScene::Rig, vertex_count) == offsetof(RigBook, vertex_count) && offsetof(ResidentScene::Rig, joint_count) == offsetof(RigBook, joint_count) &&
+              offsetof(ResidentScene::Rig, target_count) == offsetof(RigBook, target_count) && offsetof(ResidentScene::Rig, flags) == offsetof(RigBook, flags),
+              "ResidentScene::Rig is RigBook member for member: check_rig_poses and plan_rig_poses read either");
+
+// The device work of hipr_set_scene_rigs (vertex_pose.h): the rigs packed in the resident layout, the new buffers allocated and filled, and only then the old
+// ones let go and the book replaced -- a failed allocation leaves the old set bound. The scene's state is not touched: no pool, triangle or tree changes.
+int ResidentScene::set_rigs(const HiprRigDesc* descs, uint32_t count, hipStream_t st) {
+    std::vector<uint32_t> words;
+    std::vector<PoseRig> records(count);
+    std::vector<Rig> book(count);
+    for (uint32_t k = 0; k < count; ++k) {
+        RigBook b;
+        pack_rig(descs[k], words, records[k], b);
+        book[k] = {b.first_vertex, b.vertex_count, b.joint_count, b.target_count, b.flags};
+    }
+    DeviceBuffer new_records, new_data;
+    if (count) {
+        int r = new_records.resize(records.size() * sizeof(PoseRig));
+        r |= new_data.resize(std::max<size_t>(words.size(), 4) * sizeof(uint32_t));
+        if (r) {
+            (void)hipGetLastError();
+            return HIPR_ERROR_OUT_OF_MEMORY;
+        }
+        HIP_TRY(hipMemcpyAsync(new_records.ptr, records.data(), records.size() * sizeof(PoseRig), hipMemcpyHostToDevice, st));
+        if (!words.empty()) HIP_TRY(hipMemcpyAsync(new_data.ptr, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));      // `records` and `words` are read
+    }
+    rig_records = std::move(new_records);      // the old buffers go with the temporaries
+    rig_data = std::move(new_data);
+    rigs = std::move(book);
+    return HIPR_OK;
+}
+
+// The device work of hipr_pose_scene_rigs (vertex_pose.h). The scratch is allocated BEFORE the scene is touched. Then, as the other writers: not ready, ONE staging
+// copy (the block table, the calls, all matrices and target weights), ONE launch of k_pose_vertices, and what update_vertices runs after an edit of geometry:
+// queue_refit_of_marked, the records, finish_vertex_writes. A pose carries no texture coordinates: the flag and leaf passes are not queued.
+int ResidentScene::pose_rigs(const HiprRigPose* poses, uint32_t pose_count, PoseScratch& x, VertexScratch& v, hipStream_t st, HiprVertexUpdateResult* out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    PosePlan plan;
+    plan_rig_poses(poses, pose_count, rigs.data(), plan);
+    int r = x.staging.resize(plan.staging.size());
+    r |= v.words.resize(VERTEX_SCRATCH_WORDS * sizeof(uint32_t));
+    r |= v.marks_geometry.resize(std::max<size_t>(uploaded_vertex_count, 1));
+    if (r) {
+        (void)hipGetLastError();      // the failed allocation's error is answered here: it must not meet the next call's check
+        return HIPR_ERROR_OUT_OF_MEMORY;
+    }
+    for (Event& e : x.events)
+        if (!e) e = make_event(hipEventDefault);
+    const bool timed = x.events[0] && x.events[1] && x.events[2];
+    begin_write();
+    HIP_TRY(hipMemcpyAsync(x.staging.ptr, plan.staging.data(), plan.staging.size(), hipMemcpyHostToDevice, st));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (timed) HIP_TRY(hipEventRecord(x.events[0], st));
+    HIP_TRY(hipMemsetAsync(v.marks_geometry.ptr, 0, uploaded_vertex_count, st));
+    HIP_TRY(hipMemsetAsync(v.words.ptr, 0, VERTEX_SCRATCH_WORDS * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(v.words.ptr), 1, 1, st));
+    const uint8_t* staging = x.staging.as<uint8_t>();
+    hipLaunchKernelGGL(k_pose_vertices, dim3(plan.block_count), dim3(POSE_BLOCK), 0, st, reinterpret_cast<const PoseBlock*>(staging), reinterpret_cast<const PoseCall*>(staging + plan.calls_at),
+                       reinterpret_cast<const float*>(staging + plan.floats_at), rig_records.as<PoseRig>(), rig_data.as<uint32_t>(), std::min(pose_lds_joints, POSE_LDS_CAPACITY),
+                       geometry.as<HiprVertexGeometry>(), v.marks_geometry.as<uint8_t>());
+    HIP_TRY(hipGetLastError());
+    if (timed) HIP_TRY(hipEventRecord(x.events[1], st));
+    float grid_min[3] = {wide8.grid_min[0], wide8.grid_min[1], wide8.grid_min[2]}, grid_cell[3] = {wide8.grid_cell[0], wide8.grid_cell[1], wide8.grid_cell[2]};
+    if (int status = queue_refit_of_marked(v.marks_geometry.as<uint8_t>(), v.words.as<uint32_t>(), grid_min, grid_cell, st)) return status;      // plan.staging is read by now
+    queue_triangle_records(st);
+    HIP_TRY(hipGetLastError());
+    if (timed) HIP_TRY(hipEventRecord(x.events[2], st));
+    if (int status = finish_vertex_writes(true, false, v.words.as<uint32_t>(), grid_min, grid_cell, st, out)) return status;
+    float pose_ms = 0.0f, refit_ms = 0.0f;
+    if (timed) {
+        HIP_TRY(hipEventElapsedTime(&pose_ms, x.events[0], x.events[1]));
+        HIP_TRY(hipEventElapsedTime(&refit_ms, x.events[1], x.events[2]));
+    }
+    x.staging_ms = ms(t0, t1); x.pose_ms = pose_ms; x.refit_ms = refit_ms;
     return HIPR_OK;
 }
 
@@ -2067,6 +2165,63 @@ int hipr_debug_vertex_update_times(HiprContext* c, double* out4_ms) {
     if (!c || !out4_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_vertex_update_times: null argument");
     const VertexScratch& x = c->vertex_update;
     out4_ms[0] = x.staging_ms; out4_ms[1] = x.write_ms; out4_ms[2] = x.refit_ms; out4_ms[3] = x.flag_ms;
+    return HIPR_OK;
+}
+
+// Not part of the public header: every refusal of hipr_set_scene_rigs that is not a failed allocation, and nothing else -- no HIP call. The group asks every member
+// before any member writes.
+int hipr_internal_check_scene_rigs(HiprContext* c, const HiprRigDesc* rigs, uint32_t count) {
+    const char* who = "hipr_set_scene_rigs";
+    if (int st = check_context(c)) return st;
+    const ResidentScene& r = c->scene;
+    if (!r.ready) return fail(HIPR_ERROR_NOT_READY, "%s: no scene uploaded, one a failed call left behind, or one that awaits hipr_rebuild_scene_trees", who);
+    if (const char* why = check_rig_descs(rigs, count, r.uploaded_vertex_count)) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: %s", who, why);
+    return HIPR_OK;
+}
+
+// The resident rig set replaced (vertex_pose.h): checked on the host, then ResidentScene::set_rigs.
+int hipr_set_scene_rigs(HiprContext* c, const HiprRigDesc* rigs, uint32_t count) {
+    if (int st = hipr_internal_check_scene_rigs(c, rigs, count)) return st;
+    if (int finish_status = finish_all(c)) return finish_status;
+    return c->scene.set_rigs(rigs, count, c->stream);
+}
+
+// ... and every refusal of hipr_pose_scene_rigs that is not a failed allocation.
+int hipr_internal_check_rig_poses(HiprContext* c, const HiprRigPose* poses, uint32_t pose_count, const HiprVertexUpdateResult* out) {
+    const char* who = "hipr_pose_scene_rigs";
+    if (int st = check_context(c)) return st;
+    const ResidentScene& r = c->scene;
+    if (!r.ready) return fail(HIPR_ERROR_NOT_READY, "%s: no scene uploaded, one a failed call left behind, or one that awaits hipr_rebuild_scene_trees", who);
+    if (!out) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: null result", who);
+    if (const char* why = check_rig_poses(poses, pose_count, r.rigs.data(), r.rigs.size())) return fail(HIPR_ERROR_INVALID_ARGUMENT, "%s: %s", who, why);
+    // what hipr_refit_scene_transforms refuses, as hipr_update_scene_vertices
+    if (r.wide8.slot_count == 0 || !c->use_wide8() || r.args.trace_item_count != 0 || r.args.triangle_count > 0x55555555u)
+        return fail(HIPR_ERROR_UNSUPPORTED, "%s: the uploaded scene is not traced through the 8-wide tree; pose on the host and upload the scene instead", who);
+    return HIPR_OK;
+}
+
+// Bound rigs posed on the device (vertex_pose.h): the poses checked on the host, then ResidentScene::pose_rigs.
+int hipr_pose_scene_rigs(HiprContext* c, const HiprRigPose* poses, uint32_t pose_count, HiprVertexUpdateResult* out) {
+    if (int st = hipr_internal_check_rig_poses(c, poses, pose_count, out)) return st;
+    if (!pose_count) return hipr_update_scene_vertices(c, nullptr, 0, out);      // what is resident
+    if (int finish_status = finish_all(c)) return finish_status;      // no pending pass may go on over vertices and triangles that are about to change
+    c->break_chain(c->stream);
+    ScratchGuard<PoseScratch> guard(c->vertex_pose);
+    ScratchGuard<VertexScratch> marks_guard(c->vertex_update);
+    return c->scene.pose_rigs(poses, pose_count, c->vertex_pose, c->vertex_update, c->stream, out);
+}
+
+int hipr_debug_vertex_pose_times(HiprContext* c, double* out4_ms) {
+    if (!c || !out4_ms) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_vertex_pose_times: null argument");
+    const PoseScratch& x = c->vertex_pose;
+    out4_ms[0] = x.staging_ms; out4_ms[1] = x.pose_ms; out4_ms[2] = x.refit_ms; out4_ms[3] = 0.0;
+    return HIPR_OK;
+}
+
+int hipr_debug_set_pose_lds_joints(HiprContext* c, uint32_t joints) {
+    if (int st = check_context(c)) return st;
+    if (joints > POSE_LDS_CAPACITY) return fail(HIPR_ERROR_INVALID_ARGUMENT, "hipr_debug_set_pose_lds_joints: the kernel's LDS holds %u joints", POSE_LDS_CAPACITY);
+    c->scene.pose_lds_joints = joints;
     return HIPR_OK;
 }
 

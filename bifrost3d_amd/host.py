@@ -35,6 +35,10 @@ def load_host_library() -> C.CDLL:
     lib.hiprh_scene_apply_staged.argtypes = [vp, C.c_double]
     lib.hiprh_vertex_geometry.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint, vp]
     lib.hiprh_scene_mesh_range.argtypes = [vp, C.c_uint, C.POINTER(C.c_uint)]
+    lib.hiprh_scene_set_rigs.argtypes = [vp, C.POINTER(C.c_uint), C.POINTER(capi.HiprRigDesc), C.c_uint]
+    lib.hiprh_scene_pose_rigs.argtypes = [vp, C.POINTER(capi.HiprRigPose), C.c_uint, C.c_double]
+    lib.hiprh_scene_stage_rig_poses.argtypes = [vp, C.POINTER(capi.HiprRigPose), C.c_uint, C.POINTER(capi.HiprRigPose)]
+    lib.hiprh_posed_geometry.argtypes = [C.POINTER(capi.HiprRigDesc), C.POINTER(capi.HiprRigPose), vp]
     lib.hiprh_scene_rebuild.argtypes = [vp]
     lib.hiprh_scene_stage_model.argtypes = [vp, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float]
     lib.hiprh_scene_adopt_trees.argtypes = [vp, vp, C.c_uint, vp, C.c_uint, vp, C.POINTER(capi.HiprWide8BuildResult)]
@@ -308,6 +312,54 @@ class Scene:
         if self.lib.hiprh_vertex_geometry(floats(positions), floats(normals), len(positions), C.c_void_p(out.ctypes.data)) != 0:
             raise capi.HiprError("hiprh_vertex_geometry failed")
         return out
+
+    def set_rigs(self, rigs) -> bool:
+        """SceneBuilder::set_rigs: the builder's rig set replaced. `rigs` as capi.rig_descs takes them, each with a `mesh` and its `first` MESH-relative. False when
+        they were refused (nothing touched)."""
+        rigs = list(rigs)
+        array, keep = capi.rig_descs(rigs)
+        status = self.lib.hiprh_scene_set_rigs(self.handle, (C.c_uint * max(len(rigs), 1))(*[int(r["mesh"]) for r in rigs]), array, len(rigs))
+        if status < 0:
+            raise capi.HiprError("hiprh_scene_set_rigs failed")
+        return status == 1
+
+    def pooled_rigs(self, rigs):
+        """Mesh-relative rigs in POOL coordinates, what Context.set_scene_rigs takes."""
+        return [dict({k: v for k, v in r.items() if k != "mesh"}, first=self.mesh_range(r["mesh"])["vertex_offset"] + r["first"]) for r in rigs]
+
+    def pose_rigs(self, poses, rebuild_threshold: float = 0.0):
+        """SceneBuilder::pose_rigs, the whole host path: `poses` as capi.rig_poses takes them. True when the topology was kept, False when the builder rebuilt the
+        scene, None when the poses were refused (nothing touched)."""
+        poses = list(poses)
+        array, keep = capi.rig_poses(poses)
+        status = self.lib.hiprh_scene_pose_rigs(self.handle, array, len(poses), rebuild_threshold)
+        if status == -1:
+            raise capi.HiprError("hiprh_scene_pose_rigs failed")
+        return None if status == -2 else status == 1
+
+    def stage_rig_poses(self, poses):
+        """SceneBuilder::stage_rig_poses: the latest pose of each rig recorded and its instances marked as staged, nothing skinned -- `desc` must not be read until
+        apply_staged(), rebuild() or an adoption has caught up. Returns the poses as Context.pose_scene_rigs takes them, or None when they were refused."""
+        poses = list(poses)
+        array, keep = capi.rig_poses(poses)
+        pooled = (capi.HiprRigPose * max(len(poses), 1))()
+        status = self.lib.hiprh_scene_stage_rig_poses(self.handle, array, len(poses), pooled)
+        if status < 0:
+            raise capi.HiprError("hiprh_scene_stage_rig_poses failed")
+        if status != 1:
+            return None
+        return [dict(p, rig=int(pooled[k].rig)) for k, p in enumerate(poses)]
+
+    def posed_geometry(self, rig, pose):
+        """SceneBuilder::posed_geometry: the rows of one rig (a capi.rig_descs dict; `first` is not read) under one pose (a capi.rig_poses dict; `rig` is not read) as
+        records of capi.vertex_geometry_dtype(), or None when the rig or the pose is refused."""
+        rigs, keep_rig = capi.rig_descs([dict(rig, first=0)])
+        poses, keep_pose = capi.rig_poses([dict(pose, rig=0)])
+        out = np.zeros(max(int(rigs[0].vertex_count), 1), capi.vertex_geometry_dtype())
+        status = self.lib.hiprh_posed_geometry(rigs, poses, C.c_void_p(out.ctypes.data))
+        if status < 0:
+            raise capi.HiprError("hiprh_posed_geometry failed")
+        return out[:int(rigs[0].vertex_count)] if status == 1 else None
 
     def mesh_range(self, mesh: int) -> dict:
         """Where a mesh lies in the pools: vertex_offset, vertex_count, index_offset (in triples), primitive_count, flags."""

@@ -354,6 +354,7 @@ bool SceneBuilder::stage_model_transforms(const std::vector<std::pair<uint32_t, 
 }
 
 void SceneBuilder::rebuild() {
+    apply_staged_poses();
     m_staged = false; m_staged_flips = false;
     m_staged_moved.assign(m_instances.size(), false);
     for (size_t i = 0; i < m_instances.size(); ++i) m_instances[i].index_offset = index_offset_for(m_instance_mesh[i], m_instances[i].object_to_world);
@@ -368,6 +369,7 @@ bool SceneBuilder::update_model_transforms(const std::vector<std::pair<uint32_t,
 
 bool SceneBuilder::apply_staged_transforms(double rebuild_threshold) {
     if (!m_staged) return true;
+    apply_staged_poses();
     if (has_staged_edits()) { rebuild(); return false; }      // another set of triangles: nothing to refit
     const std::vector<bool> moved = m_staged_moved;
     const bool flips = m_staged_flips;
@@ -401,6 +403,7 @@ bool SceneBuilder::write_vertex_edits(const std::vector<VertexEdit>& edits, std:
             if (e.texcoords && !(std::isfinite(e.texcoords[2 * size_t(v)]) && std::isfinite(e.texcoords[2 * size_t(v) + 1]))) return false;
         }
     }
+    apply_staged_poses();      // a staged pose lands first, so that what is written now wins over it: the catch-up must not replay it over these rows
     std::vector<bool> moved_mesh(m_meshes.size(), false), mapped_mesh(m_meshes.size(), false);
     bool any_mapped = false;
     for (const VertexEdit& e : edits) {
@@ -435,6 +438,92 @@ bool SceneBuilder::update_vertices(const std::vector<VertexEdit>& edits, double 
 }
 
 bool SceneBuilder::stage_vertex_edits(const std::vector<VertexEdit>& edits, std::vector<HiprVertexEdit>& pool_edits) { return write_vertex_edits(edits, &pool_edits); }
+
+bool SceneBuilder::set_rigs(const std::vector<RigDesc>& rigs) {
+    if (!m_built) return false;
+    std::vector<HiprRigDesc> pooled;
+    std::vector<uint32_t> meshes;
+    for (const RigDesc& d : rigs) {
+        if (d.mesh >= m_meshes.size()) return false;
+        const MeshRecord& r = m_meshes[d.mesh];
+        if (uint64_t(d.rig.first_vertex) + d.rig.vertex_count > r.vertex_count || size_t(r.vertex_offset) + r.vertex_count > m_built_pools.vertices) return false;
+        if ((d.rig.rest_normals != nullptr) != ((r.flags & HIPR_MESH_NORMALS) != 0)) return false;
+        HiprRigDesc p = d.rig;
+        p.first_vertex += r.vertex_offset;
+        pooled.push_back(p);
+        meshes.push_back(d.mesh);
+    }
+    if (hipr::check_rig_descs(pooled.data(), uint32_t(pooled.size()), m_built_pools.vertices)) return false;
+    apply_staged_poses();      // poses of the rigs that go are not lost
+    m_rig_words.clear();
+    m_rig_records.assign(pooled.size(), hipr::PoseRig{});
+    m_rig_books.assign(pooled.size(), hipr::RigBook{});
+    for (size_t k = 0; k < pooled.size(); ++k) hipr::pack_rig(pooled[k], m_rig_words, m_rig_records[k], m_rig_books[k]);
+    m_rig_mesh = meshes;
+    m_staged_poses.assign(pooled.size(), StagedPose{});
+    return true;
+}
+
+void SceneBuilder::pose_rig_rows(uint32_t rig, const float* matrices, const float* weights, HiprVertexGeometry* out) const {
+    const hipr::PoseRigView view = hipr::view_of(m_rig_records[rig], m_rig_words.data());
+    for (uint32_t v = 0; v < view.vertex_count; ++v) out[v] = hipr::pose_vertex(view, v, matrices, 12u, weights);
+}
+
+void SceneBuilder::apply_staged_poses() {
+    for (size_t k = 0; k < m_staged_poses.size(); ++k) {
+        StagedPose& p = m_staged_poses[k];
+        if (!p.staged) continue;
+        pose_rig_rows(uint32_t(k), p.matrices.data(), p.weights.data(), m_geometry.data() + m_rig_books[k].first_vertex);
+        p = StagedPose{};
+    }
+}
+
+bool SceneBuilder::pose_rigs(const std::vector<HiprRigPose>& poses, double rebuild_threshold, bool* refused) {
+    if (refused) *refused = true;
+    if (!m_built || has_staged_edits() || hipr::check_rig_poses(poses.data(), uint32_t(poses.size()), m_rig_books.data(), m_rig_books.size())) return false;
+    std::vector<std::vector<HiprVertexGeometry>> rows(poses.size());
+    std::vector<VertexEdit> edits;
+    for (size_t k = 0; k < poses.size(); ++k) {
+        const hipr::RigBook& b = m_rig_books[poses[k].rig];
+        rows[k].resize(b.vertex_count);
+        pose_rig_rows(poses[k].rig, poses[k].joint_matrices, poses[k].target_weights, rows[k].data());
+        const uint32_t mesh = m_rig_mesh[poses[k].rig];
+        edits.push_back({mesh, b.first_vertex - m_meshes[mesh].vertex_offset, b.vertex_count, rows[k].data(), nullptr, nullptr, nullptr});
+    }
+    return update_vertices(edits, rebuild_threshold, refused);
+}
+
+bool SceneBuilder::stage_rig_poses(const std::vector<HiprRigPose>& poses, std::vector<HiprRigPose>& pool_poses) {
+    if (!m_built || has_staged_edits() || hipr::check_rig_poses(poses.data(), uint32_t(poses.size()), m_rig_books.data(), m_rig_books.size())) return false;
+    if (m_staged_moved.size() != m_instances.size()) m_staged_moved.assign(m_instances.size(), false);
+    for (const HiprRigPose& p : poses) {
+        const hipr::RigBook& b = m_rig_books[p.rig];
+        StagedPose& s = m_staged_poses[p.rig];
+        s.staged = true;
+        s.matrices.assign(p.joint_matrices, p.joint_matrices + (b.joint_count ? 12u * size_t(b.joint_count) : 0u));
+        s.weights.assign(p.target_weights, p.target_weights + (b.target_count ? b.target_count : 0u));
+        for (size_t i = 0; i < m_instances.size(); ++i)
+            if (m_instance_mesh[i] == m_rig_mesh[p.rig]) { m_staged_moved[i] = true; m_staged = true; }
+        pool_poses.push_back(p);
+    }
+    return true;
+}
+
+bool SceneBuilder::posed_geometry(const HiprRigDesc& rig, const HiprRigPose& pose, HiprVertexGeometry* out) {
+    HiprRigDesc alone = rig;
+    alone.first_vertex = 0;
+    HiprRigPose p = pose;
+    p.rig = 0;
+    if (!out || hipr::check_rig_descs(&alone, 1, alone.vertex_count)) return false;
+    std::vector<uint32_t> words;
+    hipr::PoseRig record;
+    hipr::RigBook book;
+    hipr::pack_rig(alone, words, record, book);
+    if (hipr::check_rig_poses(&p, 1, &book, 1)) return false;
+    const hipr::PoseRigView view = hipr::view_of(record, words.data());
+    for (uint32_t v = 0; v < view.vertex_count; ++v) out[v] = hipr::pose_vertex(view, v, pose.joint_matrices, 12u, pose.target_weights);
+    return true;
+}
 
 // The world-space corners of the triangles of the instances flagged in `moved`, recomputed in place from the instances' matrices, and the scene's bounds.
 void SceneBuilder::move_triangles(const std::vector<bool>& moved) {
@@ -514,6 +603,7 @@ bool SceneBuilder::trees_fit(uint32_t n, const HiprBvhNode* nodes, uint32_t node
 bool SceneBuilder::adopt_rebuilt_trees(const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, uint32_t deepest, const HiprSlot8* slots, const HiprWide8BuildResult& wide8) {
     const uint32_t n = uint32_t(m_triangles.size());
     auto refuse = [&] { ++m_rebuild_counts.refused; return false; };
+    apply_staged_poses();      // the pools are the source data: staged poses reach them whatever follows
     // counts that do not fit; an instance turned inside out is drawn from other index triples, which changes the set of triangles -- and so does an edited instance list
     if (m_bvh.order.size() != n || m_staged_flips || has_staged_edits() || !trees_fit(n, nodes, node_count, order, slots, wide8)) return refuse();
     // everything staged reaches the builder's own triangles, without a refit of trees that are about to be replaced and without a flatten
@@ -602,6 +692,7 @@ bool SceneBuilder::list_instance_edits(std::vector<HiprInstanceEdit>& edits) con
 }
 
 bool SceneBuilder::adopt_edited_trees(const HiprBvhNode* nodes, uint32_t node_count, const uint32_t* order, uint32_t order_count, uint32_t deepest, const HiprSlot8* slots, const HiprWide8BuildResult& wide8) {
+    apply_staged_poses();      // the pools are the source data: staged poses reach them whatever follows
     auto refuse = [&] { ++m_rebuild_counts.refused; return false; };
     std::vector<HiprInstanceEdit> unused;
     StagedGrowth unused_growth;

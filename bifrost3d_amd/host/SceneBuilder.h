@@ -6,6 +6,7 @@
 
 #include "BvhBuilder.h"
 #include "Math.h"
+#include "../csrc/vertex_pose.h"      // the rigs: ONE text of the pose arithmetic with the device's kernel
 
 #include <cassert>
 #include <cstdint>
@@ -185,6 +186,28 @@ public:
     bool update_vertices(const std::vector<VertexEdit>& edits, double rebuild_threshold = 1.5, bool* refused = nullptr);
     bool stage_vertex_edits(const std::vector<VertexEdit>& edits, std::vector<HiprVertexEdit>& pool_edits);
     static HiprVertexGeometry vertex_geometry(Vector3f position, const Vector3f* normal);      // null: no normal, as a mesh without normals holds it
+    // Rigs over meshes of a BUILT scene (what hipr_set_scene_rigs binds on the device) and their poses (csrc/vertex_pose.h: morph targets, linear-blend skinning,
+    // normals through the upper 3x3, normalised and encoded as add_mesh encodes them). set_rigs REPLACES the set; a rig's `first_vertex` is MESH-relative here. The
+    // builder keeps its own copies in the resident layout. False, nothing touched: before the scene is built, a mesh the scene does not hold or the device does not
+    // hold yet, a range past the mesh, rest normals for a mesh without HIPR_MESH_NORMALS or none for a mesh with them, and everything hipr_set_scene_rigs refuses
+    // (hipr::check_rig_descs). The rigs stay until the next set_rigs: the pools only grow. Rig k of the list is rig k of the device when both were given the same
+    // list -- after hipr_upload_scene the device's set is bound again.
+    // pose_rigs is the whole host path: the rows of every pose computed with the header's text, then update_vertices on them -- true = topology kept (desc() is then
+    // what hipr_pose_scene_rigs leaves on the device), false = the scene was rebuilt, or, with *refused set, nothing was touched: what update_vertices refuses about
+    // the builder's state and everything hipr_pose_scene_rigs refuses about the poses (hipr::check_rig_poses).
+    // stage_rig_poses is the device path's companion: it does NOT skin. It records the LATEST pose of each rig (copies of the matrices and weights), marks the
+    // instances over those meshes as staged and appends the poses as the device takes them to `pool_poses`; apply_staged_transforms(), rebuild() or an adoption
+    // skins from the recorded poses before the pools are next read -- correct because a posed vertex depends on the rest data and the pose alone. Every other
+    // writer of the geometry pool (update_vertices, stage_vertex_edits, pose_rigs, set_rigs) skins the recorded poses FIRST and writes then: the later write wins, as
+    // on the device, where the pose has long been applied.
+    struct RigDesc { uint32_t mesh; HiprRigDesc rig; };
+    bool set_rigs(const std::vector<RigDesc>& rigs);
+    bool pose_rigs(const std::vector<HiprRigPose>& poses, double rebuild_threshold = 1.5, bool* refused = nullptr);
+    bool stage_rig_poses(const std::vector<HiprRigPose>& poses, std::vector<HiprRigPose>& pool_poses);
+    size_t rig_count() const { return m_rig_books.size(); }
+    // The HiprVertexGeometry rows of one rig under one pose (rig.vertex_count of them; rig.first_vertex is not read): false when the rig or the pose is one the
+    // device refuses.
+    static bool posed_geometry(const HiprRigDesc& rig, const HiprRigPose& pose, HiprVertexGeometry* out);
     // vertex_offset, vertex_count, index_offset (in triples), primitive_count and flags of a mesh; false for a mesh the scene does not hold
     bool mesh_range(uint32_t mesh, uint32_t (&out)[5]) const;
     const std::vector<HiprMaterial>& materials() const { return m_materials; }
@@ -255,6 +278,15 @@ private:
     bool record_model_transforms(const std::vector<std::pair<uint32_t, Transform>>& model_transforms, std::vector<HiprInstanceTransform>* moved_instances);
     bool m_staged = false, m_staged_flips = false;      // transforms recorded in m_instances that m_triangles / m_bvh do not carry yet
     std::vector<bool> m_staged_moved;
+    // The bound rigs in the resident layout (csrc/vertex_pose.h pack_rig), pool coordinates; the mesh of each; the latest staged pose of each (empty: none).
+    std::vector<uint32_t> m_rig_words;
+    std::vector<hipr::PoseRig> m_rig_records;
+    std::vector<hipr::RigBook> m_rig_books;
+    std::vector<uint32_t> m_rig_mesh;
+    struct StagedPose { bool staged = false; std::vector<float> matrices, weights; };
+    std::vector<StagedPose> m_staged_poses;
+    void pose_rig_rows(uint32_t rig, const float* matrices, const float* weights, HiprVertexGeometry* out) const;
+    void apply_staged_poses();      // the recorded poses skinned into m_geometry
     std::vector<MeshRecord> m_meshes;
     std::vector<uint32_t> m_indices;
     std::vector<HiprVertexGeometry> m_geometry;

@@ -420,6 +420,46 @@ int hiprh_scene_mesh_range(void* scene, unsigned mesh, unsigned* out5) {
     return 1;
 }
 
+// SceneBuilder::set_rigs: rig k lies over mesh meshes[k], its first_vertex MESH-relative. Returns 1, 0 when refused (nothing touched), -1 on error.
+int hiprh_scene_set_rigs(void* scene, const unsigned* meshes, const HiprRigDesc* rigs, unsigned count) {
+    if (!scene || (count && (!meshes || !rigs))) return -1;
+    try {
+        std::vector<SceneBuilder::RigDesc> list(count);
+        for (unsigned k = 0; k < count; ++k) list[k] = {meshes[k], rigs[k]};
+        return static_cast<SceneBuilder*>(scene)->set_rigs(list) ? 1 : 0;
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_set_rigs: %s\n", e.what()); return -1; }
+}
+
+// SceneBuilder::pose_rigs, the whole host path. Returns 1 when the topology was kept, 0 when the scene was rebuilt, -2 when the poses were refused (nothing
+// touched), -1 on error.
+int hiprh_scene_pose_rigs(void* scene, const HiprRigPose* poses, unsigned count, double rebuild_threshold) {
+    if (!scene) return -1;
+    try {
+        bool refused = false;
+        const bool kept = static_cast<SceneBuilder*>(scene)->pose_rigs(std::vector<HiprRigPose>(poses, poses + (poses ? count : 0u)), rebuild_threshold > 0.0 ? rebuild_threshold : 1.5, &refused);
+        return refused || (count && !poses) ? -2 : (kept ? 1 : 0);
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_pose_rigs: %s\n", e.what()); return -1; }
+}
+
+// SceneBuilder::stage_rig_poses: the latest pose of each rig recorded, nothing skinned (hiprh_scene_desc must not be asked until hiprh_scene_apply_staged,
+// hiprh_scene_rebuild or an adoption has caught up); out_pool_poses[0 .. count) are the poses as hipr_pose_scene_rigs takes them. Returns 1, 0 when refused.
+int hiprh_scene_stage_rig_poses(void* scene, const HiprRigPose* poses, unsigned count, HiprRigPose* out_pool_poses) {
+    if (!scene || (count && (!poses || !out_pool_poses))) return -1;
+    try {
+        std::vector<HiprRigPose> pool_poses;
+        if (!static_cast<SceneBuilder*>(scene)->stage_rig_poses(std::vector<HiprRigPose>(poses, poses + count), pool_poses)) return 0;
+        std::copy(pool_poses.begin(), pool_poses.end(), out_pool_poses);
+        return 1;
+    } catch (const std::exception& e) { fprintf(stderr, "hiprh_scene_stage_rig_poses: %s\n", e.what()); return -1; }
+}
+
+// SceneBuilder::posed_geometry: the rows of one rig under one pose, rig->vertex_count of them. Returns 1, 0 when the rig or the pose is refused, -1 on error.
+int hiprh_posed_geometry(const HiprRigDesc* rig, const HiprRigPose* pose, HiprVertexGeometry* out) {
+    if (!rig || !pose || !out) return -1;
+    try { return SceneBuilder::posed_geometry(*rig, *pose, out) ? 1 : 0; }
+    catch (const std::exception& e) { fprintf(stderr, "hiprh_posed_geometry: %s\n", e.what()); return -1; }
+}
+
 // SceneBuilder::rebuild: a fresh tree over the instances and materials as they stand. Returns 0, -1 on error.
 int hiprh_scene_rebuild(void* scene) {
     if (!scene) return -1;

@@ -306,6 +306,36 @@ class Context:
                     grid_min=np.array(refit.grid_min[:], np.float32), grid_cell=np.array(refit.grid_cell[:], np.float32), moved_triangles=result.moved_triangles,
                     candidate_triangles=result.candidate_triangles, changed_triangles=result.changed_triangles, all_triangles_opaque=bool(result.all_triangles_opaque))
 
+    def set_scene_rigs(self, rigs, group=None) -> int:
+        """hipr_set_scene_rigs: the resident rig set replaced (an empty list removes all rigs). `rigs` as capi.rig_descs takes them, `first` in POOL coordinates.
+        Returns the status: a refusal leaves the bound set and the scene as found. `group`: a HiprGroup handle, for hipr_group_set_scene_rigs."""
+        rigs = list(rigs)
+        array, keep = capi.rig_descs(rigs)
+        call, handle = (self.lib.hipr_group_set_scene_rigs, group) if group is not None else (self.lib.hipr_set_scene_rigs, self.handle)
+        return call(handle, array, len(rigs))
+
+    def pose_scene_rigs(self, poses, group=None) -> dict:
+        """hipr_pose_scene_rigs: bound rigs posed by one kernel, then what update_scene_vertices runs after an edit of geometry. `poses` as capi.rig_poses takes
+        them. Returns a dict shaped like update_scene_vertices'. `group`: a HiprGroup handle, for hipr_group_pose_scene_rigs."""
+        poses = list(poses)
+        array, keep = capi.rig_poses(poses)
+        result = capi.HiprVertexUpdateResult()
+        call, handle = (self.lib.hipr_group_pose_scene_rigs, group) if group is not None else (self.lib.hipr_pose_scene_rigs, self.handle)
+        status = call(handle, array, len(poses), C.byref(result))
+        if status != capi.HIPR_OK:
+            return dict(status=status)
+        refit = result.refit
+        return dict(status=status, needs_rebuild=bool(refit.needs_rebuild), child_half_area=refit.child_half_area, uploaded_half_area=refit.uploaded_half_area,
+                    grid_min=np.array(refit.grid_min[:], np.float32), grid_cell=np.array(refit.grid_cell[:], np.float32), moved_triangles=result.moved_triangles,
+                    candidate_triangles=result.candidate_triangles, changed_triangles=result.changed_triangles, all_triangles_opaque=bool(result.all_triangles_opaque))
+
+    def vertex_pose_times(self) -> dict:
+        """Milliseconds of the last pose_scene_rigs: the block table, matrices and weights packed and their staging copy, the pose kernel, the refit passes with the
+        records."""
+        out = (C.c_double * 4)()
+        self._check(self.lib.hipr_debug_vertex_pose_times(self.handle, out), "hipr_debug_vertex_pose_times")
+        return dict(staging=out[0], pose=out[1], refit=out[2])
+
     def vertex_update_times(self) -> dict:
         """Milliseconds of the last update_scene_vertices: the table and rows packed and their staging copy, the pool writes, the refit passes with the records, the
         flag pass with the leaf pass."""

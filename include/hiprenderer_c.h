@@ -670,6 +670,53 @@ typedef struct HiprVertexUpdateResult {
     uint32_t candidate_triangles, changed_triangles, all_triangles_opaque;   /* as HiprTexelUpdateResult */
 } HiprVertexUpdateResult;
 int hipr_update_scene_vertices(HiprContext* context, const HiprVertexEdit* edits, uint32_t edit_count, HiprVertexUpdateResult* out);
+/* Skinned and morphed meshes of the RESIDENT scene posed on the device (csrc/vertex_pose.h). hipr_update_scene_vertices takes FINISHED vertices: an animated mesh
+ * would be skinned, its normals encoded and 16 bytes per vertex copied across every frame. A rig keeps what does not change -- rest positions and normals, joint
+ * indices and weights, morph-target deltas -- on the device; a pose is joint_count 3x4 matrices and target_count weights, and one kernel writes the posed vertices
+ * into the geometry pool. The arithmetic is the fixed chain of csrc/vertex_pose.h (morph targets in index order, linear-blend skinning over four slots, normals
+ * through the upper 3x3 -- not the inverse transpose -- normalised and encoded as add_mesh encodes them), the same text SceneBuilder::pose_rigs runs.
+ *
+ * hipr_set_scene_rigs REPLACES the resident rig set (count 0 removes all rigs); the device keeps its own copies of every array. A rig is a range of the RESIDENT
+ * geometry pool, as in HiprVertexEdit. hipr_upload_scene drops the rigs (ranges are pool coordinates); hipr_update_scene_geometry, the refit, material, lighting,
+ * texel, vertex and instance edits, hipr_append_scene_pools and hipr_rebuild_scene_trees keep them: none moves a pool vertex. Refused before anything is touched:
+ *   HIPR_ERROR_NOT_READY          no scene, a scene a failed call left behind, or a scene awaiting a rebuild;
+ *   HIPR_ERROR_INVALID_ARGUMENT   null `rigs` with a non-zero count; a rig with `vertex_count` 0, a range past the resident pool, neither joints nor targets, more than
+ *                                 65536 joints or 256 targets, a null array where a count asks for data; two rigs whose ranges overlap; a joint index >= joint_count;
+ *                                 a weight outside [0, 1] or not finite; a vertex whose four weights are all 0 while joint_count > 0; a rest position or a target
+ *                                 delta that is not finite or above 2^30 in magnitude; a rest normal that is not finite or whose squared length is not finite and > 0.
+ * The new set is allocated and copied before the old one is let go: HIPR_ERROR_OUT_OF_MEMORY leaves the old set bound. */
+typedef struct HiprRigDesc {
+    uint32_t first_vertex;                 /* index into the RESIDENT vertex pools */
+    uint32_t vertex_count;                 /* > 0 */
+    uint32_t joint_count;                  /* 0: no skin */
+    uint32_t target_count;                 /* 0 .. 256 morph targets */
+    const float*    rest_positions;        /* float3 per vertex */
+    const float*    rest_normals;          /* float3 per vertex, or NULL: a mesh without HIPR_MESH_NORMALS, oct_normal stays {0, 0} */
+    const uint16_t* joints;                /* 4 per vertex, each < joint_count (joint_count > 0) */
+    const float*    weights;               /* 4 per vertex, each in [0, 1], not all 0 (joint_count > 0); a slot of weight 0 is skipped */
+    const float*    target_positions;      /* target-major float3 deltas: target_count x vertex_count (target_count > 0) */
+    const float*    target_normals;        /* the same for normals, or NULL */
+} HiprRigDesc;
+int hipr_set_scene_rigs(HiprContext* context, const HiprRigDesc* rigs, uint32_t count);
+/* hipr_pose_scene_rigs poses bound rigs: ONE launch whatever the number of poses, then exactly what hipr_update_scene_vertices runs after an edit of geometry (the
+ * moved triangles, the bounds and the grid, the refit of the 8-wide tree, the records; `out` is filled as there, candidate_triangles and changed_triangles are 0).
+ * Afterwards the device holds, byte for byte, what SceneBuilder::pose_rigs and a fresh upload leave, and what hipr_update_scene_vertices leaves when it is given
+ * SceneBuilder::posed_geometry. A posed vertex depends on the rest data and the pose alone, never on what the pool held. An empty list is HIPR_OK and reports what
+ * is resident. `refit.needs_rebuild` = 1 leaves the scene awaiting hipr_rebuild_scene_trees, as there. Joint matrices map OBJECT space to OBJECT space: the caller
+ * has multiplied in the inverse bind matrix and the mesh's inverse world transform. Refused before anything is touched:
+ *   HIPR_ERROR_NOT_READY          as above;
+ *   HIPR_ERROR_INVALID_ARGUMENT   a null `out`; null `poses` with a non-zero count; a rig index that is not bound; the same rig twice in one call; a null array that
+ *                                 the rig needs; a matrix entry that is not finite or above 2^30 in magnitude; a target weight that is not finite or above 2^10 in
+ *                                 magnitude (with these bounds no posed position can overflow: csrc/vertex_pose.h);
+ *   HIPR_ERROR_UNSUPPORTED        what hipr_refit_scene_transforms refuses, as hipr_update_scene_vertices.
+ * Scratch is allocated before anything resident is written: HIPR_ERROR_OUT_OF_MEMORY leaves the scene as found. */
+typedef struct HiprRigPose {
+    uint32_t rig;                          /* index into the bound rig set */
+    uint32_t reserved;                     /* 0 */
+    const float* joint_matrices;           /* joint_count x 12 floats, row-major 3x4 (joint_count > 0) */
+    const float* target_weights;           /* target_count floats (target_count > 0); a weight of exactly 0 skips its target */
+} HiprRigPose;
+int hipr_pose_scene_rigs(HiprContext* context, const HiprRigPose* poses, uint32_t pose_count, HiprVertexUpdateResult* out);
 int hipr_set_scene_state(HiprContext* context, const HiprSceneState* state);
 
 /* Entry points, numbered like OR/Types.h:33-44. set_backend() of the host renderer maps Backend values onto them
@@ -768,6 +815,8 @@ int hipr_group_update_scene_lighting(HiprGroup* group, const HiprLight* lights, 
                                      HiprLightingResult* out);   /* every member checks before any member writes; member 0's arrays are handed out; their results must agree */
 int hipr_group_update_scene_texels(HiprGroup* group, const HiprTexelEdit* edits, uint32_t edit_count, HiprTexelUpdateResult* out);   /* every member checks before any member writes */
 int hipr_group_update_scene_vertices(HiprGroup* group, const HiprVertexEdit* edits, uint32_t edit_count, HiprVertexUpdateResult* out);   /* every member checks before any member writes */
+int hipr_group_set_scene_rigs(HiprGroup* group, const HiprRigDesc* rigs, uint32_t count);   /* every member checks before any member writes */
+int hipr_group_pose_scene_rigs(HiprGroup* group, const HiprRigPose* poses, uint32_t pose_count, HiprVertexUpdateResult* out);   /* every member checks before any member writes */
 int hipr_group_update_scene_materials(HiprGroup* group, const HiprMaterialUpdate* materials, uint32_t material_count,
                                       const HiprInstanceMaterial* assignments, uint32_t assignment_count);   /* every member checks before any member writes */
 int hipr_group_set_scene_state(HiprGroup* group, const HiprSceneState* state);
@@ -962,6 +1011,14 @@ int hipr_debug_texel_update_times(HiprContext* context, double* out4_ms);
  * clock), the pool writes with the marks, the moved triangles with the refit passes and the records, the flag pass with the leaf pass (each between events on the
  * stream: the call does not synchronise for them) (tools/vertex_update_probe.py). */
 int hipr_debug_vertex_update_times(HiprContext* context, double* out4_ms);
+/* ... and for the context's last successful hipr_pose_scene_rigs that did any work: the block table, matrices and weights packed and their staging copy queued (the
+ * host's clock), the pose kernel with the marks, the moved triangles with the refit passes and the records (each between events on the stream), and 0
+ * (tools/vertex_pose_probe.py). */
+int hipr_debug_vertex_pose_times(HiprContext* context, double* out4_ms);
+/* The LDS budget of the pose kernel in joints for this context's next poses (32 when the context is made): a rig with more joints gathers its matrices from global
+ * memory. 0: every rig gathers. Refuses a value above the kernel's capacity of 320 (HIPR_ERROR_INVALID_ARGUMENT). For measurements and tests: both paths give the
+ * same bytes. */
+int hipr_debug_set_pose_lds_joints(HiprContext* context, uint32_t joints);
 
 #ifdef __cplusplus
 }
